@@ -7,8 +7,18 @@ examples/quadrotor_hovering.cpp, warm-started from the previous step, plant adva
 The timed region always starts from the cold state of tiny_setup, so K steps = the first K steps of
 the reference's 100-step episode (K = 100 -> 882 ADMM iterations per instance).
 State is resident in HBM before timing starts.  The K-step region is repeated (cold start, barrier,
-K steps, statistics exchange, barrier) until at least --min-seconds of timed work has run; `value`
-comes from the MEDIAN repetition, min / max are reported beside it.
+K steps, statistics exchange, barrier).  A plain run times that region ONCE, so --steps is the number of
+timed steps and `ms_per_step` the time of one of them; under --full it is repeated until at least
+--min-seconds of timed work has run, `value` comes from the MEDIAN repetition, min / max are reported beside it.
+
+A plain run (no --full) does only what the headline needs: setup, --warmup steps, the --steps timed steps,
+--dump-outputs if asked for, the one JSON line.  --full adds everything else this script measures (the
+repetitions above, `regimes`, `configs`, `cpu_baseline`, `strong_scaling`, the details file described below).
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller after its LAST step goes to
+DIR/<name>.npy (float64, ~23 MB): solution x|u, the plant state advanced on the device, iteration count,
+solved flag and residuals of a fixed seeded sample of instances (all of them up to 16 384), and the job-wide
+statistics of the timed region.  The inputs are the same from run to run: two builds compare file by file.
 
 How it starts -- all three forms run the same code:
   python bench.py --gpus 1 ...                             one process, one GPU
@@ -26,10 +36,11 @@ Under weak scaling with N > 1 the strong-scaling form is measured as well, after
 `strong_scaling` in the same line.
 
 Output: stdout carries exactly ONE line, compact (compact_line: <= 4 KiB of strict JSON -- the contract's keys, `roofline`,
-`cpu_baseline`, a few numbers per regime and per `configs` entry); the full record described below goes to
-gpurun_out/bench_details.json (the line names it under `details`).
+`cpu_baseline`, a few numbers per regime and per `configs` entry); under --full (or with --details PATH) the full record
+described below goes to the details file (default: DETAILS_PATH below; the line names it under `details`).
 
-Rooflines (full record; the line keeps frac / achieved / peak / kernel / avg_launch_ms of each):
+Rooflines (full record; the line keeps frac / achieved / peak / kernel / avg_launch_ms of each; `roofline`, `roofline_hbm` and
+`roofline_fp64` come from the timed launches themselves and are in every run, the rest needs --full):
   roofline         the bound that BINDS the timed launches: FP64 VALU issue when the launches carry many
                    ADMM iterations (cold / fused steps), HBM when they are single warm steps; `traffic` = HBM
                    bytes per launch measured with rocprofv3 PMC passes (profiles/traffic.json, `traffic_source`)
@@ -283,8 +294,13 @@ def parse_args(argv=None):
                     help="closed-loop MPC steps fused into one kernel launch (ADMM state stays in registers); "
                          "0 = auto: the largest divisor of --steps that is <= 100; 1 = one launch per step")
     ap.add_argument("--opt", action="append", default=[], help="solver option name=value (experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repetitions until --min-seconds, regimes, configs, CPU baseline, strong scaling, "
+                         "the details file (a plain run times --steps steps once and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     ap.add_argument("--min-seconds", type=float, default=5.0,
-                    help="repeat the timed K-step region until this much timed work has run (median reported)")
+                    help="--full: repeat the timed K-step region until this much timed work has run (median reported)")
     ap.add_argument("--max-repeats", type=int, default=5000)
     ap.add_argument("--no-regimes", action="store_true", help="skip the untimed one-launch-per-step replay")
     ap.add_argument("--regimes", action="store_true", help="(kept for old command lines: the replay is always on)")
@@ -512,8 +528,9 @@ class Hover:
             st = self.stats.to("cpu")
         return elapsed, st.tolist(), s.timing_ms()
 
-    def measure(self, min_seconds, warmup=True):
-        """-> dict(elapsed median, rep_s, kernel ms arrays, job-wide statistics of one repetition)"""
+    def measure(self, min_seconds, warmup=True, repeat=True):
+        """-> dict(elapsed median, rep_s, kernel ms arrays, job-wide statistics of one repetition); repeat=False: exactly one
+        timed repetition (a plain run: --steps timed steps, nothing more)"""
         np, s, job, args = self.np, self.s, self.job, self.args
         with job.torch.cuda.stream(job.stream):
             if warmup:
@@ -528,7 +545,7 @@ class Hover:
                 job.barrier()
             e0, st, km = self.timed_repetition()
             e0 = job.max_over_ranks([e0])[0]
-            repeats = int(min(max(3, -(-min_seconds // max(e0, 1e-6))), args.max_repeats))
+            repeats = int(min(max(3, -(-min_seconds // max(e0, 1e-6))), args.max_repeats)) if repeat else 1
             rep_s, rep_kernel_ms = [e0], [km]
             for _ in range(repeats - 1):
                 e, st, km = self.timed_repetition()
@@ -543,6 +560,27 @@ class Hover:
         if self.exchange is not None:
             self.exchange.close()
         self.s.close()
+
+
+DUMP_SAMPLE = 16384          # instances --dump-outputs writes (a fixed, seeded sample of larger batches)
+
+
+def dump_outputs(hv, stats, out_dir):
+    """--dump-outputs: what the timed path handed its caller after its last step (solution x|u = vnew|znew, the plant state the
+    device advanced, iteration count, solved flag, residuals) for a fixed seeded sample of this rank's instances, and the job-wide
+    statistics of the timed region, as float64 DIR/<name>.npy.  At most DUMP_SAMPLE instances: ~23 MB at (12, 4, 10)."""
+    np, s, B = hv.np, hv.s, hv.B
+    s.synchronize()
+    idx = np.arange(B) if B <= DUMP_SAMPLE else np.sort(np.random.default_rng(0).choice(B, DUMP_SAMPLE, replace=False))
+    st = s.status()
+    arrays = {"sample_index": idx, "solution_x": s.get("vnew")[idx], "solution_u": s.get("znew")[idx], "x0_next": s.get("x0")[idx],
+              "iter": st["iter"][idx], "solved": st["solved"][idx],
+              "residuals": np.stack([st[k][idx] for k in ("primal_residual_state", "primal_residual_input", "dual_residual_state",
+                                                          "dual_residual_input")], axis=1),
+              "stats": np.asarray(stats)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def regimes_replay(hv, fl, bytes_warm, full=True, reps=5):
@@ -736,15 +774,17 @@ def run(args, result_fd, setup_done):
             job.barrier()
     enter_phase("measuring")
     nx, nu, N, T, launches = hv.nx, hv.nu, hv.N, hv.T, hv.launches
-    m = hv.measure(args.min_seconds)
+    m = hv.measure(args.min_seconds, repeat=args.full)
     elapsed, rep_s, st = m["elapsed"], m["rep_s"], m["st"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hv, st, args.dump_outputs)
     acc_iters, acc_solved, max_resid = st[7], st[8], st[3:7]        # job-wide, one repetition (each starts with a reset)
     kern_ms, kern_sum_rep = m["kern_ms"], m["kern_sum_rep"]
     fl = flops_per_iter(nx, nu, N)
     bytes_warm = hv.s.algorithmic_bytes(cold=False)
 
     regimes = None
-    if rank == 0 and not args.no_regimes:
+    if rank == 0 and args.full and not args.no_regimes:
         regimes = regimes_replay(hv, fl, bytes_warm)
         regimes["traffic_note"] = "roofline.traffic is a citation of a committed rocprofv3 PMC run (profiles/traffic.json), not of this run"
     exchange_kind = hv.exchange.kind if hv.exchange is not None else "none (one rank)"
@@ -762,7 +802,7 @@ def run(args, result_fd, setup_done):
 
     # N > 1 under weak scaling: the strong-scaling form of the metric as well (65 536 instances in TOTAL, sharded)
     strong_extra = None
-    if world > 1 and not strong and not args.no_strong:
+    if args.full and world > 1 and not strong and not args.no_strong:
         hs = Hover(job, args, shard_size(args.batch, rank, world), args.batch)
         ms_ = hs.measure(min(args.min_seconds, 2.0))
         sst = ms_["st"]
@@ -773,7 +813,7 @@ def run(args, result_fd, setup_done):
         hs.close()
 
     configs, spec_path = None, None
-    if rank == 0 and world == 1 and not args.no_configs:
+    if rank == 0 and world == 1 and args.full and not args.no_configs:
         import tempfile
         import bench_configs
         spec_path = os.path.join(tempfile.mkdtemp(prefix="tinympc_bench_"), "config_samples.pkl")
@@ -784,7 +824,7 @@ def run(args, result_fd, setup_done):
     # CPU baseline LAST (rank 0, N = 1 only): the real reference on every host core, the SAME workload as the timed region
     cpu = None
     cpu_phase_s = check_phase_s = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         t_cpu = time.perf_counter()
         cpu = cpu_baseline_subprocess(args.cpu_seconds, args.steps)
         cpu_phase_s = time.perf_counter() - t_cpu
@@ -862,7 +902,7 @@ def run(args, result_fd, setup_done):
         if cpu is not None:
             out["cpu_baseline"] = cpu
         out["wall_seconds"] = _r(time.perf_counter() - t_start, 4)
-        details = write_details(out, args.details)
+        details = write_details(out, args.details) if (args.full or args.details) else None
         sys.stdout.flush()
         os.write(result_fd, (compact_line(out, details) + "\n").encode())
     enter_phase("finished")

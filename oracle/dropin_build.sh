@@ -1,16 +1,17 @@
 #!/bin/bash
 # Drop-in boundary check: compile the REFERENCE's own example mains
 # (by path, nothing copied) against the REFERENCE's headers, but link them against
-# libtinympc_amd.so instead of libtinympcstatic.a.  Needs /root/reference, so it only runs in the
-# build container; the binaries land in tests/dropin/_build/ (git-ignored, travel to the GPU box).
-#   build.sh           -> tests/dropin/_build/<example>          (linked against OUR library)
-#   build.sh --golden  -> also builds each example against the real reference sources and records
-#                         its stdout in tests/golden/stdout_<example>.txt
+# libtinympc_amd.so instead of libtinympcstatic.a.  Needs the reference sources ($TINYMPC_REFERENCE),
+# so it only does something where they exist; the binaries land in oracle/_ref/dropin/ (git-ignored,
+# shipped with the tree like the rest of oracle/_ref/).  Our own callers are tests/dropin/*.cpp.
+#   dropin_build.sh           -> oracle/_ref/dropin/<example>   (linked against OUR library)
+#   dropin_build.sh --golden  -> also builds each example against the real reference sources and records
+#                                its stdout in tests/golden/stdout_<example>.txt
 set -e
-HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(cd "$HERE/../.." && pwd)
+ROOT=$(cd "$(dirname "$0")/.." && pwd); HERE=$ROOT/tests/dropin
 REF=${TINYMPC_REFERENCE:-/root/reference}
 [ -d "$REF/examples" ] || { echo "no $REF: keeping prebuilt binaries"; exit 0; }
-OUT=$HERE/_build; mkdir -p "$OUT"
+OUT=$ROOT/oracle/_ref/dropin; mkdir -p "$OUT"
 INC="-I$REF/src -I$REF/include/Eigen -I$REF/include -I$REF/examples"
 # default alignment flags on purpose: Eigen must use plain malloc/free (SURVEY.md 8(b) ownership row)
 CXXFLAGS="-O2 -DNDEBUG -std=c++17 -w"

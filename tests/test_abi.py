@@ -47,9 +47,9 @@ def test_struct_sizes_match_reference_layout():
         assert getattr(W, name).offset == off, name
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/src/tinympc"), reason="needs the reference headers")
 def test_layout_against_the_real_reference_header(tmp_path):
-    """offsetof/sizeof from the reference's OWN types.hpp vs the plain-data mirrors of our header."""
+    """offsetof/sizeof from the reference's OWN types.hpp vs the plain-data mirrors of our header.  The reference's figures are
+    kept in tests/golden/layout_reference.txt; where the reference headers exist they are measured again and must equal it."""
     fields = ["x", "u", "vnew", "x_min", "numStateCones", "cx", "Acx", "vc", "numStateLinear", "Alin_x", "blin_x", "vl",
               "numtvStateLinear", "tv_Alin_x", "vl_tv", "Q", "R", "Adyn", "fdyn", "Xref", "Uref", "Qu",
               "primal_residual_state", "status", "iter"]
@@ -57,15 +57,19 @@ def test_layout_against_the_real_reference_header(tmp_path):
     prog = ("#include <cstdio>\n#include <cstddef>\n#include \"@INC@\"\nint main(){"
             "printf(\"sizes %zu %zu %zu %zu %zu\\n\", sizeof(TinySolution), sizeof(TinyCache), sizeof(TinySettings),"
             " sizeof(TinyWorkspace), sizeof(TinySolver));" + body + "return 0;}")
+    builds = [("ours", HEADER, [])]
+    if os.path.isdir(REF + "/src/tinympc"):
+        builds.append(("ref", "tinympc/types.hpp", ["-I" + REF + "/src", "-I" + REF + "/include/Eigen", "-I" + REF + "/include"]))
     outs = []
-    for tag, inc, flags in (("ref", "tinympc/types.hpp", ["-I" + REF + "/src", "-I" + REF + "/include/Eigen", "-I" + REF + "/include"]),
-                            ("ours", HEADER, [])):
+    for tag, inc, flags in builds:
         src = tmp_path / f"{tag}.cpp"
         src.write_text(prog.replace("@INC@", inc))
         exe = tmp_path / tag
         subprocess.check_call(["g++", "-std=c++17", "-w", "-Wno-invalid-offsetof", *flags, str(src), "-o", str(exe)])
         outs.append(subprocess.check_output([str(exe)]).decode())
-    assert outs[0] == outs[1], f"layout drift:\n{outs[0]}\nvs\n{outs[1]}"
+    gold = open(os.path.join(GOLDEN, "layout_reference.txt")).read()
+    for out in outs:
+        assert out == gold, f"layout drift:\n{out}\nvs the reference's\n{gold}"
 
 
 @pytest.mark.skipif(not os.path.isdir(REF + "/src/tinympc"), reason="needs the reference headers")
@@ -87,15 +91,19 @@ def test_rho_adapter_layout_against_the_real_reference_header(tmp_path):
     assert "sizeof(TinyRhoAdapterPOD) == 304 && sizeof(TinyRhoBenchmarkResultPOD) == 56" in src_text
 
 
-@pytest.mark.skipif(not os.path.isdir(REF + "/src/tinympc"), reason="needs the reference headers")
 def test_every_function_the_reference_headers_declare_is_exported_or_accounted_for():
     """tiny_api.hpp, admm.hpp, codegen.hpp, rho_benchmark.hpp of the reference against `nm -D libtinympc_amd.so`: the only names
     missing are the C++-mangled internals of rho_benchmark.cpp and the five functions upstream declares but never defines
-    (INTEGRATION.md)."""
-    declared = set()
-    for h in ("tiny_api.hpp", "admm.hpp", "codegen.hpp", "rho_benchmark.hpp"):
-        text = re.sub(r"//.*", "", open(os.path.join(REF, "src", "tinympc", h)).read())
-        declared |= set(re.findall(r"^\s*(?:int|void|bool|tinytype)\s+\*?(\w+)\s*\(", text, flags=re.M))
+    (INTEGRATION.md).  The declared names are kept in tests/golden/reference_declared_functions.txt; where the reference sources
+    exist they are read again and must equal it."""
+    declared = set(open(os.path.join(GOLDEN, "reference_declared_functions.txt")).read().split())
+    have_ref_src = os.path.isdir(REF + "/src/tinympc")
+    if have_ref_src:
+        live = set()
+        for h in ("tiny_api.hpp", "admm.hpp", "codegen.hpp", "rho_benchmark.hpp"):
+            text = re.sub(r"//.*", "", open(os.path.join(REF, "src", "tinympc", h)).read())
+            live |= set(re.findall(r"^\s*(?:int|void|bool|tinytype)\s+\*?(\w+)\s*\(", text, flags=re.M))
+        assert live == declared, (sorted(live - declared), sorted(declared - live))
     assert len(declared) >= 35, sorted(declared)
     nm = subprocess.run(["nm", "-D", "--defined-only", tm.LIB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in nm.splitlines() if ln.strip()}
@@ -109,21 +117,26 @@ def test_every_function_the_reference_headers_declare_is_exported_or_accounted_f
     rho_internals = set(rho_helpers)
     never_defined = {"update_primal", "compute_sensitivity_matrices", "tiny_update_matrices_with_derivatives",
                      "tiny_setup_state_soc_constraints", "tiny_setup_input_soc_constraints"}
-    sources = "".join(open(os.path.join(REF, "src", "tinympc", f)).read() for f in ("admm.cpp", "tiny_api.cpp", "codegen.cpp", "rho_benchmark.cpp"))
-    for f in never_defined:                                   # (declared, called by nobody, defined nowhere)
+    if have_ref_src:
+        sources = "".join(open(os.path.join(REF, "src", "tinympc", f)).read() for f in ("admm.cpp", "tiny_api.cpp", "codegen.cpp", "rho_benchmark.cpp"))
+    for f in never_defined if have_ref_src else ():          # (declared, called by nobody, defined nowhere)
         assert not re.search(r"^[\w:<>\*& ]+\b%s\s*\([^;]*\)\s*\{" % f, sources, flags=re.M), f
     assert declared - exported == rho_internals | never_defined, sorted(declared - exported - rho_internals - never_defined)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libtinympc_ref.so")), reason="needs oracle/_ref (built where /root/reference exists)")
 def test_every_symbol_the_reference_library_defines_is_exported():
     """`nm -D` of the real reference compiled by oracle/Makefile vs libtinympc_amd.so: every function the reference DEFINES
-    (C names and C++-mangled ones; Eigen / libstdc++ instantiations and the shim's own ref_* hooks aside) is a symbol here."""
+    (C names and C++-mangled ones; Eigen / libstdc++ instantiations and the shim's own ref_* hooks aside) is a symbol here.
+    The reference's list is kept in tests/golden/reference_symbols.txt; where oracle/_ref is built it must equal it."""
     def syms(path, only_text):
         out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
         return {ln.split()[2] for ln in out.splitlines() if len(ln.split()) == 3 and (not only_text or ln.split()[1] == "T")}
-    ref = {s for s in syms(os.path.join(ROOT, "oracle", "_ref", "libtinympc_ref.so"), True)
-           if not s.startswith(("ref_", "_ZN5Eigen", "_ZNK5Eigen", "_ZSt", "_ZNS", "_ZNK", "_ZN9__gnu", "_init", "_fini"))}
+    ref = set(open(os.path.join(GOLDEN, "reference_symbols.txt")).read().split())
+    ref_so = os.path.join(ROOT, "oracle", "_ref", "libtinympc_ref.so")
+    if os.path.exists(ref_so):
+        live = {s for s in syms(ref_so, True)
+                if not s.startswith(("ref_", "_ZN5Eigen", "_ZNK5Eigen", "_ZSt", "_ZNS", "_ZNK", "_ZN9__gnu", "_init", "_fini"))}
+        assert live == ref, (sorted(live - ref), sorted(ref - live))
     assert len(ref) >= 25, sorted(ref)
     assert not (ref - syms(tm.LIB_PATH, False)), sorted(ref - syms(tm.LIB_PATH, False))
 
@@ -198,8 +211,8 @@ def test_tiny_setup_rejects_bad_dimensions(capfd):
     assert "State transition matrix (A) has 3 rows. Expected 4." in capfd.readouterr().out     # tiny_api.cpp:13-19
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "tests", "dropin", "_build", "cartpole_example")),
-                    reason="drop-in binaries not built (tests/dropin/build.sh needs /root/reference)")
+@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "dropin", "cartpole_example")),
+                    reason="drop-in binaries not built (oracle/dropin_build.sh needs the reference sources)")
 @pytest.mark.parametrize("ex", ["cartpole_example", "quadrotor_hovering", "rocket_landing_mpc"])
 def test_dropin_example_setup_output_matches_reference(ex):
     """The reference's own example main(), compiled against the reference's headers and linked against
@@ -207,7 +220,7 @@ def test_dropin_example_setup_output_matches_reference(ex):
     the reference's stdout.  (The solves need a GPU: tests/test_gpu_dropin.py.)"""
     if tm.device_count() > 0:
         pytest.skip("full run covered by the GPU test")
-    exe = os.path.join(ROOT, "tests", "dropin", "_build", ex)
+    exe = os.path.join(ROOT, "oracle", "_ref", "dropin", ex)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     gold = open(os.path.join(GOLDEN, f"stdout_{ex}.txt")).read()
     marker = "Precomputation finished!\n\n"

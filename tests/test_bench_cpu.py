@@ -26,6 +26,14 @@ def test_steps_per_launch_divides_the_timed_steps():
         assert T and 1 <= T <= 100 and steps % T == 0
 
 
+def test_plain_run_is_the_default_and_extras_need_full():
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert args.full is False and args.dump_outputs is None and args.steps == 7 and args.warmup == 3
+    args = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert args.full is True and args.dump_outputs == "out"
+
+
 def test_bench_refuses_to_run_without_a_gpu():
     import torch
     if torch.cuda.is_available():

@@ -1,5 +1,5 @@
 """GPU test of the drop-in boundary: the reference's own example programs (compiled against the reference's
-headers, linked against libtinympc_amd.so by tests/dropin/build.sh) must print exactly what they print when
+headers, linked against libtinympc_amd.so by oracle/dropin_build.sh) must print exactly what they print when
 linked against the reference itself -- iteration counts per solve, 'Solver converged in N iterations',
 6-digit tracking errors, totals (BASELINE config 1 = cartpole_example)."""
 import os
@@ -9,16 +9,23 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "tests", "dropin", "_build")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "dropin")
+
+
+def dropin_binary(name):
+    """oracle/_ref/dropin/<name>: built by __graft_entry__.build() (oracle/dropin_build.sh) where the reference sources exist, shipped
+    with the tree like the rest of oracle/_ref/ -- a machine without them must not pass the (b) row by skipping it"""
+    exe = os.path.join(BUILD, name)
+    if not os.path.exists(exe):
+        pytest.fail("oracle/_ref/dropin/%s is missing: __graft_entry__.build() makes it from the reference sources "
+                    "(oracle/dropin_build.sh) and oracle/_ref/ ships with the tree" % name)
+    return exe
 
 
 @pytest.mark.parametrize("ex", ["cartpole_example", "quadrotor_hovering", "quadrotor_tracking", "rocket_landing_mpc",
                                 "quadrotor_linear_constraints", "quadrotor_tv_linear_constraints"])
 def test_reference_example_stdout_identical(ex):
-    exe = os.path.join(BUILD, ex)
-    if not os.path.exists(exe):
-        pytest.fail("tests/dropin/_build/%s is missing: the drop-in binaries are built by __graft_entry__.build() in the container that has "
-                    "/root/reference and travel to the GPU box with the snapshot -- a box without them must not pass the (b) row by skipping it" % os.path.basename(exe))
+    exe = dropin_binary(ex)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     gold = open(os.path.join(ROOT, "tests", "golden", f"stdout_{ex}.txt")).read()
@@ -34,10 +41,7 @@ def test_phase_functions_called_with_real_eigen_types():
     project_soc and project_hyperplane cross the library boundary with real Eigen objects by value / by reference and an
     Eigen return value.  Every printed number must equal what the same program prints when linked against the reference
     (1e-9 of the line's largest magnitude: FMA contraction differs, nothing else may)."""
-    exe = os.path.join(BUILD, "phase_driver")
-    if not os.path.exists(exe):
-        pytest.fail("tests/dropin/_build/%s is missing: the drop-in binaries are built by __graft_entry__.build() in the container that has "
-                    "/root/reference and travel to the GPU box with the snapshot -- a box without them must not pass the (b) row by skipping it" % os.path.basename(exe))
+    exe = dropin_binary("phase_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     gold = open(os.path.join(ROOT, "tests", "golden", "stdout_phase_driver.txt")).read().splitlines()
@@ -87,10 +91,7 @@ def test_adaptive_rho_through_the_reference_structs():
     step the iteration count and solved flag must be identical to the real reference's, cache->rho and the moved
     Kinf / Pinf / C2 entries and the applied control within 1e-7 of the line's largest magnitude (they are printed after 6+
     Taylor steps of a closed loop; the batched tests hold single solves to 1e-9)."""
-    exe = os.path.join(BUILD, "adaptive_driver")
-    if not os.path.exists(exe):
-        pytest.fail("tests/dropin/_build/%s is missing: the drop-in binaries are built by __graft_entry__.build() in the container that has "
-                    "/root/reference and travel to the GPU box with the snapshot -- a box without them must not pass the (b) row by skipping it" % os.path.basename(exe))
+    exe = dropin_binary("adaptive_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     gold = open(os.path.join(ROOT, "tests", "golden", "stdout_adaptive_driver.txt")).read().splitlines()
@@ -116,10 +117,7 @@ def test_reference_codegen_examples_generate_a_project_that_solves(tmp_path, ex,
     they leave behind is the plain-C one of csrc/codegen.hip -- it must hold the solver the example configured (dimensions,
     rho, tolerances, cache computed by tiny_setup) and, built with its own Makefile, solve a batch on this GPU."""
     import re
-    exe = os.path.join(BUILD, ex)
-    if not os.path.exists(exe):
-        pytest.fail("tests/dropin/_build/%s is missing: the drop-in binaries are built by __graft_entry__.build() in the container that has "
-                    "/root/reference and travel to the GPU box with the snapshot -- a box without them must not pass the (b) row by skipping it" % os.path.basename(exe))
+    exe = dropin_binary(ex)
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300, cwd=tmp_path)
     assert p.returncode == 0 and p.stdout == "", p.stdout + p.stderr          # verbose = 0: the reference prints nothing either
     out = tmp_path / gen_dir
@@ -146,10 +144,7 @@ def test_rho_benchmark_helpers_called_through_their_cxx_names():
     linked against the reference -- dimensions and flags exactly, every number to 1e-9 relative (summation order of the
     dense products differs, nothing else may)."""
     import re
-    exe = os.path.join(BUILD, "rho_driver")
-    if not os.path.exists(exe):
-        pytest.fail("tests/dropin/_build/%s is missing: the drop-in binaries are built by __graft_entry__.build() in the container that has "
-                    "/root/reference and travel to the GPU box with the snapshot -- a box without them must not pass the (b) row by skipping it" % os.path.basename(exe))
+    exe = dropin_binary("rho_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     gold = open(os.path.join(ROOT, "tests", "golden", "stdout_rho_driver.txt")).read().splitlines()

@@ -84,7 +84,7 @@ def test_bench_plain_process_spawns_its_own_ranks_weak_and_strong():
     env = dict(os.environ, TINYMPC_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--no-regimes",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--no-regimes",
             "--min-seconds", "0.05", "--batch", "8192"]
     p = subprocess.run(base, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -141,8 +141,8 @@ def test_bench_line_carries_the_other_configs_and_honest_hbm_fields(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     details = str(tmp_path / "bench_details.json")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--min-seconds", "0.3", "--cpu-seconds", "0.5",
-                        "--details", details], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--min-seconds", "0.3",
+                        "--cpu-seconds", "0.5", "--details", details], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stdout.count("\n") == 1 and p.stdout.startswith("{")      # stdout IS the one line
 
@@ -193,6 +193,46 @@ def test_bench_line_carries_the_other_configs_and_honest_hbm_fields(tmp_path):
     assert sum(rg["iters_per_step"]) == 882                            # the reference's 100-step hover episode, SURVEY.md 8(c)
     assert d["cpu_baseline"]["kind"] in ("reference", "port") and d["cpu_baseline"]["value"] > 0
     assert d["gpu_phase_seconds"] > 0
+
+
+def test_plain_bench_times_its_steps_once_and_dumps_what_they_returned(tmp_path):
+    """A plain run (no --full) times exactly --steps steps once and prints the headline line without the --full legs;
+    --dump-outputs writes what the last timed step returned as float64 .npy files (at most 64 MB), the same in two runs."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out_dir = tmp_path / run
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                            "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert p.stdout.count("\n") == 1 and p.stdout.startswith("{")
+        line = json.loads(p.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert line[k] is not None, k
+        assert line["steps"] == 20 and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert abs(line["value"] - 65536 * 20 / (line["ms_per_step"] * 20 * 1e-3)) < 1e-5 * line["value"]
+        assert abs(line["admm_iters_per_solve"] - 34.55) < 1e-9         # 691 iterations over the first 20 steps of the episode
+        for k in ("configs", "cpu_baseline", "warm_regime", "roofline_hbm", "strong_scaling", "details"):
+            assert k not in line, k
+        files = sorted(os.listdir(out_dir))
+        assert files == sorted(n + ".npy" for n in ("sample_index", "solution_x", "solution_u", "x0_next", "iter", "solved", "residuals", "stats"))
+        arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(os.path.getsize(out_dir / f) for f in files) <= 64 * 2 ** 20
+        idx = arrays["sample_index"]
+        assert idx.shape == (16384,) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 65536
+        assert arrays["solution_x"].shape == (16384, 12, 10) and arrays["solution_u"].shape == (16384, 4, 9)
+        assert np.all(np.isfinite(arrays["solution_x"])) and np.all(np.isin(arrays["solved"], (0.0, 1.0)))
+        for k in ("solution_x", "solution_u", "x0_next", "iter"):       # identical instances: every sampled one returned the same
+            assert np.array_equal(arrays[k], np.broadcast_to(arrays[k][:1], arrays[k].shape)), k
+        assert arrays["stats"][7] == 691 * 65536                         # accumulated iterations of the timed region
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 def test_sharded_sweep_driver_counts_what_the_single_process_counts(tmp_path):
