@@ -433,6 +433,27 @@ __device__ __forceinline__ void ring1_half(double& a0, double src, const double*
 #define FFB14 FFB13 "v_fmac_f64_dpp %[xn], %[t], %[b13] row_newbcast:%[c0]+13 row_mask:0xf bank_mask:0xf\n\t"
 #define FFB15 FFB14 "v_fmac_f64_dpp %[xn], %[t], %[b14] row_newbcast:%[c0]+14 row_mask:0xf bank_mask:0xf\n\t"
 #define FFB16 FFB15 "v_fmac_f64_dpp %[xn], %[t], %[b15] row_newbcast:%[c0]+15 row_mask:0xf bank_mask:0xf\n\t"
+// B u_i accumulated IN PLACE (nx a multiple of 4): bank_mask keeps the lanes from nx on -- u_i on the input lanes, the broadcast
+// sources of the chain -- out of every FMA, so t needs no copy into a second accumulator.  A disabled lane is re-written with the
+// value it held (the same u_k whether the read was early or late), which is why the chain may read t right behind writing it.  State
+// lanes: the same FMAs in the same order on the same values as with the copy.  Input lanes keep u_i itself where the copy form added
+// u_k * 0 to it (the two differ only in the sign of an exact zero, or when some u_k is not finite).
+#define FFI1 "v_fmac_f64_dpp %[t], %[t], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI2 FFI1 "v_fmac_f64_dpp %[t], %[t], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI3 FFI2 "v_fmac_f64_dpp %[t], %[t], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI4 FFI3 "v_fmac_f64_dpp %[t], %[t], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI5 FFI4 "v_fmac_f64_dpp %[t], %[t], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI6 FFI5 "v_fmac_f64_dpp %[t], %[t], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI7 FFI6 "v_fmac_f64_dpp %[t], %[t], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI8 FFI7 "v_fmac_f64_dpp %[t], %[t], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI9 FFI8 "v_fmac_f64_dpp %[t], %[t], %[b8] row_newbcast:%[c0]+8 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI10 FFI9 "v_fmac_f64_dpp %[t], %[t], %[b9] row_newbcast:%[c0]+9 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI11 FFI10 "v_fmac_f64_dpp %[t], %[t], %[b10] row_newbcast:%[c0]+10 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI12 FFI11 "v_fmac_f64_dpp %[t], %[t], %[b11] row_newbcast:%[c0]+11 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI13 FFI12 "v_fmac_f64_dpp %[t], %[t], %[b12] row_newbcast:%[c0]+12 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI14 FFI13 "v_fmac_f64_dpp %[t], %[t], %[b13] row_newbcast:%[c0]+13 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI15 FFI14 "v_fmac_f64_dpp %[t], %[t], %[b14] row_newbcast:%[c0]+14 row_mask:0xf bank_mask:%[bm]\n\t"
+#define FFI16 FFI15 "v_fmac_f64_dpp %[t], %[t], %[b15] row_newbcast:%[c0]+15 row_mask:0xf bank_mask:%[bm]\n\t"
 #define FMA1 [a0] "v"(ma[0])
 #define FMA2 FMA1, [a1] "v"(ma[1])
 #define FMA3 FMA2, [a2] "v"(ma[2])
@@ -490,13 +511,22 @@ __device__ __forceinline__ void ring1_half(double& a0, double src, const double*
     }
 #define FUSED_FWD_CASE(NA_, NB_) FUSED_FWD_CASE_(NA_, NB_)
 #define FUSED_FWD_CASE_(NA_, NB_)                                                                                       \
-    if constexpr (NA == NA_ && NB == NB_) {                                                                             \
+    if constexpr (NA == NA_ && NB == NB_ && !(INPLACE && NA_ % 4 == 0)) {                                               \
         asm("v_add_f64 %[tt], %[xi], %[g]\n\t"                                                                          \
             "v_max_f64 %[vm], %[lo], %[tt]\n\t" FFA##NA_                                                                \
             "v_min_f64 %[vn], %[hi], %[vm]\n\t"                                                                         \
             "v_mov_b64 %[xn], %[t]\n\t" FFB##NB_                                                                        \
             : [tt] "=&v"(tt), [vm] "=&v"(vm), [vn] "=&v"(vn), [xn] "=&v"(xn), [t] "+&v"(t)                               \
             : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [c0] "i"(NA_), FMA##NA_, FMB##NB_);                  \
+    }                                                                                                                   \
+    if constexpr (NA == NA_ && NB == NB_ && INPLACE && NA_ % 4 == 0) {                                                  \
+        asm("v_add_f64 %[tt], %[xi], %[g]\n\t" FFA##NA_                                                                 \
+            "v_max_f64 %[vn], %[lo], %[tt]\n\t"                                                                         \
+            "v_min_f64 %[vn], %[hi], %[vn]\n\t" FFI##NB_                                                                \
+            : [tt] "=&v"(tt), [vn] "=&v"(vn), [t] "+&v"(t)                                                              \
+            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [c0] "i"(NA_), [bm] "i"((1 << (NA_ / 4)) - 1),       \
+              FMA##NA_, FMB##NB_);                                                                                      \
+        xn = t;                                                                                                         \
     }
 // ---- the same fused steps for HALF rows (nx+nu <= 8: two instances per DPP row, see ring1_half): every column is a pair of
 // bank-masked FMAs -- all low halves, ONE wait state (a bank-masked DPP op re-writes its disabled lanes with the vdst it read
@@ -639,7 +669,8 @@ __device__ __forceinline__ void fused_forward_step_half(double& tt, double& vn, 
     (void)vm;
 }
 // forward step: tt = xi + g; vn = min(hi, max(lo, tt)); t += sum_k bcast(xi, k) ma[k]; xn = t + sum_k bcast(t, NA + k) mb_[k]
-template <int NA, int NB>
+// (INPLACE: the in-place B u chain where NA is a multiple of 4 -- t and xn are then one register; the one-row kernel's short box loop only)
+template <int NA, int NB, bool INPLACE = false>
 __device__ __forceinline__ void fused_forward_step(double& tt, double& vn, double& t, double& xn, double xi, double g, double lo, double hi,
                                                    const double* ma, const double* mb_) {
     double vm;
@@ -657,6 +688,19 @@ __device__ __forceinline__ double vmax64(double a, double b) {
 __device__ __forceinline__ double vmin64(double a, double b) {
     double r;
     asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+// a - b where it is written: the empty volatile statement behind it keeps hipcc from sinking the subtraction to the loop latch.  (The
+// subtraction itself stays a compiler instruction: hipcc's hazard bookkeeping counts an asm statement as no wait state at all.)
+__device__ __forceinline__ double pinned_sub64(double a, double b) {
+    double r = a - b;
+    asm volatile("" : "+v"(r));
+    return r;
+}
+// min(hi, max(lo, t)) as ONE asm statement: the two of vmin64(hi, vmax64(lo, t)) are back to back, and hipcc pads such a pair with an s_nop
+__device__ __forceinline__ double vclamp64(double lo, double hi, double t) {
+    double r;
+    asm("v_max_f64 %0, %1, %2\n\tv_min_f64 %0, %3, %0" : "=&v"(r) : "v"(lo), "v"(t), "v"(hi));
     return r;
 }
 
@@ -1462,11 +1506,16 @@ void admm_solve_kernel(const SolveArgs P) {
                     // registers, only when the probe lets the test run (said here, not left to the compiler's sinking); long ones keep
                     // the running maxima of the forward sweep
                     constexpr bool LAZY_RES = N <= 12;
+                    // the short box loop with nx a multiple of 4 (the quadrotor's): the forward step's B u chain runs in place, g of a
+                    // forward step is formed one step late -- where it takes the place of the s_nop hipcc puts between two asm statements
+                    // -- and the last slot's clamp is one asm statement.  Elsewhere (long horizons, whose g and x live partly in AGPRs;
+                    // the cone variant; the copy form) these cost more wait states and copies than they save: the form of before
+                    constexpr bool TIGHT = FUSED && !HALF && LAZY_RES && !SOC && NX % 4 == 0;
                     double pmax = 0.0, dmax = 0.0;
                     auto slot_update = [&](const int s, const double lo, const double hi, const double gcv, const double glv, const double gtv) {
                         const double xi = X[s];
                         const double t = xi + G[s];                                 // :85 / :88
-                        const double vn = vmin64(hi, vmax64(lo, t));                // :91-98
+                        const double vn = TIGHT ? vclamp64(lo, hi, t) : vmin64(hi, vmax64(lo, t));   // :91-98
                         if constexpr (!LAZY_RES) {
                             pmax = resid_max<true>(pmax, xi - vn);
                             dmax = resid_max<true>(dmax, VP[s] - vn);
@@ -1535,6 +1584,7 @@ void admm_solve_kernel(const SolveArgs P) {
                             if constexpr (LTP) gtr[d % SPR] = sTG[cl + d * CSL];
                         }
                     }
+                    double tt_d = 0.0, vn_d = 0.0;              // TIGHT: x + g and vnew of the step before (its g is formed one step late)
 #pragma unroll
                     for (int i = 0; i < N - 1; ++i) {
                         const double lo_n = UB ? lo_u : sLo[(i + 1) * 16 + j], hi_n = UB ? hi_u : sHi[(i + 1) * 16 + j];
@@ -1558,13 +1608,20 @@ void admm_solve_kernel(const SolveArgs P) {
                                 lo_c = lo_n; hi_c = hi_n;
                                 continue;
                             }
-                            fused_forward_step<NX, NU>(tt, vn, t, xn, xi, G[i], lo_c, hi_c, mf1, mf2);
+                            fused_forward_step<NX, NU, TIGHT>(tt, vn, t, xn, xi, G[i], lo_c, hi_c, mf1, mf2);
                             X[i + 1] = xn;
                             if constexpr (!LAZY_RES) {
                                 pmax = resid_max<true>(pmax, xi - vn);
                                 dmax = resid_max<true>(dmax, VP[i] - vn);
                             }
-                            G[i] = tt - vn;
+                            if constexpr (TIGHT) {
+                                // g <- (x + g) - vnew of the step BEFORE, pinned between this step's chains and the next step's: an
+                                // instruction there that reads none of this step's outputs spares hipcc's s_nop between the two asm
+                                // statements, and is the first of the two wait states the next chain's broadcast of x_{i+1} needs
+                                __builtin_amdgcn_sched_barrier(0);
+                                if (i > 0) G[i - 1] = pinned_sub64(tt_d, vn_d);
+                                tt_d = tt; vn_d = vn;
+                            } else G[i] = tt - vn;
                             VN[i] = vn;
                             if constexpr (SOC) sC[cw + i * SLOT_D] = fma(xi, socmask, gr[i % SPR]);   // x + gc -> cone step (below); see slot_update
                             lo_c = lo_n; hi_c = hi_n;
@@ -1575,6 +1632,8 @@ void admm_solve_kernel(const SolveArgs P) {
                         slot_update(i, lo_c, hi_c, gr[SOC ? i % SPR : 0], glr[LSP ? i % SPR : 0], gtr[LTP ? i % SPR : 0]);
                         lo_c = lo_n; hi_c = hi_n;
                     }
+                    if constexpr (TIGHT && N >= 2) G[N - 2] = tt_d - vn_d;
+                    (void)tt_d; (void)vn_d;
                     slot_update(N - 1, lo_c, hi_c, gr[SOC ? (N - 1) % SPR : 0], glr[LSP ? (N - 1) % SPR : 0], gtr[LTP ? (N - 1) % SPR : 0]);
                     if constexpr (LPL) {
                         // ---- half-space projections (admm.cpp:137-211) + their dual update (:239-254), transposed
