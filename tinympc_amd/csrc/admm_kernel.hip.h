@@ -186,67 +186,43 @@ struct SolveArgs {
 // EARLY-CLOBBER ("&"): they are written while src / m[] are still being read, so they must never
 // share a register with an input (without it hipcc happily aliases an accumulator with src).
 //
-//   TF_  : v_fmac_f64_dpp acc, src, m[k] row_newbcast:COL0+k      acc += bcast(src, lane COL0+k) * m[k]
-#define TF_(acc, mi, k) "v_fmac_f64_dpp %" #acc ", %2, %" #mi " row_newbcast:%3+" #k " row_mask:0xf bank_mask:0xf\n\t"
-// two-accumulator chains, every column an fmac (both accumulators carry a value in)
-#define TB1 TF_(0, 4, 0)
-#define TB2 TB1 TF_(1, 5, 1)
-#define TB3 TB2 TF_(0, 6, 2)
-#define TB4 TB3 TF_(1, 7, 3)
-#define TB5 TB4 TF_(0, 8, 4)
-#define TB6 TB5 TF_(1, 9, 5)
-#define TB7 TB6 TF_(0, 10, 6)
-#define TB8 TB7 TF_(1, 11, 7)
-#define TB9 TB8 TF_(0, 12, 8)
-#define TB10 TB9 TF_(1, 13, 9)
-#define TB11 TB10 TF_(0, 14, 10)
-#define TB12 TB11 TF_(1, 15, 11)
-#define TB13 TB12 TF_(0, 16, 12)
-#define TB14 TB13 TF_(1, 17, 13)
-#define TB15 TB14 TF_(0, 18, 14)
-#define TB16 TB15 TF_(1, 19, 15)
-// single-accumulator chain (operand numbering: %0 acc, %1 src, %2 COL0, %3.. m[k])
-#define TS_(mi, k) "v_fmac_f64_dpp %0, %1, %" #mi " row_newbcast:%2+" #k " row_mask:0xf bank_mask:0xf\n\t"
-#define TS1 TS_(3, 0)
-#define TS2 TS1 TS_(4, 1)
-#define TS3 TS2 TS_(5, 2)
-#define TS4 TS3 TS_(6, 3)
-#define TS5 TS4 TS_(7, 4)
-#define TS6 TS5 TS_(8, 5)
-#define TS7 TS6 TS_(9, 6)
-#define TS8 TS7 TS_(10, 7)
-#define TS9 TS8 TS_(11, 8)
-#define TS10 TS9 TS_(12, 9)
-#define TS11 TS10 TS_(13, 10)
-#define TS12 TS11 TS_(14, 11)
-#define TS13 TS12 TS_(15, 12)
-#define TS14 TS13 TS_(16, 13)
-#define TS15 TS14 TS_(17, 14)
-#define TS16 TS15 TS_(18, 15)
-#define TM1 "v"(m[0])
-#define TM2 TM1, "v"(m[1])
-#define TM3 TM2, "v"(m[2])
-#define TM4 TM3, "v"(m[3])
-#define TM5 TM4, "v"(m[4])
-#define TM6 TM5, "v"(m[5])
-#define TM7 TM6, "v"(m[6])
-#define TM8 TM7, "v"(m[7])
-#define TM9 TM8, "v"(m[8])
-#define TM10 TM9, "v"(m[9])
-#define TM11 TM10, "v"(m[10])
-#define TM12 TM11, "v"(m[11])
-#define TM13 TM12, "v"(m[12])
-#define TM14 TM13, "v"(m[13])
-#define TM15 TM14, "v"(m[14])
-#define TM16 TM15, "v"(m[15])
-#define RING_CASE(K)                                                                        \
-    if constexpr (NCOL == K) {                                                              \
-        asm("s_nop 1\n\t" TB##K : "+&v"(a0), "+&v"(a1) : "v"(src), "i"(COL0), TM##K);        \
-    }
-#define RING1_CASE(K)                                                                       \
-    if constexpr (NCOL == K) {                                                              \
-        asm("s_nop 1\n\t" TS##K : "+&v"(a0) : "v"(src), "i"(COL0), TM##K);                   \
-    }
+// Every block is ONE column instruction repeated by ONE ladder:
+//   DPP_FMA(acc, src, m, lane, bank)  acc += bcast(src, lane) * m on the lanes of `bank`.  The arguments are strings: operand NAMES of the
+//                                     enclosing asm statement, `lane` any text the assembler folds to a number ("%[c0]+3")
+//   DPP_REP(K, S)                     S(0, 0) S(1, 1) S(2, 0) ... S(K-1, (K-1) & 1): column index and its parity; K = 1 .. 16, a number or a macro
+//                                     that expands to one.  S: a DPP_FMA with its chain's names filled in, or an operand-list entry (with its comma)
+#define DPP_FMA(acc, src, m, lane, bank) "v_fmac_f64_dpp %[" acc "], %[" src "], %[" m "] row_newbcast:" lane " row_mask:0xf bank_mask:" bank "\n\t"
+#define DPP_REP1(S) S(0, 0)
+#define DPP_REP2(S) DPP_REP1(S) S(1, 1)
+#define DPP_REP3(S) DPP_REP2(S) S(2, 0)
+#define DPP_REP4(S) DPP_REP3(S) S(3, 1)
+#define DPP_REP5(S) DPP_REP4(S) S(4, 0)
+#define DPP_REP6(S) DPP_REP5(S) S(5, 1)
+#define DPP_REP7(S) DPP_REP6(S) S(6, 0)
+#define DPP_REP8(S) DPP_REP7(S) S(7, 1)
+#define DPP_REP9(S) DPP_REP8(S) S(8, 0)
+#define DPP_REP10(S) DPP_REP9(S) S(9, 1)
+#define DPP_REP11(S) DPP_REP10(S) S(10, 0)
+#define DPP_REP12(S) DPP_REP11(S) S(11, 1)
+#define DPP_REP13(S) DPP_REP12(S) S(12, 0)
+#define DPP_REP14(S) DPP_REP13(S) S(13, 1)
+#define DPP_REP15(S) DPP_REP14(S) S(14, 0)
+#define DPP_REP16(S) DPP_REP15(S) S(15, 1)
+#define DPP_REP_(K, S) DPP_REP##K(S)
+#define DPP_REP(K, S) DPP_REP_(K, S)
+// operand lists: the matrix row m[] of a ring block as [m0] .. [mK-1]; ma[] / mb_[] of a fused sweep step as [a0] .. and [b0] ..
+#define DPP_ROW_M(k, p) , [m##k] "v"(m[k])
+#define DPP_ROW_A(k, p) , [a##k] "v"(ma[k])
+#define DPP_ROW_B(k, p) , [b##k] "v"(mb_[k])
+// ring blocks.  Two accumulators: even columns on a0, odd ones on a1, every column an fmac (both accumulators carry a value in); or one
+#define RING2_COL(k, p) DPP_FMA("a" #p, "src", "m" #k, "%[c0]+" #k, "0xf")
+#define RING1_COL(k, p) DPP_FMA("a0", "src", "m" #k, "%[c0]+" #k, "0xf")
+#define RING_CASE(K)                                                                                                                     \
+    if constexpr (NCOL == K)                                                                                                             \
+        asm("s_nop 1\n\t" DPP_REP(K, RING2_COL) : [a0] "+&v"(a0), [a1] "+&v"(a1) : [src] "v"(src), [c0] "i"(COL0) DPP_REP(K, DPP_ROW_M));
+#define RING1_CASE(K)                                                                                                                    \
+    if constexpr (NCOL == K)                                                                                                             \
+        asm("s_nop 1\n\t" DPP_REP(K, RING1_COL) : [a0] "+&v"(a0) : [src] "v"(src), [c0] "i"(COL0) DPP_REP(K, DPP_ROW_M));
 
 template <int C>
 __device__ __forceinline__ double row_bcast(double v) {
@@ -332,28 +308,11 @@ __device__ __forceinline__ double ring_short(double init, double src, const doub
 // accumulator loses the first one's result (the second writes the stale lanes 0-7 back).  One wait state in between is enough.
 // So a chain runs all its low-half FMAs (their enabled lanes accumulate through the interlocked src2 path; the disabled lanes keep
 // being re-written with a value that does not change), then `s_nop 0`, then all its high-half FMAs.
-#define THL_(mi, k) "v_fmac_f64_dpp %0, %1, %" #mi " row_newbcast:%2+" #k " row_mask:0xf bank_mask:0x3\n\t"
-#define THH_(mi, k) "v_fmac_f64_dpp %0, %1, %" #mi " row_newbcast:8+%2+" #k " row_mask:0xf bank_mask:0xc\n\t"
-#define THL1 THL_(3, 0)
-#define THL2 THL1 THL_(4, 1)
-#define THL3 THL2 THL_(5, 2)
-#define THL4 THL3 THL_(6, 3)
-#define THL5 THL4 THL_(7, 4)
-#define THL6 THL5 THL_(8, 5)
-#define THL7 THL6 THL_(9, 6)
-#define THL8 THL7 THL_(10, 7)
-#define THH1 THH_(3, 0)
-#define THH2 THH1 THH_(4, 1)
-#define THH3 THH2 THH_(5, 2)
-#define THH4 THH3 THH_(6, 3)
-#define THH5 THH4 THH_(7, 4)
-#define THH6 THH5 THH_(8, 5)
-#define THH7 THH6 THH_(9, 6)
-#define THH8 THH7 THH_(10, 7)
-#define RINGH_CASE(K)                                                                       \
-    if constexpr (NCOL == K) {                                                              \
-        asm("s_nop 1\n\t" THL##K "s_nop 0\n\t" THH##K : "+&v"(a0) : "v"(src), "i"(COL0), TM##K);   \
-    }
+#define RINGH_LO(k, p) DPP_FMA("a0", "src", "m" #k, "%[c0]+" #k, "0x3")
+#define RINGH_HI(k, p) DPP_FMA("a0", "src", "m" #k, "8+%[c0]+" #k, "0xc")
+#define RINGH_CASE(K)                                                                                                                    \
+    if constexpr (NCOL == K)                                                                                                             \
+        asm("s_nop 1\n\t" DPP_REP(K, RINGH_LO) "s_nop 0\n\t" DPP_REP(K, RINGH_HI) : [a0] "+&v"(a0) : [src] "v"(src), [c0] "i"(COL0) DPP_REP(K, DPP_ROW_M));
 // a0 += sum_k bcast_half(src, COL0+k) * m[k]   (each half of the row reads its OWN lanes COL0+k)
 template <int COL0, int NCOL>
 __device__ __forceinline__ void ring1_half(double& a0, double src, const double* m) {
@@ -369,313 +328,152 @@ __device__ __forceinline__ void ring1_half(double& a0, double src, const double*
 // filled with work (38 s_nop per (12,4,10) iteration gone, +2.7 % measured as an upper bound with the nops simply deleted)
 // and no compiler-inserted copy can land between the producer of a source and its first DPP read.  Same instructions, same
 // operand order as the unfused code: bit-identical results.
-#define FCA1 "v_fmac_f64_dpp %[acc], %[sa], %[a0] row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA2 FCA1 "v_fmac_f64_dpp %[acc], %[sa], %[a1] row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA3 FCA2 "v_fmac_f64_dpp %[acc], %[sa], %[a2] row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA4 FCA3 "v_fmac_f64_dpp %[acc], %[sa], %[a3] row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA5 FCA4 "v_fmac_f64_dpp %[acc], %[sa], %[a4] row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA6 FCA5 "v_fmac_f64_dpp %[acc], %[sa], %[a5] row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA7 FCA6 "v_fmac_f64_dpp %[acc], %[sa], %[a6] row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA8 FCA7 "v_fmac_f64_dpp %[acc], %[sa], %[a7] row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA9 FCA8 "v_fmac_f64_dpp %[acc], %[sa], %[a8] row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA10 FCA9 "v_fmac_f64_dpp %[acc], %[sa], %[a9] row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA11 FCA10 "v_fmac_f64_dpp %[acc], %[sa], %[a10] row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA12 FCA11 "v_fmac_f64_dpp %[acc], %[sa], %[a11] row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA13 FCA12 "v_fmac_f64_dpp %[acc], %[sa], %[a12] row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA14 FCA13 "v_fmac_f64_dpp %[acc], %[sa], %[a13] row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA15 FCA14 "v_fmac_f64_dpp %[acc], %[sa], %[a14] row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-#define FCA16 FCA15 "v_fmac_f64_dpp %[acc], %[sa], %[a15] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB1 "v_fmac_f64_dpp %[acc], %[sb], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB2 FCB1 "v_fmac_f64_dpp %[acc], %[sb], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB3 FCB2 "v_fmac_f64_dpp %[acc], %[sb], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB4 FCB3 "v_fmac_f64_dpp %[acc], %[sb], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB5 FCB4 "v_fmac_f64_dpp %[acc], %[sb], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB6 FCB5 "v_fmac_f64_dpp %[acc], %[sb], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB7 FCB6 "v_fmac_f64_dpp %[acc], %[sb], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB8 FCB7 "v_fmac_f64_dpp %[acc], %[sb], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB9 FCB8 "v_fmac_f64_dpp %[acc], %[sb], %[b8] row_newbcast:%[c0]+8 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB10 FCB9 "v_fmac_f64_dpp %[acc], %[sb], %[b9] row_newbcast:%[c0]+9 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB11 FCB10 "v_fmac_f64_dpp %[acc], %[sb], %[b10] row_newbcast:%[c0]+10 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB12 FCB11 "v_fmac_f64_dpp %[acc], %[sb], %[b11] row_newbcast:%[c0]+11 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB13 FCB12 "v_fmac_f64_dpp %[acc], %[sb], %[b12] row_newbcast:%[c0]+12 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB14 FCB13 "v_fmac_f64_dpp %[acc], %[sb], %[b13] row_newbcast:%[c0]+13 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB15 FCB14 "v_fmac_f64_dpp %[acc], %[sb], %[b14] row_newbcast:%[c0]+14 row_mask:0xf bank_mask:0xf\n\t"
-#define FCB16 FCB15 "v_fmac_f64_dpp %[acc], %[sb], %[b15] row_newbcast:%[c0]+15 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA1 "v_fmac_f64_dpp %[t], %[xi], %[a0] row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA2 FFA1 "v_fmac_f64_dpp %[t], %[xi], %[a1] row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA3 FFA2 "v_fmac_f64_dpp %[t], %[xi], %[a2] row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA4 FFA3 "v_fmac_f64_dpp %[t], %[xi], %[a3] row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA5 FFA4 "v_fmac_f64_dpp %[t], %[xi], %[a4] row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA6 FFA5 "v_fmac_f64_dpp %[t], %[xi], %[a5] row_newbcast:5 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA7 FFA6 "v_fmac_f64_dpp %[t], %[xi], %[a6] row_newbcast:6 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA8 FFA7 "v_fmac_f64_dpp %[t], %[xi], %[a7] row_newbcast:7 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA9 FFA8 "v_fmac_f64_dpp %[t], %[xi], %[a8] row_newbcast:8 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA10 FFA9 "v_fmac_f64_dpp %[t], %[xi], %[a9] row_newbcast:9 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA11 FFA10 "v_fmac_f64_dpp %[t], %[xi], %[a10] row_newbcast:10 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA12 FFA11 "v_fmac_f64_dpp %[t], %[xi], %[a11] row_newbcast:11 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA13 FFA12 "v_fmac_f64_dpp %[t], %[xi], %[a12] row_newbcast:12 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA14 FFA13 "v_fmac_f64_dpp %[t], %[xi], %[a13] row_newbcast:13 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA15 FFA14 "v_fmac_f64_dpp %[t], %[xi], %[a14] row_newbcast:14 row_mask:0xf bank_mask:0xf\n\t"
-#define FFA16 FFA15 "v_fmac_f64_dpp %[t], %[xi], %[a15] row_newbcast:15 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB1 "v_fmac_f64_dpp %[xn], %[t], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB2 FFB1 "v_fmac_f64_dpp %[xn], %[t], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB3 FFB2 "v_fmac_f64_dpp %[xn], %[t], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB4 FFB3 "v_fmac_f64_dpp %[xn], %[t], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB5 FFB4 "v_fmac_f64_dpp %[xn], %[t], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB6 FFB5 "v_fmac_f64_dpp %[xn], %[t], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB7 FFB6 "v_fmac_f64_dpp %[xn], %[t], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB8 FFB7 "v_fmac_f64_dpp %[xn], %[t], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB9 FFB8 "v_fmac_f64_dpp %[xn], %[t], %[b8] row_newbcast:%[c0]+8 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB10 FFB9 "v_fmac_f64_dpp %[xn], %[t], %[b9] row_newbcast:%[c0]+9 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB11 FFB10 "v_fmac_f64_dpp %[xn], %[t], %[b10] row_newbcast:%[c0]+10 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB12 FFB11 "v_fmac_f64_dpp %[xn], %[t], %[b11] row_newbcast:%[c0]+11 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB13 FFB12 "v_fmac_f64_dpp %[xn], %[t], %[b12] row_newbcast:%[c0]+12 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB14 FFB13 "v_fmac_f64_dpp %[xn], %[t], %[b13] row_newbcast:%[c0]+13 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB15 FFB14 "v_fmac_f64_dpp %[xn], %[t], %[b14] row_newbcast:%[c0]+14 row_mask:0xf bank_mask:0xf\n\t"
-#define FFB16 FFB15 "v_fmac_f64_dpp %[xn], %[t], %[b15] row_newbcast:%[c0]+15 row_mask:0xf bank_mask:0xf\n\t"
-// B u_i accumulated IN PLACE (nx a multiple of 4): bank_mask keeps the lanes from nx on -- u_i on the input lanes, the broadcast
-// sources of the chain -- out of every FMA, so t needs no copy into a second accumulator.  A disabled lane is re-written with the
-// value it held (the same u_k whether the read was early or late), which is why the chain may read t right behind writing it.  State
-// lanes: the same FMAs in the same order on the same values as with the copy.  Input lanes keep u_i itself where the copy form added
-// u_k * 0 to it (the two differ only in the sign of an exact zero, or when some u_k is not finite).
-#define FFI1 "v_fmac_f64_dpp %[t], %[t], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI2 FFI1 "v_fmac_f64_dpp %[t], %[t], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI3 FFI2 "v_fmac_f64_dpp %[t], %[t], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI4 FFI3 "v_fmac_f64_dpp %[t], %[t], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI5 FFI4 "v_fmac_f64_dpp %[t], %[t], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI6 FFI5 "v_fmac_f64_dpp %[t], %[t], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI7 FFI6 "v_fmac_f64_dpp %[t], %[t], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI8 FFI7 "v_fmac_f64_dpp %[t], %[t], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI9 FFI8 "v_fmac_f64_dpp %[t], %[t], %[b8] row_newbcast:%[c0]+8 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI10 FFI9 "v_fmac_f64_dpp %[t], %[t], %[b9] row_newbcast:%[c0]+9 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI11 FFI10 "v_fmac_f64_dpp %[t], %[t], %[b10] row_newbcast:%[c0]+10 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI12 FFI11 "v_fmac_f64_dpp %[t], %[t], %[b11] row_newbcast:%[c0]+11 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI13 FFI12 "v_fmac_f64_dpp %[t], %[t], %[b12] row_newbcast:%[c0]+12 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI14 FFI13 "v_fmac_f64_dpp %[t], %[t], %[b13] row_newbcast:%[c0]+13 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI15 FFI14 "v_fmac_f64_dpp %[t], %[t], %[b14] row_newbcast:%[c0]+14 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FFI16 FFI15 "v_fmac_f64_dpp %[t], %[t], %[b15] row_newbcast:%[c0]+15 row_mask:0xf bank_mask:%[bm]\n\t"
-#define FMA1 [a0] "v"(ma[0])
-#define FMA2 FMA1, [a1] "v"(ma[1])
-#define FMA3 FMA2, [a2] "v"(ma[2])
-#define FMA4 FMA3, [a3] "v"(ma[3])
-#define FMA5 FMA4, [a4] "v"(ma[4])
-#define FMA6 FMA5, [a5] "v"(ma[5])
-#define FMA7 FMA6, [a6] "v"(ma[6])
-#define FMA8 FMA7, [a7] "v"(ma[7])
-#define FMA9 FMA8, [a8] "v"(ma[8])
-#define FMA10 FMA9, [a9] "v"(ma[9])
-#define FMA11 FMA10, [a10] "v"(ma[10])
-#define FMA12 FMA11, [a11] "v"(ma[11])
-#define FMA13 FMA12, [a12] "v"(ma[12])
-#define FMA14 FMA13, [a13] "v"(ma[13])
-#define FMA15 FMA14, [a14] "v"(ma[14])
-#define FMA16 FMA15, [a15] "v"(ma[15])
-#define FMB1 [b0] "v"(mb_[0])
-#define FMB2 FMB1, [b1] "v"(mb_[1])
-#define FMB3 FMB2, [b2] "v"(mb_[2])
-#define FMB4 FMB3, [b3] "v"(mb_[3])
-#define FMB5 FMB4, [b4] "v"(mb_[4])
-#define FMB6 FMB5, [b5] "v"(mb_[5])
-#define FMB7 FMB6, [b6] "v"(mb_[6])
-#define FMB8 FMB7, [b7] "v"(mb_[7])
-#define FMB9 FMB8, [b8] "v"(mb_[8])
-#define FMB10 FMB9, [b9] "v"(mb_[9])
-#define FMB11 FMB10, [b10] "v"(mb_[10])
-#define FMB12 FMB11, [b11] "v"(mb_[11])
-#define FMB13 FMB12, [b12] "v"(mb_[12])
-#define FMB14 FMB13, [b13] "v"(mb_[13])
-#define FMB15 FMB14, [b14] "v"(mb_[14])
-#define FMB16 FMB15, [b15] "v"(mb_[15])
-#define FUSED_BWD_CASE(NA_, NB_) FUSED_BWD_CASE_(NA_, NB_)
-#define FUSED_BWD_CASE_(NA_, NB_)                                                                                       \
-    if constexpr (NA == NA_ && NB == NB_) {                                                                             \
-        asm("v_add_f64 %[tmp], %[vn], -%[g]\n\t"                                                                        \
-            "v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"                                                              \
-            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t" FCA##NA_ FCB##NB_                                           \
-            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [tmp] "=&v"(tmp)                                                      \
-            : [vn] "v"(vn), [g] "v"(g), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb), [sa] "v"(sa),    \
-              [sb] "v"(sb), [c0] "i"(NA_), FMA##NA_, FMB##NB_);                                                         \
-    }
-// the same with the cone slack's linear-cost term (admm.cpp:269 | :282 | :295): qlo = fma(-rho, w, fma(-rho, vn - g, qx)), w = vcnew - gc
-// (formed once, by the cone step: the W plane of the cone slack cells)
-#define FUSED_BWD_SOC_CASE(NA_, NB_) FUSED_BWD_SOC_CASE_(NA_, NB_)
-#define FUSED_BWD_SOC_CASE_(NA_, NB_)                                                                                   \
-    if constexpr (NA == NA_ && NB == NB_) {                                                                             \
-        asm("v_add_f64 %[tmp], %[vn], -%[g]\n\t"                                                                        \
-            "v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"                                                              \
-            "v_fma_f64 %[qlo], -%[rho], %[w], %[qlo]\n\t"                                                               \
-            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t" FCA##NA_ FCB##NB_                                           \
-            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [tmp] "=&v"(tmp)                                                      \
-            : [vn] "v"(vn), [g] "v"(g), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb), [sa] "v"(sa),    \
-              [sb] "v"(sb), [w] "v"(w), [c0] "i"(NA_), FMA##NA_, FMB##NB_);                                             \
-    }
-#define FUSED_FWD_CASE(NA_, NB_) FUSED_FWD_CASE_(NA_, NB_)
-#define FUSED_FWD_CASE_(NA_, NB_)                                                                                       \
-    if constexpr (NA == NA_ && NB == NB_ && !(INPLACE && NA_ % 4 == 0)) {                                               \
-        asm("v_add_f64 %[tt], %[xi], %[g]\n\t"                                                                          \
-            "v_max_f64 %[vm], %[lo], %[tt]\n\t" FFA##NA_                                                                \
-            "v_min_f64 %[vn], %[hi], %[vm]\n\t"                                                                         \
-            "v_mov_b64 %[xn], %[t]\n\t" FFB##NB_                                                                        \
-            : [tt] "=&v"(tt), [vm] "=&v"(vm), [vn] "=&v"(vn), [xn] "=&v"(xn), [t] "+&v"(t)                               \
-            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [c0] "i"(NA_), FMA##NA_, FMB##NB_);                  \
-    }                                                                                                                   \
-    if constexpr (NA == NA_ && NB == NB_ && INPLACE && NA_ % 4 == 0) {                                                  \
-        asm("v_add_f64 %[tt], %[xi], %[g]\n\t" FFA##NA_                                                                 \
-            "v_max_f64 %[vn], %[lo], %[tt]\n\t"                                                                         \
-            "v_min_f64 %[vn], %[hi], %[vn]\n\t" FFI##NB_                                                                \
-            : [tt] "=&v"(tt), [vn] "=&v"(vn), [t] "+&v"(t)                                                              \
-            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [c0] "i"(NA_), [bm] "i"((1 << (NA_ / 4)) - 1),       \
-              FMA##NA_, FMB##NB_);                                                                                      \
-        xn = t;                                                                                                         \
-    }
-// ---- the same fused steps for HALF rows (nx+nu <= 8: two instances per DPP row, see ring1_half): every column is a pair of
-// bank-masked FMAs -- all low halves, ONE wait state (a bank-masked DPP op re-writes its disabled lanes with the vdst it read
-// without interlock), all high halves.  In the forward step the wait state between the two halves of the first chain is the
-// step's own v_min.
-#define HAL1 "v_fmac_f64_dpp %[acc], %[sa], %[a0] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL2 HAL1 "v_fmac_f64_dpp %[acc], %[sa], %[a1] row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL3 HAL2 "v_fmac_f64_dpp %[acc], %[sa], %[a2] row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL4 HAL3 "v_fmac_f64_dpp %[acc], %[sa], %[a3] row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL5 HAL4 "v_fmac_f64_dpp %[acc], %[sa], %[a4] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL6 HAL5 "v_fmac_f64_dpp %[acc], %[sa], %[a5] row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL7 HAL6 "v_fmac_f64_dpp %[acc], %[sa], %[a6] row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-#define HAL8 HAL7 "v_fmac_f64_dpp %[acc], %[sa], %[a7] row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-#define HAH1 "v_fmac_f64_dpp %[acc], %[sa], %[a0] row_newbcast:8+0 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH2 HAH1 "v_fmac_f64_dpp %[acc], %[sa], %[a1] row_newbcast:8+1 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH3 HAH2 "v_fmac_f64_dpp %[acc], %[sa], %[a2] row_newbcast:8+2 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH4 HAH3 "v_fmac_f64_dpp %[acc], %[sa], %[a3] row_newbcast:8+3 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH5 HAH4 "v_fmac_f64_dpp %[acc], %[sa], %[a4] row_newbcast:8+4 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH6 HAH5 "v_fmac_f64_dpp %[acc], %[sa], %[a5] row_newbcast:8+5 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH7 HAH6 "v_fmac_f64_dpp %[acc], %[sa], %[a6] row_newbcast:8+6 row_mask:0xf bank_mask:0xc\n\t"
-#define HAH8 HAH7 "v_fmac_f64_dpp %[acc], %[sa], %[a7] row_newbcast:8+7 row_mask:0xf bank_mask:0xc\n\t"
-#define HBL1 "v_fmac_f64_dpp %[acc], %[sb], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL2 HBL1 "v_fmac_f64_dpp %[acc], %[sb], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL3 HBL2 "v_fmac_f64_dpp %[acc], %[sb], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL4 HBL3 "v_fmac_f64_dpp %[acc], %[sb], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL5 HBL4 "v_fmac_f64_dpp %[acc], %[sb], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL6 HBL5 "v_fmac_f64_dpp %[acc], %[sb], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL7 HBL6 "v_fmac_f64_dpp %[acc], %[sb], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:0x3\n\t"
-#define HBL8 HBL7 "v_fmac_f64_dpp %[acc], %[sb], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:0x3\n\t"
-#define HBH1 "v_fmac_f64_dpp %[acc], %[sb], %[b0] row_newbcast:8+%[c0]+0 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH2 HBH1 "v_fmac_f64_dpp %[acc], %[sb], %[b1] row_newbcast:8+%[c0]+1 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH3 HBH2 "v_fmac_f64_dpp %[acc], %[sb], %[b2] row_newbcast:8+%[c0]+2 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH4 HBH3 "v_fmac_f64_dpp %[acc], %[sb], %[b3] row_newbcast:8+%[c0]+3 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH5 HBH4 "v_fmac_f64_dpp %[acc], %[sb], %[b4] row_newbcast:8+%[c0]+4 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH6 HBH5 "v_fmac_f64_dpp %[acc], %[sb], %[b5] row_newbcast:8+%[c0]+5 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH7 HBH6 "v_fmac_f64_dpp %[acc], %[sb], %[b6] row_newbcast:8+%[c0]+6 row_mask:0xf bank_mask:0xc\n\t"
-#define HBH8 HBH7 "v_fmac_f64_dpp %[acc], %[sb], %[b7] row_newbcast:8+%[c0]+7 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAL1 "v_fmac_f64_dpp %[t], %[xi], %[a0] row_newbcast:0 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL2 HFAL1 "v_fmac_f64_dpp %[t], %[xi], %[a1] row_newbcast:1 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL3 HFAL2 "v_fmac_f64_dpp %[t], %[xi], %[a2] row_newbcast:2 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL4 HFAL3 "v_fmac_f64_dpp %[t], %[xi], %[a3] row_newbcast:3 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL5 HFAL4 "v_fmac_f64_dpp %[t], %[xi], %[a4] row_newbcast:4 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL6 HFAL5 "v_fmac_f64_dpp %[t], %[xi], %[a5] row_newbcast:5 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL7 HFAL6 "v_fmac_f64_dpp %[t], %[xi], %[a6] row_newbcast:6 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAL8 HFAL7 "v_fmac_f64_dpp %[t], %[xi], %[a7] row_newbcast:7 row_mask:0xf bank_mask:0x3\n\t"
-#define HFAH1 "v_fmac_f64_dpp %[t], %[xi], %[a0] row_newbcast:8+0 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH2 HFAH1 "v_fmac_f64_dpp %[t], %[xi], %[a1] row_newbcast:8+1 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH3 HFAH2 "v_fmac_f64_dpp %[t], %[xi], %[a2] row_newbcast:8+2 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH4 HFAH3 "v_fmac_f64_dpp %[t], %[xi], %[a3] row_newbcast:8+3 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH5 HFAH4 "v_fmac_f64_dpp %[t], %[xi], %[a4] row_newbcast:8+4 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH6 HFAH5 "v_fmac_f64_dpp %[t], %[xi], %[a5] row_newbcast:8+5 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH7 HFAH6 "v_fmac_f64_dpp %[t], %[xi], %[a6] row_newbcast:8+6 row_mask:0xf bank_mask:0xc\n\t"
-#define HFAH8 HFAH7 "v_fmac_f64_dpp %[t], %[xi], %[a7] row_newbcast:8+7 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBL1 "v_fmac_f64_dpp %[xn], %[t], %[b0] row_newbcast:%[c0]+0 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL2 HFBL1 "v_fmac_f64_dpp %[xn], %[t], %[b1] row_newbcast:%[c0]+1 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL3 HFBL2 "v_fmac_f64_dpp %[xn], %[t], %[b2] row_newbcast:%[c0]+2 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL4 HFBL3 "v_fmac_f64_dpp %[xn], %[t], %[b3] row_newbcast:%[c0]+3 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL5 HFBL4 "v_fmac_f64_dpp %[xn], %[t], %[b4] row_newbcast:%[c0]+4 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL6 HFBL5 "v_fmac_f64_dpp %[xn], %[t], %[b5] row_newbcast:%[c0]+5 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL7 HFBL6 "v_fmac_f64_dpp %[xn], %[t], %[b6] row_newbcast:%[c0]+6 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBL8 HFBL7 "v_fmac_f64_dpp %[xn], %[t], %[b7] row_newbcast:%[c0]+7 row_mask:0xf bank_mask:0x3\n\t"
-#define HFBH1 "v_fmac_f64_dpp %[xn], %[t], %[b0] row_newbcast:8+%[c0]+0 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH2 HFBH1 "v_fmac_f64_dpp %[xn], %[t], %[b1] row_newbcast:8+%[c0]+1 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH3 HFBH2 "v_fmac_f64_dpp %[xn], %[t], %[b2] row_newbcast:8+%[c0]+2 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH4 HFBH3 "v_fmac_f64_dpp %[xn], %[t], %[b3] row_newbcast:8+%[c0]+3 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH5 HFBH4 "v_fmac_f64_dpp %[xn], %[t], %[b4] row_newbcast:8+%[c0]+4 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH6 HFBH5 "v_fmac_f64_dpp %[xn], %[t], %[b5] row_newbcast:8+%[c0]+5 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH7 HFBH6 "v_fmac_f64_dpp %[xn], %[t], %[b6] row_newbcast:8+%[c0]+6 row_mask:0xf bank_mask:0xc\n\t"
-#define HFBH8 HFBH7 "v_fmac_f64_dpp %[xn], %[t], %[b7] row_newbcast:8+%[c0]+7 row_mask:0xf bank_mask:0xc\n\t"
-// Every wait state such a chain needs is a lane-local instruction the iteration needs anyway (no s_nop): behind the write of the
-// accumulator stands the forward constant of the step BEFORE (Dn = fma(p | d, nim, cf) of the source the chain is about to broadcast),
-// between the two halves the `vn - g` of the NEXT step; in the forward step `g <- (x + g) - vnew` (the residual terms are NOT pulled in:
-// they are only formed when the termination test can pass).  Same instructions, same operands as the one-instance-per-row form: bit-identical results.
-#define FUSED_HBWD_CASE(NA_, NB_) FUSED_HBWD_CASE_(NA_, NB_)
-#define FUSED_HBWD_CASE_(NA_, NB_)                                                                                      \
-    if constexpr (NA == NA_ && NB == NB_) {                                                                             \
-        asm("v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"                                                              \
-            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t"                                                             \
-            "v_fma_f64 %[dnp], %[sa], %[nim], %[cf]\n\t" HAL##NA_ HBL##NB_                                              \
-            "v_add_f64 %[tmpn], %[vnn], -%[gn]\n\t" HAH##NA_ HBH##NB_                                                   \
-            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [dnp] "=&v"(dnp), [tmpn] "=&v"(tmpn)                                  \
-            : [tmp] "v"(tmp), [vnn] "v"(vnn), [gn] "v"(gn), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb), \
-              [nim] "v"(nim), [cf] "v"(cf), [sa] "v"(sa), [sb] "v"(sb), [c0] "i"(NA_), FMA##NA_, FMB##NB_);             \
-    }
-#define FUSED_HFWD_CASE(NA_, NB_) FUSED_HFWD_CASE_(NA_, NB_)
-#define FUSED_HFWD_CASE_(NA_, NB_)                                                                                      \
-    if constexpr (NA == NA_ && NB == NB_) {                                                                             \
-        asm("v_add_f64 %[tt], %[xi], %[g]\n\t"                                                                          \
-            "v_max_f64 %[vm], %[lo], %[tt]\n\t" HFAL##NA_                                                               \
-            "v_min_f64 %[vn], %[hi], %[vm]\n\t" HFAH##NA_                                                               \
-            "v_mov_b64 %[xn], %[t]\n\t"                                                                                 \
-            "v_add_f64 %[gnew], %[tt], -%[vn]\n\t" HFBL##NB_                                                            \
-            "s_nop 0\n\t" HFBH##NB_                                                                                     \
-            : [tt] "=&v"(tt), [vm] "=&v"(vm), [vn] "=&v"(vn), [xn] "=&v"(xn), [t] "+&v"(t), [gnew] "=&v"(gnew)           \
-            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [c0] "i"(NA_), FMA##NA_, FMB##NB_);                  \
-    }
 // One (nx, nu) pair per translation unit: the Makefile (compiled-in shapes) and jit.hip (run-time instantiated ones) define
-// TINYMPC_FUSED_NX / _NU as plain numbers in front of this header, so that exactly one pair of asm statements is spelled out.
+// TINYMPC_FUSED_NX / _NU as plain numbers in front of this header (DPP_REP takes its column count from the preprocessor), so that
+// exactly one pair of asm statements is spelled out.  For every other pair, and without the defines, the step functions are empty;
+// fused_shape() is what the kernels ask before they call one.
 #if defined(TINYMPC_FUSED_NX) && defined(TINYMPC_FUSED_NU)
-#define FUSED_SHAPES(CASE) CASE(TINYMPC_FUSED_NX, TINYMPC_FUSED_NU)
+#define TINYMPC_FUSED 1
 constexpr bool fused_shape(int na, int nb) { return na == TINYMPC_FUSED_NX && nb == TINYMPC_FUSED_NU; }
-#if TINYMPC_FUSED_NX + TINYMPC_FUSED_NU <= 8
-#define FUSED_HALF_SHAPES(CASE) CASE(TINYMPC_FUSED_NX, TINYMPC_FUSED_NU)
+// the tail of every step's input operands: where the second chain's lanes begin, and the two matrix rows
+#define FUSED_ROW_OPERANDS [c0] "i"(TINYMPC_FUSED_NX) DPP_REP(TINYMPC_FUSED_NX, DPP_ROW_A) DPP_REP(TINYMPC_FUSED_NU, DPP_ROW_B)
 #else
-#define FUSED_HALF_SHAPES(CASE)
-#endif
-#else
-#define FUSED_SHAPES(CASE)
-#define FUSED_HALF_SHAPES(CASE)
 constexpr bool fused_shape(int, int) { return false; }
 #endif
+// the chains' columns.  A: lanes 0 .. nx-1 of the first source times ma[]; B: lanes nx .. nx+nu-1 of the second source times mb_[]
+#define BWD_COL_A(k, p) DPP_FMA("acc", "sa", "a" #k, #k, "0xf")
+#define BWD_COL_B(k, p) DPP_FMA("acc", "sb", "b" #k, "%[c0]+" #k, "0xf")
+#define FWD_COL_A(k, p) DPP_FMA("t", "xi", "a" #k, #k, "0xf")
+#define FWD_COL_B(k, p) DPP_FMA("xn", "t", "b" #k, "%[c0]+" #k, "0xf")
+#define FWD_COL_B_INPLACE(k, p) DPP_FMA("t", "t", "b" #k, "%[c0]+" #k, "%[bm]")
 // backward step: qlo = fma(-rho, vn - g, qx); acc = fma(qlo, smask, cb) + sum_k bcast(sa, k) ma[k] + sum_k bcast(sb, NA + k) mb_[k]
 template <int NA, int NB>
 __device__ __forceinline__ void fused_backward_step(double& qlo, double& acc, double vn, double g, double qx, double rho, double smask, double cb,
                                                     double sa, double sb, const double* ma, const double* mb_) {
-    double tmp;
-    FUSED_SHAPES(FUSED_BWD_CASE)
-    (void)tmp;
+#ifdef TINYMPC_FUSED
+    if constexpr (fused_shape(NA, NB)) {
+        double tmp;
+        asm("v_add_f64 %[tmp], %[vn], -%[g]\n\t"
+            "v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"
+            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, BWD_COL_A) DPP_REP(TINYMPC_FUSED_NU, BWD_COL_B)
+            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [tmp] "=&v"(tmp)
+            : [vn] "v"(vn), [g] "v"(g), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb), [sa] "v"(sa), [sb] "v"(sb), FUSED_ROW_OPERANDS);
+    }
+#endif
 }
+// the same with the cone slack's linear-cost term (admm.cpp:269 | :282 | :295): qlo = fma(-rho, w, fma(-rho, vn - g, qx)), w = vcnew - gc
+// (formed once, by the cone step: the W plane of the cone slack cells)
 template <int NA, int NB>
 __device__ __forceinline__ void fused_backward_step_soc(double& qlo, double& acc, double vn, double g, double qx, double w, double rho,
                                                         double smask, double cb, double sa, double sb, const double* ma, const double* mb_) {
-    double tmp;
-    FUSED_SHAPES(FUSED_BWD_SOC_CASE)
-    (void)tmp;
-}
-// the half-row forms of the two (NA + NB <= 8).  backward: qlo = fma(-rho, tmp, qx) with tmp = vn - g handed in (formed by the step before);
-// dnp = fma(sa, nim, cf); tmpn = vnn - gn for the next step.  forward: additionally gnew = tt - vn
-template <int NA, int NB>
-__device__ __forceinline__ void fused_backward_step_half(double& qlo, double& acc, double& dnp, double& tmpn, double tmp, double vnn, double gn, double qx,
-                                                         double rho, double smask, double cb, double nim, double cf, double sa, double sb,
-                                                         const double* ma, const double* mb_) {
-    FUSED_HALF_SHAPES(FUSED_HBWD_CASE)
-}
-template <int NA, int NB>
-__device__ __forceinline__ void fused_forward_step_half(double& tt, double& vn, double& t, double& xn, double& gnew, double xi, double g,
-                                                        double lo, double hi, const double* ma, const double* mb_) {
-    double vm;
-    FUSED_HALF_SHAPES(FUSED_HFWD_CASE)
-    (void)vm;
+#ifdef TINYMPC_FUSED
+    if constexpr (fused_shape(NA, NB)) {
+        double tmp;
+        asm("v_add_f64 %[tmp], %[vn], -%[g]\n\t"
+            "v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"
+            "v_fma_f64 %[qlo], -%[rho], %[w], %[qlo]\n\t"
+            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, BWD_COL_A) DPP_REP(TINYMPC_FUSED_NU, BWD_COL_B)
+            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [tmp] "=&v"(tmp)
+            : [vn] "v"(vn), [g] "v"(g), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb), [sa] "v"(sa), [sb] "v"(sb),
+              [w] "v"(w), FUSED_ROW_OPERANDS);
+    }
+#endif
 }
 // forward step: tt = xi + g; vn = min(hi, max(lo, tt)); t += sum_k bcast(xi, k) ma[k]; xn = t + sum_k bcast(t, NA + k) mb_[k]
 // (INPLACE: the in-place B u chain where NA is a multiple of 4 -- t and xn are then one register; the one-row kernel's short box loop only)
 template <int NA, int NB, bool INPLACE = false>
 __device__ __forceinline__ void fused_forward_step(double& tt, double& vn, double& t, double& xn, double xi, double g, double lo, double hi,
                                                    const double* ma, const double* mb_) {
-    double vm;
-    FUSED_SHAPES(FUSED_FWD_CASE)
-    (void)vm;
+#ifdef TINYMPC_FUSED
+    if constexpr (fused_shape(NA, NB) && !(INPLACE && TINYMPC_FUSED_NX % 4 == 0)) {
+        double vm;
+        asm("v_add_f64 %[tt], %[xi], %[g]\n\t"
+            "v_max_f64 %[vm], %[lo], %[tt]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, FWD_COL_A)
+            "v_min_f64 %[vn], %[hi], %[vm]\n\t"
+            "v_mov_b64 %[xn], %[t]\n\t"
+            DPP_REP(TINYMPC_FUSED_NU, FWD_COL_B)
+            : [tt] "=&v"(tt), [vm] "=&v"(vm), [vn] "=&v"(vn), [xn] "=&v"(xn), [t] "+&v"(t)
+            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), FUSED_ROW_OPERANDS);
+    }
+    // B u_i accumulated IN PLACE (nx a multiple of 4): bank_mask keeps the lanes from nx on -- u_i on the input lanes, the broadcast
+    // sources of the chain -- out of every FMA, so t needs no copy into a second accumulator.  A disabled lane is re-written with the
+    // value it held (the same u_k whether the read was early or late), which is why the chain may read t right behind writing it.  State
+    // lanes: the same FMAs in the same order on the same values as with the copy.  Input lanes keep u_i itself where the copy form added
+    // u_k * 0 to it (the two differ only in the sign of an exact zero, or when some u_k is not finite).
+    if constexpr (fused_shape(NA, NB) && INPLACE && TINYMPC_FUSED_NX % 4 == 0) {
+        asm("v_add_f64 %[tt], %[xi], %[g]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, FWD_COL_A)
+            "v_max_f64 %[vn], %[lo], %[tt]\n\t"
+            "v_min_f64 %[vn], %[hi], %[vn]\n\t"
+            DPP_REP(TINYMPC_FUSED_NU, FWD_COL_B_INPLACE)
+            : [tt] "=&v"(tt), [vn] "=&v"(vn), [t] "+&v"(t)
+            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), [bm] "i"((1 << (TINYMPC_FUSED_NX / 4)) - 1), FUSED_ROW_OPERANDS);
+        xn = t;
+    }
+#endif
+}
+// ---- the same fused steps for HALF rows (nx+nu <= 8: two instances per DPP row, see ring1_half): every column is a pair of
+// bank-masked FMAs -- all low halves, ONE wait state (a bank-masked DPP op re-writes its disabled lanes with the vdst it read
+// without interlock), all high halves.  In the forward step the wait state between the two halves of the first chain is the
+// step's own v_min.
+#if defined(TINYMPC_FUSED) && TINYMPC_FUSED_NX + TINYMPC_FUSED_NU <= 8
+#define TINYMPC_FUSED_HALF 1
+#endif
+#define HBWD_COL_A_LO(k, p) DPP_FMA("acc", "sa", "a" #k, #k, "0x3")
+#define HBWD_COL_A_HI(k, p) DPP_FMA("acc", "sa", "a" #k, "8+" #k, "0xc")
+#define HBWD_COL_B_LO(k, p) DPP_FMA("acc", "sb", "b" #k, "%[c0]+" #k, "0x3")
+#define HBWD_COL_B_HI(k, p) DPP_FMA("acc", "sb", "b" #k, "8+%[c0]+" #k, "0xc")
+#define HFWD_COL_A_LO(k, p) DPP_FMA("t", "xi", "a" #k, #k, "0x3")
+#define HFWD_COL_A_HI(k, p) DPP_FMA("t", "xi", "a" #k, "8+" #k, "0xc")
+#define HFWD_COL_B_LO(k, p) DPP_FMA("xn", "t", "b" #k, "%[c0]+" #k, "0x3")
+#define HFWD_COL_B_HI(k, p) DPP_FMA("xn", "t", "b" #k, "8+%[c0]+" #k, "0xc")
+// Every wait state such a chain needs is a lane-local instruction the iteration needs anyway (no s_nop): behind the write of the
+// accumulator stands the forward constant of the step BEFORE (Dn = fma(p | d, nim, cf) of the source the chain is about to broadcast),
+// between the two halves the `vn - g` of the NEXT step; in the forward step `g <- (x + g) - vnew` (the residual terms are NOT pulled in:
+// they are only formed when the termination test can pass).  Same instructions, same operands as the one-instance-per-row form: bit-identical results.
+// backward: qlo = fma(-rho, tmp, qx) with tmp = vn - g handed in (formed by the step before); dnp = fma(sa, nim, cf); tmpn = vnn - gn for
+// the next step.  forward: additionally gnew = tt - vn
+template <int NA, int NB>
+__device__ __forceinline__ void fused_backward_step_half(double& qlo, double& acc, double& dnp, double& tmpn, double tmp, double vnn, double gn, double qx,
+                                                         double rho, double smask, double cb, double nim, double cf, double sa, double sb,
+                                                         const double* ma, const double* mb_) {
+#ifdef TINYMPC_FUSED_HALF
+    if constexpr (fused_shape(NA, NB)) {
+        asm("v_fma_f64 %[qlo], -%[rho], %[tmp], %[qx]\n\t"
+            "v_fma_f64 %[acc], %[qlo], %[smask], %[cb]\n\t"
+            "v_fma_f64 %[dnp], %[sa], %[nim], %[cf]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, HBWD_COL_A_LO) DPP_REP(TINYMPC_FUSED_NU, HBWD_COL_B_LO)
+            "v_add_f64 %[tmpn], %[vnn], -%[gn]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, HBWD_COL_A_HI) DPP_REP(TINYMPC_FUSED_NU, HBWD_COL_B_HI)
+            : [qlo] "=&v"(qlo), [acc] "=&v"(acc), [dnp] "=&v"(dnp), [tmpn] "=&v"(tmpn)
+            : [tmp] "v"(tmp), [vnn] "v"(vnn), [gn] "v"(gn), [qx] "v"(qx), [rho] "v"(rho), [smask] "v"(smask), [cb] "v"(cb),
+              [nim] "v"(nim), [cf] "v"(cf), [sa] "v"(sa), [sb] "v"(sb), FUSED_ROW_OPERANDS);
+    }
+#endif
+}
+template <int NA, int NB>
+__device__ __forceinline__ void fused_forward_step_half(double& tt, double& vn, double& t, double& xn, double& gnew, double xi, double g,
+                                                        double lo, double hi, const double* ma, const double* mb_) {
+#ifdef TINYMPC_FUSED_HALF
+    if constexpr (fused_shape(NA, NB)) {
+        double vm;
+        asm("v_add_f64 %[tt], %[xi], %[g]\n\t"
+            "v_max_f64 %[vm], %[lo], %[tt]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, HFWD_COL_A_LO)
+            "v_min_f64 %[vn], %[hi], %[vm]\n\t"
+            DPP_REP(TINYMPC_FUSED_NX, HFWD_COL_A_HI)
+            "v_mov_b64 %[xn], %[t]\n\t"
+            "v_add_f64 %[gnew], %[tt], -%[vn]\n\t"
+            DPP_REP(TINYMPC_FUSED_NU, HFWD_COL_B_LO)
+            "s_nop 0\n\t"
+            DPP_REP(TINYMPC_FUSED_NU, HFWD_COL_B_HI)
+            : [tt] "=&v"(tt), [vm] "=&v"(vm), [vn] "=&v"(vn), [xn] "=&v"(xn), [t] "+&v"(t), [gnew] "=&v"(gnew)
+            : [xi] "v"(xi), [g] "v"(g), [lo] "v"(lo), [hi] "v"(hi), FUSED_ROW_OPERANDS);
+    }
+#endif
 }
 
 // v_max_f64 / v_min_f64 without the canonicalising `v_max x, x` hipcc puts in front of fmax/fmin

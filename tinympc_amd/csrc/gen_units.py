@@ -17,7 +17,7 @@ GEN = os.path.join(HERE, "_gen")
 
 
 def rows(path, nmin):
-    for line in open(os.path.join(HERE, path)):
+    for line in open(path):
         f = line.split("#")[0].split()
         if len(f) >= nmin:
             yield f
@@ -30,37 +30,51 @@ def write_if_changed(path, text):
         f.write(text)
 
 
+def read_dims(src=HERE):
+    """kernel_dims.txt and tile_dims.txt of the directory `src` -> (one_row: {(nx, nu, N): lean}, tile_order: [(nx, nu, N, W, R, lm)],
+    both in file order)."""
+    one_row = collections.OrderedDict()
+    for f in rows(os.path.join(src, "kernel_dims.txt"), 3):
+        one_row[tuple(map(int, f[:3]))] = (len(f) > 3 and f[3] == "lean")
+    tile_order = []
+    for f in rows(os.path.join(src, "tile_dims.txt"), 5):
+        tile_order.append(tuple(map(int, f[:5])) + (int(f[5]) if len(f) > 5 else 99,))
+    return one_row, tile_order
+
+
+def unit_shapes(one_row, tile_order):
+    """The (nx, nu, N) shapes that get a unit: the one-row shapes, then the shapes only tile_dims.txt lists."""
+    return list(one_row) + list(collections.OrderedDict((e[:3], None) for e in tile_order if e[:3] not in one_row))
+
+
+def unit_text(shape, one_row, tile_order):
+    """The text of _gen/u_<nx>_<nu>_<N>.hip (it includes the headers as ../<name>)."""
+    nx, nu, N = shape
+    forms = [e[3:] for e in tile_order if e[:3] == shape]
+    t = []
+    if shape in one_row or any(W == 1 for W, _, _ in forms):      # the fused sweep-step blocks are spelled out for ONE (nx, nu) pair per unit
+        t += ["#define TINYMPC_FUSED_NX %d" % nx, "#define TINYMPC_FUSED_NU %d" % nu]
+    t.append('#include "../kernel_entry.hpp"')
+    if forms:
+        t.append('#include "../tile_kernel.hip.h"')
+    t.append("namespace tinympc_amd {")
+    if shape in one_row:
+        macro = "KERNELS_LEAN" if one_row[shape] else "KERNELS_FOR"
+        t.append("extern const KernelEntry kentry_%d_%d_%d = %s(%d, %d, %d);" % (nx, nu, N, macro, nx, nu, N))
+    for W, R, lm in forms:
+        a = "%d, %d, %d, %d, %d, %d" % (nx, nu, N, W, R, lm)
+        t.append("extern const TileEntry tentry_%d_%d_%d_%d_%d_%d = { %s, tile_kernel_or_null<%s, false>(), tile_kernel_or_null<%s, true>(), "
+                 "tile_kernel_or_null<%s, false, true>(), tile_kernel_or_null<%s, true, true>() };" % (nx, nu, N, W, R, lm, a, a, a, a, a))
+    t.append("}  // namespace tinympc_amd")
+    return "\n".join(t) + "\n"
+
+
 def main():
     os.makedirs(GEN, exist_ok=True)
-    one_row = collections.OrderedDict()
-    for f in rows("kernel_dims.txt", 3):
-        one_row[tuple(map(int, f[:3]))] = (len(f) > 3 and f[3] == "lean")
-    tiles = collections.OrderedDict()
-    tile_order = []
-    for f in rows("tile_dims.txt", 5):
-        nx, nu, N, W, R = map(int, f[:5])
-        lm = int(f[5]) if len(f) > 5 else 99
-        tiles.setdefault((nx, nu, N), []).append((W, R, lm))
-        tile_order.append((nx, nu, N, W, R, lm))
-    shapes = list(one_row) + [s for s in tiles if s not in one_row]
-    for (nx, nu, N) in shapes:
-        forms = tiles.get((nx, nu, N), [])
-        t = []
-        if (nx, nu, N) in one_row or any(W == 1 for W, _, _ in forms):      # the fused sweep-step blocks are spelled out for ONE (nx, nu) pair per unit
-            t += ["#define TINYMPC_FUSED_NX %d" % nx, "#define TINYMPC_FUSED_NU %d" % nu]
-        t.append('#include "../kernel_entry.hpp"')
-        if forms:
-            t.append('#include "../tile_kernel.hip.h"')
-        t.append("namespace tinympc_amd {")
-        if (nx, nu, N) in one_row:
-            macro = "KERNELS_LEAN" if one_row[(nx, nu, N)] else "KERNELS_FOR"
-            t.append("extern const KernelEntry kentry_%d_%d_%d = %s(%d, %d, %d);" % (nx, nu, N, macro, nx, nu, N))
-        for W, R, lm in forms:
-            a = "%d, %d, %d, %d, %d, %d" % (nx, nu, N, W, R, lm)
-            t.append("extern const TileEntry tentry_%d_%d_%d_%d_%d_%d = { %s, tile_kernel_or_null<%s, false>(), tile_kernel_or_null<%s, true>(), "
-                     "tile_kernel_or_null<%s, false, true>(), tile_kernel_or_null<%s, true, true>() };" % (nx, nu, N, W, R, lm, a, a, a, a, a))
-        t.append("}  // namespace tinympc_amd")
-        write_if_changed(os.path.join(GEN, "u_%d_%d_%d.hip" % (nx, nu, N)), "\n".join(t) + "\n")
+    one_row, tile_order = read_dims()
+    shapes = unit_shapes(one_row, tile_order)
+    for shape in shapes:
+        write_if_changed(os.path.join(GEN, "u_%d_%d_%d.hip" % shape), unit_text(shape, one_row, tile_order))
     reg = ["extern const KernelEntry kentry_%d_%d_%d;" % s for s in one_row]
     reg += ["static const KernelEntry* const g_kernels[] = {"] + ["    &kentry_%d_%d_%d," % s for s in one_row] + ["};"]
     reg += ["extern const TileEntry tentry_%d_%d_%d_%d_%d_%d;" % e for e in tile_order]

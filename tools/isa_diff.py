@@ -1,10 +1,15 @@
 #!/usr/bin/env python3
-"""CPU only: does a kernel-header edit change the machine code of the compiled-in kernels?  Compiles one (nx, nu, N) translation
-unit for gfx950 from the working tree and from a git revision, and compares the instruction streams variant by variant
-(labels, comments and directives ignored).  An edit that is meant to touch only some variants can be proven not to touch the
-headline kernel without a GPU -- the measured numbers of an unchanged instruction stream stay valid.
-    python tools/isa_diff.py [rev = HEAD] [nx nu N = 12 4 10]"""
+"""CPU only: does a kernel-header edit change the machine code of the compiled-in kernels?  Compiles (nx, nu, N) translation units
+for gfx950 from the working tree and from a git revision -- each exactly as csrc/gen_units.py writes it from that tree's
+kernel_dims.txt / tile_dims.txt, tile-kernel forms included -- and compares every kernel's instruction stream and its
+.amdhsa_* directives (registers, LDS, scratch); labels, comments and the other directives are ignored.  An edit that is meant to
+touch only some variants can be proven not to touch the headline kernel without a GPU -- the measured numbers of an unchanged
+instruction stream stay valid -- and a refactor can be proven to touch nothing at all.
+    python tools/isa_diff.py [rev = HEAD] [nx nu N = 12 4 10]     one unit, one line per kernel
+    python tools/isa_diff.py [rev = HEAD] --all                   every unit of either tree, one line per unit
+Exit status 1 when any kernel differs."""
 import collections
+import concurrent.futures
 import difflib
 import os
 import re
@@ -14,72 +19,99 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "tinympc_amd", "csrc")
-HEADERS = ("admm_kernel.hip.h", "kernel_entry.hpp", "tile_kernel.hip.h")
+sys.path.insert(0, CSRC)
+import gen_units  # noqa: E402
+
+SOURCES = ("admm_kernel.hip.h", "kernel_entry.hpp", "tile_kernel.hip.h", "kernel_dims.txt", "tile_dims.txt")
+MAX_JOBS = 16          # compiles in flight (a fixed cap: the CPU count of a shared machine says nothing about this process's share)
 
 
-def assemble(srcdir, dims, out):
+def assemble(srcdir, shape, text):
+    """Compiles `text` as srcdir/_gen/u_<shape>.hip with the Makefile's device flags; returns the assembly."""
     gen = os.path.join(srcdir, "_gen")
     os.makedirs(gen, exist_ok=True)
-    name = "u_%d_%d_%d" % dims
+    name = "u_%d_%d_%d" % shape
     with open(os.path.join(gen, name + ".hip"), "w") as f:
-        f.write("#define TINYMPC_FUSED_NX %d\n#define TINYMPC_FUSED_NU %d\n" % dims[:2])      # as csrc/Makefile writes the unit
-        f.write('#include "../kernel_entry.hpp"\n')
-        f.write("namespace tinympc_amd { extern const KernelEntry kentry_%d_%d_%d = KERNELS_FOR(%d, %d, %d); }\n" % (dims + dims))
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", name + ".hip", "-o", out],
+        f.write(text)
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-S", name + ".hip", "-o", name + ".s"],
                           cwd=gen, stderr=subprocess.DEVNULL)
+    return open(os.path.join(gen, name + ".s")).read()
 
 
-def kernels(path):
-    text = open(path).read()
+def kernels(text):
+    """{kernel symbol: its instructions, then its .amdhsa_* lines} of one assembly file."""
     out = {}
-    for m in re.finditer(r"^(_ZN11tinympc_amd\w+):[^\n]*\n", text, re.M):
-        sym = m.group(1)
-        end = text.find(".Lfunc_end", m.end())
-        if end < 0 or "s_endpgm" not in text[m.end():end]:
-            continue                                            # a data symbol, not a kernel
-        lines = [l.split(";")[0].strip() for l in text[m.end():end].splitlines()]
-        out[sym] = [l for l in lines if l and not l.startswith(".") and not l.endswith(":")]
+    for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", text, re.M | re.S):
+        sym, desc = m.group(1), [l.strip() for l in m.group(2).splitlines() if l.strip()]
+        start = re.search(r"^%s:[^\n]*\n" % re.escape(sym), text, re.M)
+        end = text.find(".Lfunc_end", start.end())
+        lines = [l.split(";")[0].strip() for l in text[start.end():end].splitlines()]
+        out[sym] = [l for l in lines if l and not l.startswith(".") and not l.endswith(":")] + desc
     return out
 
 
 def label(sym):
     a = [int(v) for v in re.findall(r"L[ib](\d+)E", sym)]
-    return "<%d,%d,%d soc%d dbg%d mode%d lin%d het%d kmax%d>" % tuple(a[:9]) if len(a) >= 9 else sym
+    return "<%d,%d,%d soc%d dbg%d mode%d lin%d het%d kmax%d>" % tuple(a[:9]) if "admm_solve_kernel" in sym and len(a) >= 9 else sym
 
 
-def main():
-    rev = sys.argv[1] if len(sys.argv) > 1 else "HEAD"
-    dims = tuple(int(v) for v in sys.argv[2:5]) if len(sys.argv) >= 5 else (12, 4, 10)
-    with tempfile.TemporaryDirectory() as tmp:
-        old = os.path.join(tmp, "old")
-        os.makedirs(old)
-        for h in HEADERS:
-            with open(os.path.join(old, h), "w") as f:
-                f.write(subprocess.check_output(["git", "show", "%s:tinympc_amd/csrc/%s" % (rev, h)], cwd=ROOT, text=True))
-        new = os.path.join(tmp, "new")
-        os.makedirs(new)
-        for h in HEADERS:
-            with open(os.path.join(new, h), "w") as f:
-                f.write(open(os.path.join(CSRC, h)).read())
-        assemble(old, dims, os.path.join(tmp, "old.s"))
-        assemble(new, dims, os.path.join(tmp, "new.s"))
-        a, b = kernels(os.path.join(tmp, "old.s")), kernels(os.path.join(tmp, "new.s"))
-    changed = 0
+def compare(a, b):
+    """[(verdict, symbol, detail)] over the kernels of two assembly files; verdict: identical | CHANGED | added | removed."""
+    res = []
     for sym in sorted(set(a) | set(b)):
         x, y = a.get(sym), b.get(sym)
         if x == y:
-            print(f"identical  {label(sym)}  {len(x)} instructions")
-            continue
-        changed += 1
-        if x is None or y is None:
-            print(f"{'added' if x is None else 'removed'}    {label(sym)}")
-            continue
-        delta = collections.Counter(l.split()[0] for l in y)
-        delta.subtract(collections.Counter(l.split()[0] for l in x))
-        top = ", ".join(f"{k} {v:+d}" for k, v in sorted(delta.items(), key=lambda kv: -abs(kv[1]))[:6] if v)
-        n = sum(1 for l in difflib.unified_diff(x, y, lineterm="", n=0) if l[:1] in "+-" and l[:3] not in ("+++", "---"))
-        print(f"CHANGED    {label(sym)}  {len(x)} -> {len(y)} instructions, {n} differing lines ({top})")
-    print(f"{changed} of {len(set(a) | set(b))} variants of {dims} differ from {rev}")
+            res.append(("identical", sym, "%d instructions" % sum(1 for l in x if not l.startswith("."))))
+        elif x is None or y is None:
+            res.append(("added" if x is None else "removed", sym, ""))
+        else:
+            delta = collections.Counter(l.split()[0] for l in y)
+            delta.subtract(collections.Counter(l.split()[0] for l in x))
+            top = ", ".join(f"{k} {v:+d}" for k, v in sorted(delta.items(), key=lambda kv: -abs(kv[1]))[:6] if v)
+            n = sum(1 for l in difflib.unified_diff(x, y, lineterm="", n=0) if l[:1] in "+-" and l[:3] not in ("+++", "---"))
+            res.append(("CHANGED", sym, f"{len(x)} -> {len(y)} lines, {n} differing ({top})"))
+    return res
+
+
+def main():
+    every = "--all" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    rev = args[0] if args else "HEAD"
+    with tempfile.TemporaryDirectory() as tmp:
+        trees = {"old": os.path.join(tmp, "old"), "new": os.path.join(tmp, "new")}
+        for side, d in trees.items():
+            os.makedirs(d)
+            for h in SOURCES:
+                with open(os.path.join(d, h), "w") as f:
+                    f.write(subprocess.check_output(["git", "show", "%s:tinympc_amd/csrc/%s" % (rev, h)], cwd=ROOT, text=True) if side == "old"
+                            else open(os.path.join(CSRC, h)).read())
+        dims = {side: gen_units.read_dims(d) for side, d in trees.items()}
+        if every:
+            shapes = gen_units.unit_shapes(*dims["old"])
+            shapes += [s for s in gen_units.unit_shapes(*dims["new"]) if s not in shapes]
+        else:
+            shapes = [tuple(int(v) for v in args[1:4]) if len(args) >= 4 else (12, 4, 10)]
+
+        def one(job):
+            side, shape = job
+            if shape not in gen_units.unit_shapes(*dims[side]):
+                return ""
+            return assemble(trees[side], shape, gen_units.unit_text(shape, *dims[side]))
+        jobs = [(side, shape) for shape in shapes for side in ("old", "new")]
+        with concurrent.futures.ThreadPoolExecutor(min(MAX_JOBS, len(jobs))) as ex:
+            asm = dict(zip(jobs, ex.map(one, jobs)))
+    changed = total = 0
+    for shape in shapes:
+        res = compare(kernels(asm[("old", shape)]), kernels(asm[("new", shape)]))
+        bad = [r for r in res if r[0] != "identical"]
+        changed += len(bad)
+        total += len(res)
+        if every:
+            same_text = ", assembly byte-identical" if asm[("old", shape)] == asm[("new", shape)] else ""
+            print("%-10s u_%d_%d_%d  %d kernels%s" % (("CHANGED" if bad else "identical",) + shape + (len(res), same_text if not bad else ", %d differ" % len(bad))))
+        for verdict, sym, detail in (bad if every else res):
+            print(f"{'    ' if every else ''}{verdict:<10} {label(sym)}  {detail}")
+    print(f"{changed} of {total} variants of {'%d units' % len(shapes) if every else shapes[0]} differ from {rev}")
     return 1 if changed else 0
 
 
