@@ -52,6 +52,32 @@ def test_one_changed_instruction_is_reported(checkout):
     assert code == 1 and 0 < differing <= total, (code, differing, total)
 
 
+TILE_NAME = "tinympc_amd::admm_tile_kernel<2, 2, 4, 1, 1, 1, 0, 4, false, 0, false, 0>"
+
+
+def test_names_mode_covers_a_runtime_instantiated_tile_form(checkout):
+    """--names FILE: a cone form of the tile kernel, which no unit holds, compiled as an explicit instantiation -- identical while the
+    copy is unmodified, reported once ONE instruction of the single-chain ring block its rows run is changed."""
+    listing = checkout / "names.txt"
+    listing.write_text("# one name per line\n%s\n" % TILE_NAME)
+
+    def run():
+        p = subprocess.run([sys.executable, str(checkout / "tools" / "isa_diff.py"), "HEAD", "--names", str(listing)], capture_output=True, text=True)
+        m = re.search(r"^(\d+) of (\d+) variants of 1 names differ from HEAD$", p.stdout, re.M)
+        assert m, (p.stdout[-1000:], p.stderr[-2000:])
+        return p.returncode, int(m.group(1)), int(m.group(2))
+    assert run() == (0, 0, 1)
+    header = checkout / "tinympc_amd" / "csrc" / "admm_kernel.hip.h"          # (the tile kernel's rows run that header's ring blocks)
+    text = header.read_text()
+    before = r'asm("s_nop 1\n\t" DPP_REP(K, RING1_COL)'
+    assert text.count(before) == 1
+    header.write_text(text.replace(before, before.replace("s_nop 1", "s_nop 2")))
+    try:
+        assert run() == (1, 1, 1)
+    finally:
+        header.write_text(text)
+
+
 def test_resource_directives_are_compared():
     unit = ("\t.globl\tk\nk:\n\ts_load_dword s0, s[4:5], 0x0 ; comment\n.LBB0_1:\n\ts_endpgm\n.Lfunc_end0:\n"
             "\t.amdhsa_kernel k\n\t\t.amdhsa_next_free_vgpr %d\n\t\t.amdhsa_private_segment_fixed_size 0\n\t.end_amdhsa_kernel\n")

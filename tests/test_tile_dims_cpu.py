@@ -58,6 +58,19 @@ def test_the_last_entry_can_serve_the_runtime_instantiated_variants():
         assert not (lm != 99 and lm & (VPG | QXR)), ("the last entry is the reference form for experiments too", nx, nu, N)
 
 
+def test_one_row_shapes_list_only_the_one_row_layout():
+    """A shape the one-row kernel holds as well is listed here for its dynamic one-row-layout form: the tile alternative and the tail of
+    a split solve (batch_dispatch.hip) hand the one-row kernel's launches to it, and the tail resumes from an index list -- which only
+    the forms with R = 1 and the trajectory regenerated (LM = 4), in at most one row per instance, can (RSM in tile_kernel.hip.h)."""
+    regs, shared = one_row_shapes(), 0
+    for shape, forms in entries().items():
+        if shape in regs:
+            shared += 1
+            for W, R, lm in forms:
+                assert W <= 1 and R == 1 and lm == REGEN, (shape, W, R, lm)
+    assert shared > 0
+
+
 def test_sweep_cells_of_config5_are_all_served():
     served = set(entries()) | one_row_shapes()
     for nx in (4, 8, 12, 20):

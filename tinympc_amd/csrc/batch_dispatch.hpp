@@ -38,6 +38,7 @@ void build_tables(TinyBatch* b);
 void build_tile_tables(TinyBatch* b);
 void build_general_tables(TinyBatch* b);
 int upload_tables(TinyBatch* b);
+int upload_growing(TinyBatch* b, double** dev, size_t* capacity, const std::vector<double>& host);   // host table -> device buffer that grows
 // ---- helper kernels, cost model (batch_helpers.hip)
 constexpr int REGROUP_AUTO_MIN_STEPS = 16, REGROUP_AUTO_MIN_BATCH = 4096;
 double wave_iteration_us(int nx, int nu, int N, int wps);

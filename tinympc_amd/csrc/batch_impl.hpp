@@ -154,10 +154,10 @@ struct TinyBatch {
     double* d_vz_scratch = nullptr;
     // the split solve's TAIL on the tile kernel (round 6): after the capped first stage the open instances -- listed by that launch -- run
     // to max_iter in ONE launch of the shape's dynamic slot form (tile_dims.txt: its one-row layout), whose rows refill one by one: no
-    // follow-up stages in lock step.  Option "repack_tail": -1 by the clock (probed like the split itself), 0 never, 1 wherever the form
-    // exists.  launch_tile reads tail_index / tail_count / tail_iter_base while enqueue_split_solve has them set
-    int repack_tail = -1, tail_verdict = 0;
-    double tail_rate = 0.0;
+    // follow-up stages in lock step.  Option "repack_tail": only 1 acts -- wherever the form exists and resumes from an index list; -1 (the
+    // default) and 0 keep the follow-up stages.  run_tile_launch reads tail_index / tail_count / tail_iter_base while enqueue_split_solve
+    // has them set
+    int repack_tail = -1;
     const int* tail_index = nullptr;
     const int* tail_count = nullptr;
     int tail_iter_base = 0;

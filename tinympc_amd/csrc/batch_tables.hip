@@ -297,19 +297,25 @@ void build_general_tables(TinyBatch* b) {
     std::copy(b->tvA_u.begin(), b->tvA_u.end(), t.begin() + g.o_tau); std::copy(b->tvb_u.begin(), b->tvb_u.end(), t.begin() + g.o_tbu);
 }
 
+// a host table into its device buffer, which grows when the table has: the old buffer goes once the stream has run dry of its readers.
+// The host vectors are pageable: the copy is staged synchronously, so reusing them later is safe
+int upload_growing(TinyBatch* b, double** dev, size_t* capacity, const std::vector<double>& host) {
+    if (*capacity < host.size()) {
+        if (*dev) {
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+            (void)hipFree(*dev);
+        }
+        *dev = nullptr; *capacity = 0;
+        HIP_TRY(b, hipMalloc(dev, host.size() * sizeof(double)));
+        *capacity = host.size();
+    }
+    HIP_TRY(b, hipMemcpyAsync(*dev, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+    return TINY_OK;
+}
 int upload_tables(TinyBatch* b) {
     if (!b->tab_dirty) return TINY_OK;
     build_tables(b);
-    if (b->h_tab.size() > b->d_tab_doubles) {
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        (void)hipFree(b->d_tab);
-        b->d_tab = nullptr; b->d_tab_doubles = 0;
-        HIP_TRY(b, hipMalloc(&b->d_tab, b->h_tab.size() * sizeof(double)));
-        b->d_tab_doubles = b->h_tab.size();
-    }
-    HIP_TRY(b, hipMemcpyAsync(b->d_tab, b->h_tab.data(), b->h_tab.size() * sizeof(double), hipMemcpyHostToDevice,
-                              b->stream));
-    // h_tab is pageable: the copy above is staged synchronously, so reusing h_tab later is safe
+    if (int rc = upload_growing(b, &b->d_tab, &b->d_tab_doubles, b->h_tab)) return rc;
     b->tab_dirty = false;
     return TINY_OK;
 }

@@ -106,18 +106,27 @@ constexpr long tile_lds_bytes(int nx, int nu, int n, int w, int r, int lm, bool 
     return 8L * (2L * (ub ? 2 : n) * 16 * (w == 0 ? 1 : w) + ((lm & TILE_LM_REGEN) ? 1 : (n / r) * 64) +
                  tile_lds_arrays(lm) * (long)(n / r) * tile_lds_slot(nx, nu, w));
 }
+// registers a lane needs for `arrays` L-long arrays (L = n / r) and its matrix rows: the estimate behind every waves-per-SIMD rule below
+// and behind the host's choice of R for the cone / half-space variants (each keeps its own threshold)
+constexpr int tile_reg_estimate(int arrays, int nx, int nu, int n, int r) { return 2 * (arrays * (n / r) + 2 * (nx + nu)) + 44; }
 // two waves per SIMD when the L-long register arrays + the matrix rows fit 256 VGPRs AND eight waves' LDS fits the CU
 constexpr int tile_waves_per_simd(int nx, int nu, int n, int r, int lm = 0, int w = 1) {
-    return (2 * (tile_reg_arrays(lm) * (n / r) + 2 * (nx + nu)) + 44 <= 276 &&      // measured (round 2): (12,8,30) at 274 gains, (20,2,30) at 282 loses to spills
+    return (tile_reg_estimate(tile_reg_arrays(lm), nx, nu, n, r) <= 276 &&      // measured (round 2): (12,8,30) at 274 gains, (20,2,30) at 282 loses to spills
             (lm == 0 || 8 * tile_lds_bytes(nx, nu, n, w, r, lm, true) <= 158 * 1024)) ? 2 : 1;
 }
 
+// static LDS bytes of a cone / half-space variant (all five arrays in registers) at (w, r): bound tables (the UB form keeps two slots), the
+// trajectory, the cone slack's three planes (rows of the families that are on), two planes per half-space set (all rows) and the sets' tables
+constexpr long tile_variant_lds_bytes(int nx, int nu, int n, int w, int r, int soc, int lin, int kmax, bool ub) {
+    const long lw = 16L * w, ipw = 4 / (w * r), cr = ((soc & 2) ? nx : 0) + ((soc & 1) ? nu : 0), csr = (cr + 1) | 1, csl = (nx + nu + 1) | 1;
+    long d = 2L * (ub ? 2 : n) * lw + (n / r) * 64;
+    if (soc) d += (ipw * n + 1) * 3 * csr;
+    if (lin & 1) d += 3L * kmax * lw + 2L * ipw * n * csl;
+    if (lin & 2) d += 3L * n * kmax * lw + 2L * ipw * n * csl;
+    return 8L * d;
+}
 // waves per SIMD of a cone variant (five L-long arrays in registers, the trajectory, the bound tables and the three slack planes in
 // LDS): two when the arrays + matrix rows fit 256 VGPRs (same measured threshold as the box forms) and eight waves' LDS fits the CU
-constexpr long tile_soc_lds_bytes(int nx, int nu, int n, int w, int r, int soc, bool ub) {
-    const int cr = ((soc & 2) ? nx : 0) + ((soc & 1) ? nu : 0), csr = (cr + 1) | 1, ipw = 4 / (w * r);
-    return 8L * (2L * (ub ? 2 : n) * 16 * w + (n / r) * 64 + (long)(ipw * n + 1) * 3 * csr);
-}
 template <int V> struct TileIntTag { static constexpr int value = V; };
 template <bool C, class A, class B> struct TileSelect { typedef A type; };
 template <class A, class B> struct TileSelect<false, A, B> { typedef B type; };
@@ -126,7 +135,7 @@ template <class A, class B> struct TileSelect<false, A, B> { typedef B type; };
 #endif
 constexpr int tile_soc_waves(int nx, int nu, int n, int w, int r, int soc, bool ub) {
     if (TINYMPC_TILE_SOC_WAVES > 0) return TINYMPC_TILE_SOC_WAVES;
-    return (2 * (5 * (n / r) + 2 * (nx + nu)) + 44 <= 276 && 8 * tile_soc_lds_bytes(nx, nu, n, w, r, soc, ub) <= 158 * 1024) ? 2 : 1;
+    return (tile_reg_estimate(5, nx, nu, n, r) <= 276 && 8 * tile_variant_lds_bytes(nx, nu, n, w, r, soc, 0, 0, ub) <= 158 * 1024) ? 2 : 1;
 }
 
 // SOC: second-order-cone slacks (admm.cpp:102-135, 228-235); bit 0: the input family's cone slack is on, bit 1: the state family's.
@@ -151,7 +160,7 @@ constexpr int tile_soc_waves(int nx, int nu, int n, int w, int r, int soc, bool 
 // (EXT forms hold all five arrays in registers AND re-load the matrix rows per instance: two waves per SIMD only with room to spare --
 // (20,8,10) at the box forms' threshold spilt 320 B per lane and ran at half the shared-family form's rate)
 constexpr int tile_ext_waves(int nx, int nu, int n, int r, int lm = 0, int w = 1) {
-    return lm != 0 ? tile_waves_per_simd(nx, nu, n, r, lm, w) : (2 * (5 * (n / r) + 2 * (nx + nu)) + 44 <= 240 ? 2 : 1);
+    return lm != 0 ? tile_waves_per_simd(nx, nu, n, r, lm, w) : (tile_reg_estimate(5, nx, nu, n, r) <= 240 ? 2 : 1);
 }
 template <int NX, int NU, int N, int W, int R, int SOC = 0, int LIN = 0, int KMAX = LIN_KMAX, bool UB = false, int LM = 0, bool DYN = false, int EXT = 0>
 __global__ __launch_bounds__(64)
