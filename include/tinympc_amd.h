@@ -103,7 +103,9 @@ int tiny_batch_setup(TinyBatch** out, const double* Adyn, const double* Bdyn, co
  * one-row kernel holds run its HET variant, wide and long shapes the tile kernel's per-instance form on the shape's fastest box form
  * (run-time instantiated: needs hipRTC or the prebuilt store); TINY_ERR_UNSUPPORTED when neither kernel holds the shape.  Round 6: cones
  * that share rows, more half-spaces per knot than the register variants hold, or a variant hipRTC cannot make send a heterogeneous
- * batch to the coverage kernel, which reads the same per-instance tables (adaptive rho does not combine with per-instance data). */
+ * batch to the coverage kernel, which reads the same per-instance tables.  Adaptive rho combines with per-instance data on the shapes
+ * the one-row kernel holds (nx + nu <= 16): every instance then moves its own cache by its own sensitivity tables
+ * (tiny_batch_compute_sensitivity), or by the one set tiny_batch_set_sensitivity installs for all of them. */
 int tiny_batch_setup_hetero(TinyBatch** out, const double* Adyn, const double* Bdyn, const double* fdyn,
                             const double* Qdiag, const double* Rdiag, const double* rho,
                             int nx, int nu, int N, int batch, int device, int verbose);
@@ -143,12 +145,28 @@ int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_
  * Quu_inv, AmBKt, APf, BPf, Q, R, which the reference keeps as they were.  The cache then is per-instance STATE that persists
  * from solve to solve (tiny_batch_reset puts tiny_setup's cache back).  The reference's RhoAdapter flag is read uninitialised
  * upstream; the behaviour reproduced is the one with that flag false ("matrices sized by the first adaptation of every
- * solve"), which is also the only one that does not crash (profiles/r02_adaptive_rho_probe.txt).  One-row kernel only. */
+ * solve"), which is also the only one that does not crash (profiles/r02_adaptive_rho_probe.txt).  One-row kernel only, shared
+ * family or per-instance batch (tiny_batch_setup_hetero); not with half-spaces, overlapping cones, one_shot or repack_after.  Without
+ * sensitivity tables (the two entry points below) the solve fails with TINY_ERR_DIM. */
 int tiny_batch_set_adaptive_rho(TinyBatch* b, int enable, double rho_min, double rho_max, int enable_clipping);
 /* == cache->dKinf_drho (nu x nx), dPinf_drho (nx x nx), dC1_drho (nu x nu), dC2_drho (nx x nx): column-major, shared by every
- * instance; dC1 / dC2 may be NULL (zero).  tiny_initialize_sensitivity_matrices (tiny_api.cpp:479-540) is the quadrotor's set. */
+ * instance; dC1 / dC2 may be NULL (zero).  tiny_initialize_sensitivity_matrices (tiny_api.cpp:479-540) is the quadrotor's set.  On a
+ * per-instance batch: the same tables for every instance. */
 int tiny_batch_set_sensitivity(TinyBatch* b, const double* dKinf_drho, const double* dPinf_drho, const double* dC1_drho,
                                const double* dC2_drho);
+/* The same four tables COMPUTED on the GPU (csrc/sensitivity_kernel.hip.h) for this batch's own system: the derivative with respect
+ * to rho of the cache tiny_setup computes -- rho enters Q and R twice there -- evaluated at the cache as it stands (after
+ * tiny_batch_set_cache too).  With K = Kinf, C1 = Quu_inv, Acl = A - B K:  dPinf solves dP = Acl' dP Acl + 2 (I + K' K),
+ * dKinf = C1 (B' dP Acl - 2 K), dC1 = -C1 (2 I + B' dP B) C1, dC2 = -(B dKinf)'.  The reference declares such a function
+ * (tiny_api.hpp:29-31) and defines none; its quadrotor literals are a DIFFERENT set (not this derivative) and stay what
+ * tiny_initialize_sensitivity_matrices installs.  Shared family: installed exactly as tiny_batch_set_sensitivity would.
+ * Per-instance batch: every instance's own tables, kept on the device.  Any nx + nu <= 32, nu <= 16; TINY_ERR_ARG when
+ * A - B Kinf is not a contraction (no derivative exists). */
+int tiny_batch_compute_sensitivity(TinyBatch* b);
+/* What is installed, computed or set: name = "dKinf_drho" | "dPinf_drho" | "dC1_drho" | "dC2_drho"; returns the element count. */
+int tiny_batch_get_sensitivity(TinyBatch* b, const char* name, double* out, int capacity);
+/* ... of one instance of a per-instance batch; the same names, or "steps": the squarings the Lyapunov solve took (1 .. 64). */
+int tiny_batch_get_sensitivity_instance(TinyBatch* b, int instance, const char* name, double* out, int capacity);
 /* per-instance cache state of an adaptive batch, host arrays with a leading batch axis, column-major matrices: which =
  * "rho" [batch], "Kinf" [batch][nu*nx], "Pinf" [batch][nx*nx], "C1" [batch][nu*nu], "C2" [batch][nx*nx] */
 int tiny_batch_set_cache_state(TinyBatch* b, const char* which, const double* src);
@@ -532,6 +550,10 @@ int tiny_set_u_ref(TinySolver* solver, const TinyMatrixPOD* u_ref);
  * reference's quadrotor tables (tiny_api.cpp:479-540).  With settings->adaptive_rho = 1 tiny_solve then re-estimates rho
  * every 5th iteration (admm.cpp:397-423) and writes the moved cache (rho, Kinf, Pinf, C1, C2) back into the TinyCache. */
 void tiny_initialize_sensitivity_matrices(TinySolver* solver);
+/* The same four cache members computed for the solver's OWN system, any nx + nu <= 32, nu <= 16 (tiny_batch_compute_sensitivity:
+ * the derivative of tiny_setup's cache, on the GPU).  0, or a TINY_ERR_* code.  Not the reference's declared-and-never-defined
+ * function of a similar name: that one stays unexported. */
+int tiny_compute_sensitivity(TinySolver* solver);
 /* codegen.hpp:9-18.  The reference freezes one TinySolver into Eigen-initialised C++ for microcontrollers; these freeze the
  * solver's PROBLEM FAMILY (dimensions, settings, the cache as it stands, dynamics, costs, bounds, cones, half-spaces,
  * references; with adaptive_rho on also the sensitivity tables) into a plain-C project for this library:

@@ -45,7 +45,8 @@ BATCH_SYMBOLS = (
     "tiny_batch_phase", "tiny_batch_get_timing", "tiny_batch_get_step_log", "tiny_batch_set_reference_trajectory", "tiny_batch_last_error", "tiny_batch_supported_dims", "tiny_batch_algorithmic_bytes", "tiny_batch_kernel_path",
     "tiny_jit_compile", "tiny_jit_prebuild", "tiny_jit_used", "tiny_batch_allreduce_stats", "tiny_batch_stats_message",
     "tiny_rccl_unique_id", "tiny_rccl_comm_init_rank", "tiny_rccl_comm_destroy", "tiny_rccl_comm_count", "tiny_rccl_available", "tiny_reduce_stats_messages",
-    "tiny_batch_get_option", "tiny_predict_split", "tiny_step_regroup_plan", "tiny_batch_get_plan", "tiny_batch_set_plan", "tiny_batch_set_cache", "tiny_batch_set_adaptive_rho", "tiny_batch_set_sensitivity", "tiny_batch_set_cache_state", "tiny_batch_get_cache_state")
+    "tiny_batch_get_option", "tiny_predict_split", "tiny_step_regroup_plan", "tiny_batch_get_plan", "tiny_batch_set_plan", "tiny_batch_set_cache", "tiny_batch_set_adaptive_rho", "tiny_batch_set_sensitivity", "tiny_batch_set_cache_state", "tiny_batch_get_cache_state",
+    "tiny_batch_compute_sensitivity", "tiny_batch_get_sensitivity", "tiny_batch_get_sensitivity_instance")
 GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_cone_constraints",
@@ -56,7 +57,7 @@ REFERENCE_SYMBOLS = (
     "tiny_setup", "tiny_set_bound_constraints", "tiny_set_cone_constraints", "tiny_set_linear_constraints",
     "tiny_set_tv_linear_constraints", "tiny_precompute_and_set_cache",
     "tiny_solve", "solve", "tiny_update_settings", "tiny_set_default_settings", "tiny_set_x0", "tiny_set_x_ref",
-    "tiny_set_u_ref", "tiny_solve_batch", "tiny_destroy", "tiny_initialize_sensitivity_matrices",
+    "tiny_set_u_ref", "tiny_solve_batch", "tiny_destroy", "tiny_initialize_sensitivity_matrices", "tiny_compute_sensitivity",
     "tiny_codegen", "tiny_codegen_with_sensitivity", "codegen_create_directories", "codegen_data_header", "codegen_data_source",
     "codegen_example",
     # the phase functions of admm.hpp:12-34
@@ -202,6 +203,9 @@ def lib():
         L.tiny_batch_get_option.restype = C.c_long
         L.tiny_batch_set_adaptive_rho.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int]
         L.tiny_batch_set_sensitivity.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.tiny_batch_compute_sensitivity.argtypes = [C.c_void_p]
+        L.tiny_batch_get_sensitivity.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
+        L.tiny_batch_get_sensitivity_instance.argtypes = [C.c_void_p, C.c_int, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set_cache_state.argtypes = [C.c_void_p, C.c_char_p, _dp]
         L.tiny_batch_get_cache_state.argtypes = [C.c_void_p, C.c_char_p, _dp]
         L.tiny_rccl_unique_id.argtypes = [C.c_void_p]
@@ -512,6 +516,32 @@ class TinyBatchSolver:
         a = [_colmajor(dKinf, (nu, nx)), _colmajor(dPinf, (nx, nx)), None if dC1 is None else _colmajor(dC1, (nu, nu)),
              None if dC2 is None else _colmajor(dC2, (nx, nx))]
         self._check(lib().tiny_batch_set_sensitivity(self._h, *[None if v is None else v.ctypes.data_as(_dp) for v in a]), "set_sensitivity")
+
+    _SENS_SHAPES = {"dKinf_drho": lambda s: (s.nu, s.nx), "dPinf_drho": lambda s: (s.nx, s.nx), "dC1_drho": lambda s: (s.nu, s.nu),
+                    "dC2_drho": lambda s: (s.nx, s.nx), "steps": lambda s: (1, 1)}
+
+    def compute_sensitivity(self):
+        """the four d(.)/d(rho) tables of this batch's own system(s), computed on the GPU (csrc/sensitivity_kernel.hip.h): the
+        derivative of tiny_setup's cache at the cache as it stands; a per-instance batch gets every instance's own"""
+        self._check(lib().tiny_batch_compute_sensitivity(self._h), "compute_sensitivity")
+
+    def sensitivity(self, name):
+        """what is installed, computed or set: 'dKinf_drho' (nu, nx), 'dPinf_drho' (nx, nx), 'dC1_drho' (nu, nu), 'dC2_drho' (nx, nx)"""
+        r, c = self._SENS_SHAPES[name](self)
+        out = np.zeros(r * c)
+        n = lib().tiny_batch_get_sensitivity(self._h, name.encode(), out.ctypes.data_as(_dp), r * c)
+        if n != r * c:
+            self._check(n if n < 0 else ERR_ARG, f"sensitivity({name})")
+        return out.reshape((r, c), order="F")
+
+    def sensitivity_instance(self, instance, name):
+        """... of one instance of a per-instance batch; also 'steps': the squarings its Lyapunov solve took"""
+        r, c = self._SENS_SHAPES[name](self)
+        out = np.zeros(r * c)
+        n = lib().tiny_batch_get_sensitivity_instance(self._h, int(instance), name.encode(), out.ctypes.data_as(_dp), r * c)
+        if n != r * c:
+            self._check(n if n < 0 else ERR_ARG, f"sensitivity_instance({name})")
+        return int(out[0]) if name == "steps" else out.reshape((r, c), order="F")
 
     _CACHE_SHAPES = {"rho": lambda s: (1, 1), "Kinf": lambda s: (s.nu, s.nx), "Pinf": lambda s: (s.nx, s.nx),
                      "C1": lambda s: (s.nu, s.nu), "C2": lambda s: (s.nx, s.nx)}

@@ -135,7 +135,8 @@ struct SolveArgs {
     int* next_count;
     // Adaptive rho (ADAPT variants; admm.cpp:397-423 + rho_benchmark.cpp): the cache is per-instance STATE -- rho, Kinf, Pinf
     // (and the dead copies C1, C2) move every 5th iteration and persist from solve to solve.  arho [batch]; aK [batch][nu*nx],
-    // aP [batch][nx*nx], aC1 [batch][nu*nu], aC2 [batch][nx*nx] column-major (aC1 / aC2 may be null); atab: ATAB_* lane tables.
+    // aP [batch][nx*nx], aC1 [batch][nu*nu], aC2 [batch][nx*nx] column-major (aC1 / aC2 may be null); atab: ATAB_* lane tables --
+    // one set for the family, or (HET && ADAPT) [batch][ATAB_DOUBLES], every instance's own (sensitivity_kernel.hip.h).
     double *arho, *aK, *aP, *aC1, *aC2;
     const double* atab;
     double arho_min, arho_max;
@@ -781,9 +782,15 @@ void admm_solve_kernel(const SolveArgs P) {
     // ADAPT: the lane tables every adaptation reads (ATAB_AT, ATAB_DK, ATAB_DP), lane-major [table][lane][AKC] so that a lane's
     // coefficients are consecutive (ds_read_b128), and each row's log of rho steps that C1 / C2 still have to take (flush_c)
     constexpr int AKC = NX > NU ? NX : NU;
-    __shared__ double sTab[ADAPT ? 3 * 16 * AKC : 1];
+    // HET && ADAPT: every row has its own instance's tables (SolveArgs::atab is then [batch][ATAB_DOUBLES]).  They are read through
+    // L2 at the adaptation itself -- every fifth iteration, three tables of at most 16 x 16 doubles per row -- instead of from four
+    // per-row LDS copies (4 x 3 * 16 * AKC doubles: 18 KB per wave at (12,4), which with the 9.5 KB below would leave five waves per CU where the LDS of the
+    // shared-family form leaves eight).  LDS per wave of the (12,4,10) form: sPt 1.5 KB + bounds 2 x 1.25 KB + sP 4.5 KB + sDl 1 KB =
+    // 9.5 KB, two waves per SIMD as the shared-family ADAPT form.
+    constexpr bool HA = HET && ADAPT;
+    __shared__ double sTab[(ADAPT && !HET) ? 3 * 16 * AKC : 1];
     __shared__ double sDl[ADAPT ? 4 * ADAPT_LOG : 1];
-    if constexpr (ADAPT)
+    if constexpr (ADAPT && !HET)
         for (int e = lane; e < 3 * 16 * AKC; e += 64) {
             const int t = e / (16 * AKC), r = e % (16 * AKC);
             sTab[e] = P.atab[t * 256 + (r % AKC) * 16 + r / AKC];              // ATAB_AT / ATAB_DK / ATAB_DP = 0 / 256 / 512
@@ -1058,6 +1065,10 @@ void admm_solve_kernel(const SolveArgs P) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
+            // ADAPT: the lane tables of the adaptation -- the family's, or (HET) this instance's own, re-based for every tile
+            const double* atab_i = nullptr;
+            if constexpr (HET && ADAPT) atab_i = P.atab + (size_t)b * ATAB_DOUBLES;
+            (void)atab_i;
             // record base of this lane: input lanes read knot s-1 at slot s
             const size_t lbase = (size_t)b * (N * NZ) + j - (is_input ? NZ : 0);
             double X[N], G[N], VN[N], VP[N], QX[N], Dn[N - 1];
@@ -1131,7 +1142,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     double* c2 = P.aC2 + (size_t)b * (NX * NX) + NX * j;
                     double v[NX], d[NX];
 #pragma unroll
-                    for (int k = 0; k < NX; ++k) { v[k] = c2[k]; d[k] = P.atab[ATAB_DC2 + k * 16 + j]; }
+                    for (int k = 0; k < NX; ++k) { v[k] = c2[k]; d[k] = P.atab[(HA ? (size_t)b * ATAB_DOUBLES : (size_t)0) + ATAB_DC2 + k * 16 + j]; }
                     for (int i = 0; i < n; ++i) {
                         const double dl = sDl[grp * ADAPT_LOG + i];
 #pragma unroll
@@ -1144,7 +1155,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     double* c1 = P.aC1 + (size_t)b * (NU * NU) + NU * j;
                     double v[NU], d[NU];
 #pragma unroll
-                    for (int k = 0; k < NU; ++k) { v[k] = c1[k]; d[k] = P.atab[ATAB_DC1 + k * 16 + j]; }
+                    for (int k = 0; k < NU; ++k) { v[k] = c1[k]; d[k] = P.atab[(HA ? (size_t)b * ATAB_DOUBLES : (size_t)0) + ATAB_DC1 + k * 16 + j]; }
                     for (int i = 0; i < n; ++i) {
                         const double dl = sDl[grp * ADAPT_LOG + i];
 #pragma unroll
@@ -1556,7 +1567,7 @@ void admm_solve_kernel(const SolveArgs P) {
                         if (it > 0 && it % 5 == 0) {
                             double at[NX];
 #pragma unroll
-                            for (int k = 0; k < NX; ++k) at[k] = sTab[j * AKC + k];
+                            for (int k = 0; k < NX; ++k) at[k] = HA ? atab_i[ATAB_AT + k * 16 + j] : sTab[j * AKC + k];
                             double pri_res = 0.0, ax_max = 0.0, z_max = 0.0, dual_res = 0.0, px_max = 0.0, aty_max = 0.0, q_max = 0.0;
                             double pxq_max = 0.0;              // max |Q x_i|, |R u_i| over the knots before the last: entries of P x AND of q
 #pragma unroll
@@ -1606,15 +1617,15 @@ void admm_solve_kernel(const SolveArgs P) {
                             const double delta = new_rho - rho;
                             if (is_state) {
 #pragma unroll
-                                for (int k = 0; k < NU; ++k) mb[NX + k] = -taylor_step(-mb[NX + k], delta, sTab[(16 + j) * AKC + k]);
+                                for (int k = 0; k < NU; ++k) mb[NX + k] = -taylor_step(-mb[NX + k], delta, (HA ? atab_i[ATAB_DK + k * 16 + j] : sTab[(16 + j) * AKC + k]));
 #pragma unroll
                                 for (int k = 0; k < NX; ++k) {
                                     const int e = grp * NX * NX + k + NX * j;
-                                    sP[e] = taylor_step(sP[e], delta, sTab[(32 + j) * AKC + k]);
+                                    sP[e] = taylor_step(sP[e], delta, (HA ? atab_i[ATAB_DP + k * 16 + j] : sTab[(32 + j) * AKC + k]));
                                 }
                             } else if (is_input) {
 #pragma unroll
-                                for (int k = 0; k < NX; ++k) mf1[k] = -taylor_step(-mf1[k], delta, sTab[(16 + j) * AKC + k]);
+                                for (int k = 0; k < NX; ++k) mf1[k] = -taylor_step(-mf1[k], delta, (HA ? atab_i[ATAB_DK + k * 16 + j] : sTab[(16 + j) * AKC + k]));
                             }
                             if (P.aC1 || P.aC2) {                                           // C1 / C2: logged, applied by flush_c
                                 if (j == 0) sDl[grp * ADAPT_LOG + ndl] = delta;

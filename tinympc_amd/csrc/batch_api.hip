@@ -347,7 +347,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_iter_log, b->d_u0_log, b->d_lslack, b->d_ldual, b->d_tlslack, b->d_tldual, b->d_gtab, b->d_traj,
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
-                    b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
     if (b->h_wire) hipHostFree(b->h_wire);
@@ -635,16 +635,102 @@ int tiny_batch_set_adaptive_rho(TinyBatch* b, int enable, double rho_min, double
 }
 
 // == cache->dKinf_drho (nu x nx), dPinf_drho (nx x nx), dC1_drho (nu x nu), dC2_drho (nx x nx), column-major, shared by every
-// instance (what tiny_initialize_sensitivity_matrices fills, tiny_api.cpp:479-540); dC1 / dC2 may be NULL (taken as zero)
+// instance (what tiny_initialize_sensitivity_matrices fills, tiny_api.cpp:479-540); dC1 / dC2 may be NULL (taken as zero).  On a
+// per-instance batch: the same tables for every instance (it replaces what tiny_batch_compute_sensitivity left)
 int tiny_batch_set_sensitivity(TinyBatch* b, const double* dKinf, const double* dPinf, const double* dC1, const double* dC2) {
     if (!b || !dKinf || !dPinf) return TINY_ERR_NULL;
     const size_t nx = b->nx, nu = b->nu;
+    b->sens_inst = false; b->sens_steps = 0;
     b->dKinf.assign(dKinf, dKinf + nu * nx);
     b->dPinf.assign(dPinf, dPinf + nx * nx);
     if (dC1) b->dC1.assign(dC1, dC1 + nu * nu); else b->dC1.clear();
     if (dC2) b->dC2.assign(dC2, dC2 + nx * nx); else b->dC2.clear();
     b->atab_dirty = true;
     return TINY_OK;
+}
+
+// The tables computed on the device (sensitivity_kernel.hip.h): the derivative of tiny_setup's cache with respect to rho, at the cache as
+// it stands (tiny_batch_set_cache included).  Shared family: one system through the kernel, installed as tiny_batch_set_sensitivity
+// installs the caller's.  Per-instance batch: every instance's own tables, kept on the device.
+int tiny_batch_compute_sensitivity(TinyBatch* b) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    const int nx = b->nx, nu = b->nu;
+    if (nx + nu > 32 || nu > 16) return fail(b, TINY_ERR_UNSUPPORTED, "the sensitivity kernel holds nx + nu <= 32, nu <= 16");
+    if (!b->hetero) {
+        std::vector<double> dK((size_t)nu * nx), dP((size_t)nx * nx), dC1((size_t)nu * nu), dC2((size_t)nx * nx);
+        int steps = -1;
+        const int rc = compute_sensitivity_host(nx, nu, b->A.a.data(), b->B.a.data(), b->cache.Kinf.a.data(), b->cache.Quu_inv.a.data(), dK.data(), dP.data(),
+                                                dC1.data(), dC2.data(), &steps, b->stream);
+        if (rc) return fail(b, rc, "the sensitivity kernel could not be run");
+        if (steps < 0) return fail(b, TINY_ERR_ARG, "the Lyapunov equation of the sensitivity tables did not converge (A - B Kinf is not a contraction)");
+        if (int rc2 = tiny_batch_set_sensitivity(b, dK.data(), dP.data(), dC1.data(), dC2.data())) return rc2;
+        b->sens_steps = steps;
+        return TINY_OK;
+    }
+    const size_t B = b->batch, xx = (size_t)nx * nx, xu = (size_t)nx * nu, uu = (size_t)nu * nu;
+    if (!b->d_sdK) {
+        HIP_TRY(b, hipMalloc(&b->d_sdK, B * xu * sizeof(double)));
+        HIP_TRY(b, hipMalloc(&b->d_sdP, B * xx * sizeof(double)));
+        HIP_TRY(b, hipMalloc(&b->d_sdC1, B * uu * sizeof(double)));
+        HIP_TRY(b, hipMalloc(&b->d_sdC2, B * xx * sizeof(double)));
+        HIP_TRY(b, hipMalloc(&b->d_ssteps, B * sizeof(int)));
+    }
+    if (nx + nu <= 16 && !b->d_atabs) HIP_TRY(b, hipMalloc(&b->d_atabs, B * ATAB_DOUBLES * sizeof(double)));
+    SensitivityArgs s = {};
+    s.A = b->d_hA; s.B = b->d_hB; s.Kinf = b->d_hK; s.Quu_inv = b->d_hQuu; s.riccati_iters = b->d_hiters;
+    s.dKinf = b->d_sdK; s.dPinf = b->d_sdP; s.dC1 = b->d_sdC1; s.dC2 = b->d_sdC2; s.steps = b->d_ssteps;
+    s.atabs = nx + nu <= 16 ? b->d_atabs : nullptr;
+    s.nx = nx; s.nu = nu; s.batch = b->batch;
+    // (as the Riccati launch: eight waves per CU in flight, fewer where the LDS of a wide shape holds fewer -- the rest of the batch by grid stride)
+    if (launch_sensitivity(b->stream, s, (int)std::min<size_t>(B, (size_t)b->num_cus * 8)) != TINY_OK) return fail(b, TINY_ERR_HIP, "the sensitivity kernel failed");
+    std::vector<int> st(B);
+    HIP_TRY(b, hipMemcpy(st.data(), b->d_ssteps, B * sizeof(int), hipMemcpyDeviceToHost));
+    b->sens_inst = true;
+    b->dKinf.clear(); b->dPinf.clear(); b->dC1.clear(); b->dC2.clear();
+    b->atab_dirty = true;
+    for (size_t i = 0; i < B; ++i)
+        if (st[i] < 0) return fail(b, TINY_ERR_ARG, "the Lyapunov equation of the sensitivity tables did not converge for instance %zu", i);
+    return TINY_OK;
+}
+
+// What is installed, computed or set: name = "dKinf_drho" | "dPinf_drho" | "dC1_drho" | "dC2_drho"; returns the element count
+int tiny_batch_get_sensitivity(TinyBatch* b, const char* name, double* out, int capacity) {
+    if (!b || !name) return TINY_ERR_NULL;
+    if (b->hetero && b->sens_inst) return fail(b, TINY_ERR_ARG, "this batch keeps per-instance sensitivity tables (tiny_batch_get_sensitivity_instance)");
+    const std::vector<double>* v = nullptr;
+    if (!strcmp(name, "dKinf_drho")) v = &b->dKinf;
+    else if (!strcmp(name, "dPinf_drho")) v = &b->dPinf;
+    else if (!strcmp(name, "dC1_drho")) v = &b->dC1;
+    else if (!strcmp(name, "dC2_drho")) v = &b->dC2;
+    else return fail(b, TINY_ERR_ARG, "unknown sensitivity table %s", name);
+    if (b->dKinf.empty()) return fail(b, TINY_ERR_ARG, "no sensitivity tables are installed (tiny_batch_set_sensitivity / tiny_batch_compute_sensitivity)");
+    if (out && capacity >= (int)v->size() && !v->empty()) memcpy(out, v->data(), v->size() * sizeof(double));
+    return (int)v->size();
+}
+// ... of ONE instance of a per-instance batch; name as above, or "steps" (Lyapunov squarings taken; 0: the tables were set by the caller)
+int tiny_batch_get_sensitivity_instance(TinyBatch* b, int instance, const char* name, double* out, int capacity) {
+    if (!b || !name || !out) return TINY_ERR_NULL;
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance out of range");
+    if (!(b->hetero && b->sens_inst)) {
+        if (!strcmp(name, "steps")) { if (capacity >= 1) out[0] = b->sens_steps; return 1; }
+        return tiny_batch_get_sensitivity(b, name, out, capacity);
+    }
+    HIP_TRY(b, hipSetDevice(b->device));
+    const int nx = b->nx, nu = b->nu;
+    const double* src = nullptr; int n = 0;
+    if (!strcmp(name, "dKinf_drho")) { src = b->d_sdK; n = nu * nx; }
+    else if (!strcmp(name, "dPinf_drho")) { src = b->d_sdP; n = nx * nx; }
+    else if (!strcmp(name, "dC1_drho")) { src = b->d_sdC1; n = nu * nu; }
+    else if (!strcmp(name, "dC2_drho")) { src = b->d_sdC2; n = nx * nx; }
+    else if (!strcmp(name, "steps")) {
+        int st = 0;
+        HIP_TRY(b, hipMemcpy(&st, b->d_ssteps + instance, sizeof(int), hipMemcpyDeviceToHost));
+        if (capacity >= 1) out[0] = st;
+        return 1;
+    } else return fail(b, TINY_ERR_ARG, "unknown sensitivity table %s", name);
+    if (capacity >= n) HIP_TRY(b, hipMemcpy(out, src + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
+    return n;
 }
 
 // Per-instance cache state of an adaptive batch, host arrays with a leading batch axis (column-major matrices): which =

@@ -49,6 +49,7 @@ int enqueue_lockstep_estimate(TinyBatch* b);
 // ---- launches besides launch_solve (batch_impl.hpp)
 int launch_general(TinyBatch* b, int phase = 0);
 int launch_riccati(TinyBatch* b, const RiccatiArgs& r, size_t lds_bytes, int grid);
+int launch_sensitivity(hipStream_t stream, const SensitivityArgs& s, int grid);
 // ---- the clock-checked dispatch: what probes left behind, the cost models as host arithmetic
 void learn_from_probe(TinyBatch* b, int max_iter, bool auto_split);
 void read_lockstep_estimate(TinyBatch* b);

@@ -114,9 +114,34 @@ static __global__ void broadcast_vec_kernel(double* __restrict__ dst, const doub
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) dst[i] = src[i % per];
 }
 
-// every instance's cache state <- the family's cache (rho, Kinf, Pinf, C1 = Quu_inv, C2 = AmBKt: tiny_api.cpp:375-376)
+// per-instance batch whose caller set ONE set of sensitivity tables: every instance's lane tables <- the family's (ATAB_DK ... ATAB_DC2)
+// with ATAB_AT from the instance's own A and B
+static __global__ __launch_bounds__(256) void expand_atabs_kernel(double* __restrict__ atabs, const double* __restrict__ atab, const double* __restrict__ A,
+                                                                  const double* __restrict__ B, int nx, int nu, int batch) {
+    const int e = threadIdx.x, k = e / 16, j = e % 16;
+    for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+        double* t = atabs + (size_t)b * ATAB_DOUBLES;
+        double at = 0.0;
+        if (k < nx && j < nx) at = A[(size_t)b * nx * nx + k + nx * j];
+        else if (k < nx && j < nx + nu) at = B[(size_t)b * nx * nu + k + nx * (j - nx)];
+        t[ATAB_AT + e] = at;
+        for (int o = ATAB_DK; o < ATAB_DOUBLES; o += 256) t[o + e] = atab[o + e];
+    }
+}
+
+// every instance's cache state <- the family's cache (rho, Kinf, Pinf, C1 = Quu_inv, C2 = AmBKt: tiny_api.cpp:375-376); per-instance
+// batch: <- the instance's own Riccati output
 int adaptive_fresh_state(TinyBatch* b) {
     const int nx = b->nx, nu = b->nu;
+    if (b->hetero) {
+        const size_t B = b->batch;
+        struct { double* dst; const double* src; size_t n; } parts[] = {{b->d_arho, b->d_hrho, B}, {b->d_aK, b->d_hK, B * nu * nx}, {b->d_aP, b->d_hP, B * nx * nx},
+                                                                        {b->d_aC1, b->d_hQuu, B * nu * nu}, {b->d_aC2, b->d_hAmBKt, B * nx * nx}};
+        for (auto& p : parts) HIP_TRY(b, hipMemcpyAsync(p.dst, p.src, p.n * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        b->astate_fresh = true;
+        return TINY_OK;
+    }
     std::vector<double> h;
     h.push_back(b->cache.rho);
     h.insert(h.end(), b->cache.Kinf.a.begin(), b->cache.Kinf.a.end());
@@ -154,9 +179,11 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
         if (int rc = adaptive_fresh_state(b)) return rc;
         b->atab_dirty = true;
     }
+    if (b->hetero && need_tables && !b->d_atabs) HIP_TRY(b, hipMalloc(&b->d_atabs, B * ATAB_DOUBLES * sizeof(double)));
+    if (b->hetero && b->sens_inst) return TINY_OK;           // (every instance's own tables: sensitivity_kernel wrote d_atabs)
     if (b->atab_dirty && need_tables) {
         if ((int)b->dKinf.size() != nu * nx || (int)b->dPinf.size() != nx * nx)
-            return fail(b, TINY_ERR_DIM, "adaptive rho is on but the sensitivity tables are not set (tiny_batch_set_sensitivity)");
+            return fail(b, TINY_ERR_DIM, "adaptive rho is on but the sensitivity tables are not set (tiny_batch_set_sensitivity / tiny_batch_compute_sensitivity)");
         std::vector<double> t(ATAB_DOUBLES, 0.0);
         auto at = [&](int base, int k, int j) -> double& { return t[(size_t)base + k * 16 + j]; };
         for (int j = 0; j < nx; ++j) {                       // state lanes
@@ -173,6 +200,10 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
         for (int j = 0; j < nu; ++j)                          // C1 is nu x nu: its column j is kept by lane j
             for (int k = 0; k < nu; ++k) at(ATAB_DC1, k, j) = b->dC1.empty() ? 0.0 : b->dC1[k + (size_t)nu * j];
         HIP_TRY(b, hipMemcpyAsync(b->d_atab, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
+        if (b->hetero) {
+            hipLaunchKernelGGL(expand_atabs_kernel, dim3((unsigned)std::min<size_t>(B, 2048)), dim3(256), 0, b->stream, b->d_atabs, b->d_atab, b->d_hA, b->d_hB, nx, nu, b->batch);
+            HIP_TRY(b, hipGetLastError());
+        }
         HIP_TRY(b, hipStreamSynchronize(b->stream));
         b->atab_dirty = false;
     }

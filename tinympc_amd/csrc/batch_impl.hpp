@@ -10,6 +10,7 @@
 #include "general_kernel.hip.h"
 #include "jit.hpp"
 #include "riccati_kernel.hip.h"
+#include "sensitivity_kernel.hip.h"
 #include "tile_kernel.hip.h"
 #include "cache.hpp"
 
@@ -210,6 +211,14 @@ struct TinyBatch {
     double adaptive_min = 1.0, adaptive_max = 100.0;
     std::vector<double> dKinf, dPinf, dC1, dC2;
     double *d_arho = nullptr, *d_aK = nullptr, *d_aP = nullptr, *d_aC1 = nullptr, *d_aC2 = nullptr, *d_atab = nullptr;
+    // tiny_batch_compute_sensitivity (sensitivity_kernel.hip.h).  Shared family: the result lands in dKinf ... dC2 above, sens_steps
+    // keeps the Lyapunov step count (0: the tables were set by the caller).  Per-instance batch: [batch][...] device arrays and the
+    // [batch][ATAB_DOUBLES] lane tables the HET && ADAPT form of the one-row kernel reads; sens_inst = they hold every instance's
+    // own tables (false: d_atabs is expanded from the caller's one set, see ensure_adaptive)
+    int sens_steps = 0;
+    bool sens_inst = false;
+    double *d_sdK = nullptr, *d_sdP = nullptr, *d_sdC1 = nullptr, *d_sdC2 = nullptr, *d_atabs = nullptr;
+    int* d_ssteps = nullptr;
     // tiny_batch_allreduce_stats (group_api.hip): the gather table of the 64-byte statistics messages, device + pinned host
     double *d_wire = nullptr, *h_wire = nullptr;
     int wire_ranks = 0;
@@ -222,6 +231,8 @@ struct TinyBatch {
 namespace tinympc_amd {
 int fail(TinyBatch* b, int code, const char* fmt, ...);
 int launch_solve(TinyBatch* b);
+int compute_sensitivity_host(int nx, int nu, const double* A, const double* B, const double* Kinf, const double* Quu_inv, double* dK, double* dP,
+                             double* dC1, double* dC2, int* steps, hipStream_t stream);   // batch_dispatch.hip: one system through sensitivity_kernel
 bool apply_shipped_plan(TinyBatch* b);               // batch_api.hip: the matching entry of data/plans.txt, if any, imported into a fresh handle
 int xfer_fields(TinyBatch* b, const TinyField* fields, const size_t* offsets, int n, double* d_buf, bool to_device,
                 bool with_status, size_t off_status, size_t off_resid);

@@ -916,6 +916,28 @@ void tiny_initialize_sensitivity_matrices(TinySolver* solver) {
     mat_assign(&c->dC2_drho, k_dC2_drho, 12, 12);
 }
 
+// the same four members for the solver's own system: sensitivity_kernel.hip.h at the solver's cache as it stands
+int tiny_compute_sensitivity(TinySolver* solver) {
+    if (!solver || !solver->cache || !solver->work) return TINY_ERR_NULL;
+    TinyCache* c = solver->cache;
+    const TinyWorkspace* w = solver->work;
+    const int nx = w->nx, nu = w->nu;
+    if (!shaped(c->Kinf, nu, nx) || !shaped(c->Quu_inv, nu, nu) || !shaped(w->Adyn, nx, nx) || !shaped(w->Bdyn, nx, nu)) return TINY_ERR_DIM;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return TINY_ERR_NO_DEVICE; }
+    if (hipSetDevice(0) != hipSuccess) { (void)hipGetLastError(); return TINY_ERR_NO_DEVICE; }
+    std::vector<double> dK((size_t)nu * nx), dP((size_t)nx * nx), dC1((size_t)nu * nu), dC2((size_t)nx * nx);
+    int steps = -1;
+    if (int rc = compute_sensitivity_host(nx, nu, w->Adyn.data, w->Bdyn.data, c->Kinf.data, c->Quu_inv.data, dK.data(), dP.data(), dC1.data(), dC2.data(),
+                                          &steps, nullptr)) return rc;
+    if (steps < 0) return TINY_ERR_ARG;
+    mat_assign(&c->dKinf_drho, dK.data(), nu, nx);
+    mat_assign(&c->dPinf_drho, dP.data(), nx, nx);
+    mat_assign(&c->dC1_drho, dC1.data(), nu, nu);
+    mat_assign(&c->dC2_drho, dC2.data(), nx, nx);
+    return 0;
+}
+
 int tiny_solve_batch(TinySolver** solvers, int n) { return solve_group(solvers, n); }
 
 // ---- admm.hpp:12-17: the phases of one iteration, each on the GPU ------------------------------

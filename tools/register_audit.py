@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """CPU only: register / scratch / occupancy report of every kernel instantiation compiled into the library
 (hipcc -Rpass-analysis=kernel-resource-usage on tinympc_amd/csrc/_gen/{k,t}_*.hip).  Scratch > 0 = spilled to memory.
+The one-row forms csrc/jit_prebuilt.txt names (run-time instantiated, never in a unit) are compiled here as explicit instantiations and
+listed after the compiled-in ones; the setup kernels of batch_dispatch.hip (riccati_kernel, sensitivity_kernel) come last.
     python tools/register_audit.py [--all] > profiles/rNN_register_audit.md"""
 import concurrent.futures
 import glob
@@ -11,21 +13,43 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GEN = os.path.join(ROOT, "tinympc_amd", "csrc", "_gen")
+CSRC = os.path.join(ROOT, "tinympc_amd", "csrc")
+GEN = os.path.join(CSRC, "_gen")
 
 
-def usage(src):
+def usage(src, cwd=GEN, extra=()):
     with tempfile.TemporaryDirectory() as tmp:
-        p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
-                            "-c", src, "-o", os.path.join(tmp, "o.o")], capture_output=True, text=True, cwd=GEN)
+        p = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage", *extra,
+                            "-c", src, "-o", os.path.join(tmp, "o.o")], capture_output=True, text=True, cwd=cwd)
     rows = []
     for b in p.stderr.split("Function Name:")[1:]:
         name = b.split()[0]
         g = lambda k: int(re.search(k + r": (\d+)", b).group(1))
-        rows.append(dict(kind="tile" if "tile_kernel" in name else "one-row", args=[int(v) for _, v in re.findall(r"L([ib])(\d+)E", name)],
+        rows.append(dict(kind="tile" if "tile_kernel" in name else "one-row", name=name, args=[int(v) for _, v in re.findall(r"L([ib])(\d+)E", name)],
                          vgpr=g("VGPRs"), agpr=g("AGPRs"), scratch=g(r"ScratchSize \[bytes/lane\]"), occ=g(r"Occupancy \[waves/SIMD\]"),
                          lds=g(r"LDS Size \[bytes/block\]")))
     return rows
+
+
+def prebuilt_one_row_rows():
+    """the one-row forms of csrc/jit_prebuilt.txt, each compiled as an explicit instantiation with its shape's fused step blocks"""
+    names = [l.split("#")[0].strip() for l in open(os.path.join(CSRC, "jit_prebuilt.txt"))]
+    rows = []
+    for n in (n for n in names if "admm_solve_kernel<" in n):
+        nx, nu = (int(v) for v in re.match(r".*admm_solve_kernel<\s*(\d+)\s*,\s*(\d+)", n).groups())
+        with tempfile.NamedTemporaryFile("w", suffix=".hip", dir=GEN, delete=False) as f:
+            f.write('#define TINYMPC_FUSED_NX %d\n#define TINYMPC_FUSED_NU %d\n#include "../admm_kernel.hip.h"\n'
+                    'template __global__ void tinympc_amd::%s(const tinympc_amd::SolveArgs);\n' % (nx, nu, n[n.index("admm_"):]))
+        try:
+            rows += usage(f.name)
+        finally:
+            os.unlink(f.name)
+    return rows
+
+
+def setup_kernel_rows():
+    """riccati_kernel / sensitivity_kernel: device code of batch_dispatch.hip"""
+    return [r for r in usage("batch_dispatch.hip", cwd=CSRC, extra=("--cuda-device-only",)) if re.search(r"riccati_kernel|sensitivity_kernel", r["name"])]
 
 
 def main():
@@ -54,6 +78,14 @@ def main():
         if len(a) >= 13 and a[12]:
             tag += ", PREFETCH form"
         print(f"| ({a[0]},{a[1]},{a[2]}) | {tag} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
+    pre = prebuilt_one_row_rows()
+    if pre:
+        print("\none-row forms of csrc/jit_prebuilt.txt (run-time instantiated; HET = per-instance problem data, ADAPT = adaptive rho):\n")
+        print("| (nx,nu,N) | variant | VGPR | AGPR | scratch B/lane | waves/SIMD | LDS B |")
+        print("|---|---|---|---|---|---|---|")
+        for r in pre:
+            a = r["args"]
+            print(f"| ({a[0]},{a[1]},{a[2]}) | soc{a[3]} dbg{a[4]} mode{a[5]} lin{a[6]} het{a[7]} adapt{a[9]} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
     print("\ntile kernel `admm_tile_kernel<NX,NU,N,W,R>`:\n")
     print("| (nx,nu,N) | W x R | form | VGPR | AGPR | scratch B/lane | waves/SIMD | LDS B |")
     print("|---|---|---|---|---|---|---|---|")
@@ -61,6 +93,12 @@ def main():
         a = r["args"]
         form = "box in registers (UB)" if len(a) >= 9 and a[8] else "box table in LDS"
         print(f"| ({a[0]},{a[1]},{a[2]}) | {a[3]} x {a[4]} | {form} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
+    print("\nsetup kernels of batch_dispatch.hip (one wavefront per instance; their LDS is dynamic, sized by the shape at launch):\n")
+    print("| kernel | VGPR | AGPR | scratch B/lane | waves/SIMD | static LDS B |")
+    print("|---|---|---|---|---|---|")
+    for r in setup_kernel_rows():
+        kname = "sensitivity_kernel" if "sensitivity_kernel" in r["name"] else "riccati_kernel"
+        print(f"| {kname} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
 
 
 if __name__ == "__main__":
