@@ -161,11 +161,14 @@ int tiny_batch_set_sensitivity(TinyBatch* b, const double* dKinf_drho, const dou
  * (tiny_api.hpp:29-31) and defines none; its quadrotor literals are a DIFFERENT set (not this derivative) and stay what
  * tiny_initialize_sensitivity_matrices installs.  Shared family: installed exactly as tiny_batch_set_sensitivity would.
  * Per-instance batch: every instance's own tables, kept on the device.  Any nx + nu <= 32, nu <= 16; TINY_ERR_ARG when
- * A - B Kinf is not a contraction (no derivative exists). */
+ * A - B Kinf is not a contraction (no derivative exists) -- nothing is installed then.  On a per-instance batch the message
+ * names the first such instance, NO instance's tables are usable and an adaptive solve fails with TINY_ERR_DIM until a later call
+ * succeeds or tiny_batch_set_sensitivity installs one set; tiny_batch_get_sensitivity_instance still reads what was computed. */
 int tiny_batch_compute_sensitivity(TinyBatch* b);
 /* What is installed, computed or set: name = "dKinf_drho" | "dPinf_drho" | "dC1_drho" | "dC2_drho"; returns the element count. */
 int tiny_batch_get_sensitivity(TinyBatch* b, const char* name, double* out, int capacity);
-/* ... of one instance of a per-instance batch; the same names, or "steps": the squarings the Lyapunov solve took (1 .. 64). */
+/* ... of one instance of a per-instance batch; the same names, or "steps": the squarings the Lyapunov solve took (1 .. 64;
+ * -1: it did not converge for this instance, 0: the tables were set by the caller). */
 int tiny_batch_get_sensitivity_instance(TinyBatch* b, int instance, const char* name, double* out, int capacity);
 /* per-instance cache state of an adaptive batch, host arrays with a leading batch axis, column-major matrices: which =
  * "rho" [batch], "Kinf" [batch][nu*nx], "Pinf" [batch][nx*nx], "C1" [batch][nu*nu], "C2" [batch][nx*nx] */

@@ -41,3 +41,36 @@ def test_a_loop_that_has_gone_chaotic_is_recognised_whatever_size_the_probe_has(
     assert three >= one and three > 0.1, (one, three)
     base, pert = f.oracle_episode(d, 1, 0.0), f.oracle_episode(d, 1, 1e-15)
     assert [it for _, _, it in base] == [it for _, _, it in pert]          # the iteration counts do not move: only the fields do
+
+
+def test_hetero_adaptive_draws_are_functions_of_the_seed():
+    """tools/fuzz_parity.py hetero_adaptive_draw: two draws of one seed are identical, down to every array, and the oracle half of a
+    trial (hetero_adaptive_oracle, hetero_adaptive_floor) runs from a draw alone"""
+    assert build_oracle()
+    import fuzz_parity as f
+    import sens_ref
+
+    def same(a, b):
+        if isinstance(a, dict):
+            return a.keys() == b.keys() and all(same(a[k], b[k]) for k in a)
+        if isinstance(a, (list, tuple)):
+            return len(a) == len(b) and all(same(x, y) for x, y in zip(a, b))
+        return np.array_equal(a, b)
+    seen = set()
+    for seed in range(1, 41):
+        a, b = f.hetero_adaptive_draw(seed), f.hetero_adaptive_draw(seed)
+        assert same(a, b), seed
+        assert (a["nx"], a["nu"], a["N"]) in f.HET_ADAPT_SHAPES and 1 <= a["B"] <= 9 and 0 <= a["kw"]["max_iter"] <= 59
+        assert len({fam["rho"] for fam in a["fams"]}) == a["B"]                    # every instance its own rho
+        seen.add(((a["nx"], a["nu"], a["N"]), a["tables"] is None, a["cache"] is None, "state_cone" in a["kw"]))
+        if "state_cone" in a["kw"]:
+            assert (a["nx"], a["nu"], a["N"]) == (6, 3, 10)
+    assert {k[0] for k in seen} == set(f.HET_ADAPT_SHAPES) and {k[1] for k in seen} == {k[2] for k in seen} == {k[3] for k in seen} == {True, False}
+    d = f.hetero_adaptive_draw(8)                                                  # (6, 3, 10), B = 4, computed tables
+    assert (d["nx"], d["B"], d["tables"]) == (6, 4, None)
+    fam = d["fams"][1]
+    K, _, C1, _ = sens_ref.dare_cache(fam["A"], fam["B"], fam["Q"], fam["R"], fam["rho"])
+    tab = sens_ref.tables(fam["A"], fam["B"], K, C1)
+    r1, r2 = f.hetero_adaptive_oracle(d, 1, tab), f.hetero_adaptive_oracle(d, 1, tab)
+    assert r1["counts"] == r2["counts"] and all(np.array_equal(r1[k], r2[k]) for k in r1 if k != "counts")
+    assert f.hetero_adaptive_floor(d, 1, tab) < 1e-9

@@ -201,10 +201,11 @@ STATE = ("Kinf", "Pinf", "C1", "C2")
 BOX = dict(x_min=-2.0, x_max=2.0, u_min=-0.4, u_max=0.4)
 
 
-def oracle_runs(fam, tables, x0, Xref, Uref, clip, scale=1.0, max_iter=80):
-    """one cold solve, then a warm one from 0.9 x0 (the cache state persists) -> [record, record]"""
+def oracle_runs(fam, tables, x0, Xref, Uref, clip, scale=1.0, max_iter=80, **settings):
+    """one cold solve, then a warm one from 0.9 x0 (the cache state persists) -> [record, record]; settings: further entries of the
+    oracle's config (abs_pri_tol, abs_dua_tol, ...)"""
     nx, nu = fam["nx"], fam["nu"]
-    cfg = sc.adaptive_cfg(sc.default_config(fam, max_iter=max_iter, x_min=np.full((nx, 1), BOX["x_min"]), x_max=np.full((nx, 1), BOX["x_max"]),
+    cfg = sc.adaptive_cfg(sc.default_config(fam, max_iter=max_iter, **settings, x_min=np.full((nx, 1), BOX["x_min"]), x_max=np.full((nx, 1), BOX["x_max"]),
                                             u_min=np.full((nu, 1), BOX["u_min"]), u_max=np.full((nu, 1), BOX["u_max"])),
                           rho_min=0.7, rho_max=6.0, clip=clip, sensitivity={k: np.asarray(tables[k]) * scale for k in NAMES})
     o = sc.make_solver(OracleSolver, fam, cfg)
@@ -277,14 +278,20 @@ def test_shared_family_adaptive_solve_with_computed_tables_matches_the_oracle():
 HET_SEED = 1300
 
 
-def het_setup(nx, nu, N, B=11):
-    fams = [random_family(nx, nu, N, HET_SEED + 17 * i + nx) for i in range(B)]
-    rng = np.random.default_rng(HET_SEED + nx + N)
+def het_data(nx, nu, N, B=11, seed=HET_SEED):
+    """the families, x0 and references of het_setup (numpy only)"""
+    fams = [random_family(nx, nu, N, seed + 17 * i + nx) for i in range(B)]
+    rng = np.random.default_rng(seed + nx + N)
     for f in fams:
         f["rho"] = float(rng.uniform(1.0, 3.0))
     x0 = rng.uniform(-1, 1, (B, nx))
     Xref = np.repeat(rng.uniform(-0.3, 0.3, (B, nx, 1)), N, axis=2) + rng.normal(0, 0.02, (B, nx, N))
     Uref = rng.normal(0, 0.05, (B, nu, N - 1))
+    return fams, x0, Xref, Uref
+
+
+def het_setup(nx, nu, N, B=11, seed=HET_SEED):
+    fams, x0, Xref, Uref = het_data(nx, nu, N, B, seed)
     s = hetero_batch(fams, N)
     s.set_bound_constraints(np.full((nx, 1), BOX["x_min"]), np.full((nx, 1), BOX["x_max"]), np.full((nu, 1), BOX["u_min"]), np.full((nu, 1), BOX["u_max"]))
     s.update_settings(max_iter=80)

@@ -640,7 +640,7 @@ int tiny_batch_set_adaptive_rho(TinyBatch* b, int enable, double rho_min, double
 int tiny_batch_set_sensitivity(TinyBatch* b, const double* dKinf, const double* dPinf, const double* dC1, const double* dC2) {
     if (!b || !dKinf || !dPinf) return TINY_ERR_NULL;
     const size_t nx = b->nx, nu = b->nu;
-    b->sens_inst = false; b->sens_steps = 0;
+    b->sens_inst = false; b->sens_failed = false; b->sens_steps = 0;
     b->dKinf.assign(dKinf, dKinf + nu * nx);
     b->dPinf.assign(dPinf, dPinf + nx * nx);
     if (dC1) b->dC1.assign(dC1, dC1 + nu * nu); else b->dC1.clear();
@@ -686,11 +686,17 @@ int tiny_batch_compute_sensitivity(TinyBatch* b) {
     if (launch_sensitivity(b->stream, s, (int)std::min<size_t>(B, (size_t)b->num_cus * 8)) != TINY_OK) return fail(b, TINY_ERR_HIP, "the sensitivity kernel failed");
     std::vector<int> st(B);
     HIP_TRY(b, hipMemcpy(st.data(), b->d_ssteps, B * sizeof(int), hipMemcpyDeviceToHost));
-    b->sens_inst = true;
+    // (the kernel wrote over whatever d_atabs held: the caller's one set is gone whether or not every instance converged)
     b->dKinf.clear(); b->dPinf.clear(); b->dC1.clear(); b->dC2.clear();
     b->atab_dirty = true;
+    b->sens_inst = false; b->sens_failed = false;
     for (size_t i = 0; i < B; ++i)
-        if (st[i] < 0) return fail(b, TINY_ERR_ARG, "the Lyapunov equation of the sensitivity tables did not converge for instance %zu", i);
+        if (st[i] < 0) {
+            // nothing is installed: ensure_adaptive refuses the adaptive solve; tiny_batch_get_sensitivity_instance still reads the arrays
+            b->sens_failed = true;
+            return fail(b, TINY_ERR_ARG, "the Lyapunov equation of the sensitivity tables did not converge for instance %zu", i);
+        }
+    b->sens_inst = true;
     return TINY_OK;
 }
 
@@ -712,7 +718,7 @@ int tiny_batch_get_sensitivity(TinyBatch* b, const char* name, double* out, int 
 int tiny_batch_get_sensitivity_instance(TinyBatch* b, int instance, const char* name, double* out, int capacity) {
     if (!b || !name || !out) return TINY_ERR_NULL;
     if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance out of range");
-    if (!(b->hetero && b->sens_inst)) {
+    if (!(b->hetero && (b->sens_inst || b->sens_failed))) {
         if (!strcmp(name, "steps")) { if (capacity >= 1) out[0] = b->sens_steps; return 1; }
         return tiny_batch_get_sensitivity(b, name, out, capacity);
     }

@@ -181,6 +181,9 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
     }
     if (b->hetero && need_tables && !b->d_atabs) HIP_TRY(b, hipMalloc(&b->d_atabs, B * ATAB_DOUBLES * sizeof(double)));
     if (b->hetero && b->sens_inst) return TINY_OK;           // (every instance's own tables: sensitivity_kernel wrote d_atabs)
+    if (b->hetero && b->sens_failed && need_tables)
+        return fail(b, TINY_ERR_DIM, "adaptive rho is on but tiny_batch_compute_sensitivity failed for at least one instance (steps = -1 in "
+                                     "tiny_batch_get_sensitivity_instance): no tables are installed");
     if (b->atab_dirty && need_tables) {
         if ((int)b->dKinf.size() != nu * nx || (int)b->dPinf.size() != nx * nx)
             return fail(b, TINY_ERR_DIM, "adaptive rho is on but the sensitivity tables are not set (tiny_batch_set_sensitivity / tiny_batch_compute_sensitivity)");

@@ -214,9 +214,11 @@ struct TinyBatch {
     // tiny_batch_compute_sensitivity (sensitivity_kernel.hip.h).  Shared family: the result lands in dKinf ... dC2 above, sens_steps
     // keeps the Lyapunov step count (0: the tables were set by the caller).  Per-instance batch: [batch][...] device arrays and the
     // [batch][ATAB_DOUBLES] lane tables the HET && ADAPT form of the one-row kernel reads; sens_inst = they hold every instance's
-    // own tables (false: d_atabs is expanded from the caller's one set, see ensure_adaptive)
+    // own tables (false: d_atabs is expanded from the caller's one set, see ensure_adaptive).  sens_failed: the last per-instance
+    // computation left at least one instance without a derivative -- nothing is installed (an adaptive solve is refused), the
+    // per-instance arrays stay readable so that the caller can find out which instances failed (steps = -1)
     int sens_steps = 0;
-    bool sens_inst = false;
+    bool sens_inst = false, sens_failed = false;
     double *d_sdK = nullptr, *d_sdP = nullptr, *d_sdC1 = nullptr, *d_sdC2 = nullptr, *d_atabs = nullptr;
     int* d_ssteps = nullptr;
     // tiny_batch_allreduce_stats (group_api.hip): the gather table of the 64-byte statistics messages, device + pinned host

@@ -2,7 +2,7 @@
 """Differential fuzzing of the HIP path against the oracle: random shapes (register, tile and coverage kernels), random
 problem data, random settings (check_termination 0..4, odd max_iter, tolerances, every enable switch, cones, static and
 time-varying half-spaces), random warm states.  Bar: identical iteration counts / solved flags, fields within 1e-9.
-    python tools/fuzz_parity.py [n_trials] [seed]"""
+    python tools/fuzz_parity.py [n_trials] [seed] [phases | adaptive | hetero_adaptive]"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,6 +141,146 @@ def adaptive_trial(seed):
     return None
 
 
+HET_ADAPT_SHAPES = [(12, 4, 10), (6, 3, 10), (5, 3, 7)]
+HET_ADAPT_FIELDS = ("x", "u", "vnew", "znew", "g", "y", "v", "z")
+HET_ADAPT_SOC = ("vcnew", "zcnew", "gc", "yc")
+
+
+def hetero_adaptive_draw(seed):
+    """Everything a hetero_adaptive_trial needs that does not come from the device: a pure function of the seed (numpy only)."""
+    rng = np.random.default_rng(seed + 909_000)
+    nx, nu, N = HET_ADAPT_SHAPES[rng.integers(len(HET_ADAPT_SHAPES))]
+    B = int(rng.integers(1, 10))
+    fams = []
+    for _ in range(B):                                   # every instance its own system and its own rho
+        M = rng.standard_normal((nx, nx))
+        A = M * rng.uniform(0.5, 0.99) / np.max(np.abs(np.linalg.eigvals(M)))
+        fams.append(dict(nx=nx, nu=nu, N=N, rho=float(rng.uniform(0.5, 5.0)), A=A, B=rng.standard_normal((nx, nu)) / np.sqrt(nx),
+                         f=rng.normal(0, 0.01, nx), Q=rng.uniform(1, 10, nx), R=rng.uniform(0.1, 1, nu)))
+    kw = dict(max_iter=int(rng.integers(0, 60)), check_termination=int(rng.integers(0, 4)), abs_pri_tol=float(10 ** rng.uniform(-4, -1)),
+              abs_dua_tol=float(10 ** rng.uniform(-4, -1)), en_state_bound=int(rng.integers(0, 2)), en_input_bound=int(rng.integers(0, 2)),
+              x_min=rng.uniform(-2.0, -0.1, (nx, N)), x_max=rng.uniform(0.1, 2.0, (nx, N)),
+              u_min=rng.uniform(-1.0, -0.05, (nu, N - 1)), u_max=rng.uniform(0.05, 1.0, (nu, N - 1)))
+    if (nx, nu, N) == (6, 3, 10) and rng.random() < 0.2:     # one 3-row cone per family (the one further run-time instantiation)
+        kw.update(en_state_soc=int(rng.integers(0, 2)), en_input_soc=int(rng.integers(0, 2)),
+                  state_cone=([int(rng.integers(0, nx - 2))], [3], [float(rng.uniform(0.2, 1.5))]),
+                  input_cone=([0], [3], [float(rng.uniform(0.2, 1.5))]))
+    lo = float(rng.uniform(0.3, 2.0))
+    adapt = dict(rho_min=lo, rho_max=lo * float(rng.uniform(2, 50)), clip=int(rng.random() < 0.8))
+    cases = sc.zero_cases(fams[0], B)
+    warm = bool(rng.random() < 0.5)
+    for k, v in cases.items():
+        if k in ("x0", "Xref", "Uref") or warm:
+            cases[k] = rng.normal(0.0, 0.4, v.shape)
+    cache = None
+    if rng.random() < 0.5:                               # every instance starts from a moved rho and slightly moved Kinf / Pinf / C1 / C2:
+        shapes = {"Kinf": (nu, nx), "Pinf": (nx, nx), "C1": (nu, nu), "C2": (nx, nx)}      # factors on its own fresh cache
+        cache = {"rho": rng.uniform(0.5, 2.0, B)}
+        for k in sc.CACHE_STATE:
+            cache[k] = 1.0 + rng.normal(0, 1e-3, (B,) + shapes[k])
+    tables = None
+    if rng.random() < 0.5:                               # one random set for all instances (set_sensitivity); else: computed, per instance
+        tables = {"dKinf_drho": rng.normal(0, 2e-3, (nu, nx)), "dPinf_drho": rng.normal(0, 5e-2, (nx, nx)),
+                  "dC1_drho": rng.normal(0, 1e-3, (nu, nu)), "dC2_drho": rng.normal(0, 1e-3, (nx, nx))}
+    return dict(nx=nx, nu=nu, N=N, B=B, fams=fams, kw=kw, adapt=adapt, cases=cases, warm=warm, cache=cache, tables=tables)
+
+
+def hetero_adaptive_oracle(d, i, tables, scale=1.0):
+    """instance i of a draw on its own oracle with the given tables (times scale) -> record of everything the trial compares"""
+    fam = d["fams"][i]
+    cfg = sc.adaptive_cfg(sc.default_config(fam, **d["kw"]), sensitivity={k: np.asarray(tables[k]) * scale for k in sc.SENS}, **d["adapt"])
+    o = sc.make_solver(OracleSolver, fam, cfg)
+    sc.load_case(o, d["cases"], i)
+    if d["cache"] is not None:
+        o.set("rho", fam["rho"] * d["cache"]["rho"][i])
+        for k in sc.CACHE_STATE:
+            o[k] = o[k] * d["cache"][k][i]
+    o.solve()
+    soc = cfg["en_state_soc"] or cfg["en_input_soc"]
+    rec = {k: o[k].copy() for k in HET_ADAPT_FIELDS + (HET_ADAPT_SOC if soc else ()) + sc.CACHE_STATE}
+    rec["rho"] = np.array([o.get("rho")])
+    rec["counts"] = (int(o.get("sol_iter")), int(o.get("sol_solved")), int(o.get("status")))
+    o.close()
+    return rec
+
+
+def hetero_adaptive_floor(d, i, tables):
+    """the oracle's own amplification of a 1e-15 relative change of the tables (tests/test_gpu_sensitivity.py): worst relative field
+    difference of the two runs, inf where their iteration counts differ"""
+    a, b = hetero_adaptive_oracle(d, i, tables), hetero_adaptive_oracle(d, i, tables, 1.0 + 1e-15)
+    if a["counts"] != b["counts"] or not all(np.all(np.isfinite(a[k])) for k in a if k != "counts"):
+        return float("inf")
+    return max(rel_err(b[k], a[k]) for k in a if k != "counts")
+
+
+def hetero_adaptive_run(d):
+    """the draw on the device (per-instance batch, HET && ADAPT form of the one-row kernel) against one oracle per instance"""
+    import tinympc_amd as tm
+    nx, nu, N, B, fams, kw, cases = (d[k] for k in ("nx", "nu", "N", "B", "fams", "kw", "cases"))
+    soc = bool(kw.get("en_state_soc") or kw.get("en_input_soc"))
+    s = tm.TinyBatchSolver.hetero(*[np.stack([f[k] for f in fams]) for k in ("A", "B", "f", "Q", "R")], np.array([f["rho"] for f in fams]), N)
+    try:
+        s.set_bound_constraints(kw["x_min"], kw["x_max"], kw["u_min"], kw["u_max"])
+        if "state_cone" in kw:
+            s.set_cone_constraints(*kw["state_cone"], *kw["input_cone"])
+        s.update_settings(kw["abs_pri_tol"], kw["abs_dua_tol"], kw["max_iter"], kw["check_termination"], kw["en_state_bound"], kw["en_input_bound"],
+                          kw.get("en_state_soc", 0), kw.get("en_input_soc", 0))
+        if d["tables"] is None:
+            s.compute_sensitivity()
+            tables = [{k: s.sensitivity_instance(i, k) for k in sc.SENS} for i in range(B)]
+        else:
+            s.set_sensitivity(*[d["tables"][k] for k in sc.SENS])
+            tables = [d["tables"]] * B
+        s.set_adaptive_rho(1, d["adapt"]["rho_min"], d["adapt"]["rho_max"], d["adapt"]["clip"])
+        s.set_x0(cases["x0"])
+        for f in ("Xref", "Uref", "vnew", "znew", "g", "y", "v", "z", "x", "u") + (("gc", "yc") if soc else ()):
+            s.set(f, cases[f])
+        if d["cache"] is not None:
+            s.set_cache_state("rho", np.array([f["rho"] for f in fams]) * d["cache"]["rho"])
+            for k in sc.CACHE_STATE:
+                s.set_cache_state(k, s.get_cache_state(k) * d["cache"][k])
+        s.solve()
+        st = s.status()
+        out = {k: s.get(k) for k in HET_ADAPT_FIELDS + (HET_ADAPT_SOC if soc else ())}
+        out.update({k: s.get_cache_state(k) for k in sc.CACHE_STATE + ("rho",)})
+        path = s.kernel_path()
+    finally:
+        s.close()
+    desc = (f"seed {d['seed']} hetero adaptive shape {(nx, nu, N)} B {B} max_iter {kw['max_iter']} ct {kw['check_termination']} "
+            f"soc {kw.get('en_state_soc', 0)}{kw.get('en_input_soc', 0)} tables {'set' if d['tables'] is not None else 'computed'} "
+            f"cache {'moved' if d['cache'] is not None else 'fresh'} warm {int(d['warm'])} [{path}]")
+    if path not in ("regs", "jit"):
+        return f"{desc}: the launch left the one-row kernel"
+    for i in range(B):
+        ref = hetero_adaptive_oracle(d, i, tables[i])
+        got = (int(st["iter"][i]), int(st["solved"][i]), int(st["status"][i]))
+        worst, wk = 0.0, ""
+        for k, v in ref.items():
+            if k != "counts":
+                e = rel_err(np.atleast_1d(out[k][i]), v)
+                if not e <= worst:                       # (a NaN counts as the worst)
+                    worst, wk = e, k
+        if got == ref["counts"] and worst <= 1e-7:
+            continue
+        floor = hetero_adaptive_floor(d, i, tables[i])  # ill-conditioned: the oracle itself moves that far for one rounding in the tables
+        what = f"counts {got} vs {ref['counts']}" if got != ref["counts"] else f"worst error {worst:.3e} in {wk}"
+        if (got != ref["counts"] and floor == float("inf")) or (got == ref["counts"] and worst <= 100.0 * floor):
+            return f"SKIP {desc}: instance {i} {what}, ill-conditioned (oracle amplification {floor:.3e})"
+        return f"{desc}: instance {i} {what} (oracle amplification {floor:.3e})"
+    return None
+
+
+def hetero_adaptive_trial(seed):
+    """Adaptive rho on per-instance batches (the HET && ADAPT form of the one-row kernel): random systems with their own rho, settings,
+    knot-varying bounds, clip range, cold or warm iterates, per-instance starting cache state, computed or set tables, cones on
+    (6, 3, 10).  Every instance against its own oracle: identical iter / solved / status; rho, fields and the moved cache to 1e-7
+    (adaptive_trial's figure).  Beyond it the oracle's own amplification of a 1e-15 relative change of the tables decides: a deviation
+    within 100 x that amplification is returned as "SKIP ..." (ill-conditioned trial), anything else as a mismatch."""
+    d = hetero_adaptive_draw(seed)
+    d["seed"] = seed
+    return hetero_adaptive_run(d)
+
+
 PHASES = ("update_linear_cost", "backward_pass_grad", "forward_pass", "update_slack", "update_dual")
 
 
@@ -199,10 +339,12 @@ if __name__ == "__main__":
         trial = phase_trial
     if len(sys.argv) > 3 and sys.argv[3] == "adaptive":
         trial = adaptive_trial
+    if len(sys.argv) > 3 and sys.argv[3] == "hetero_adaptive":
+        trial = hetero_adaptive_trial
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     s0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     assert build_oracle()
-    bad = 0
+    bad = skipped = 0
     for seed in range(s0, s0 + n):
         if os.environ.get("FUZZ_VERBOSE"):
             print("seed", seed, flush=True)
@@ -210,8 +352,11 @@ if __name__ == "__main__":
             r = trial(seed)
         except Exception as e:                      # noqa: BLE001
             r = f"seed {seed}: {type(e).__name__}: {e}"
-        if r:
+        if r and r.startswith("SKIP "):             # (hetero_adaptive: an ill-conditioned trial, see hetero_adaptive_trial)
+            skipped += 1
+            print(r, flush=True)
+        elif r:
             bad += 1
             print("MISMATCH", r, flush=True)
-    print(f"{n} trials, {bad} mismatches")
+    print(f"{n} trials, {bad} mismatches" + (f", {skipped} skipped as ill-conditioned" if skipped else ""))
     sys.exit(1 if bad else 0)
