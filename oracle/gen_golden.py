@@ -20,10 +20,13 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "g
 
 
 def main():
-    """python oracle/gen_golden.py [--only name,name,...]   (--only: just those single-solve suites of section 2)"""
+    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges   (--only: just those single-solve suites of section 2;
+    --soc-edges: just section 6, tests/golden/project_soc_edges.npz)"""
     if build_ref() is None:
         sys.exit("oracle/_ref/libtinympc_ref.so missing and /root/reference absent")
     os.makedirs(OUT, exist_ok=True)
+    if "--soc-edges" in sys.argv:
+        return project_soc_edges()
     only = None
     if "--only" in sys.argv:
         only = set(sys.argv[sys.argv.index("--only") + 1].split(","))
@@ -166,8 +169,24 @@ def episode_and_phase_kats():
         "primal_residual_state", "dual_residual_state", "primal_residual_input", "dual_residual_input")])
     s.close()
     np.savez_compressed(os.path.join(OUT, "phase_kat.npz"), **ph)
+    project_soc_edges()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes:", tot)
+
+
+def project_soc_edges():
+    # 6. project_soc (admm.cpp:39-60) on the directed set of tests/soc_ref.py: inputs within a float rounding of a branch boundary, at
+    # the margin of the kernels' all-inside fast path, at both ends of the float and double ranges, non-finite, at mu = 2^+-60, 2^+-61,
+    # 0 and -0.5 -- the reference's own answers, compared bit for bit by tests/test_soc_ref_cpu.py and tests/test_gpu_soc_edges.py
+    sys.path.insert(0, os.path.join(OUT, ".."))
+    import soc_ref
+    S, mus, labels, names = soc_ref.fixture_items()
+    prob, _ = sc.load_problem("codegen_random")
+    s = sc.make_solver(RefSolver, prob, sc.default_config(prob))
+    P = np.stack([s.project_soc(S[i], mus[i]) for i in range(len(S))])
+    s.close()
+    np.savez_compressed(os.path.join(OUT, "project_soc_edges.npz"), s=S, mu=mus, out=P, label=labels, names=np.array(names))
+    print("project_soc_edges: items", len(S), "bytes", os.path.getsize(os.path.join(OUT, "project_soc_edges.npz")))
 
 
 if __name__ == "__main__":
