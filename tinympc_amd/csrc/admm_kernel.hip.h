@@ -40,16 +40,10 @@
 
 namespace tinympc_amd {
 
-// ---- table layout shared with the host (batch_api.cpp builds it) --------------------------
-// All lane tables are [column k][lane j] with 16 lanes, doubles.
-enum : int {
-    TAB_MB = 0,          // backward:  cols k<nx multiply p_{i+1}[k], cols nx.. multiply r_i[k-nx]
-    TAB_MF1 = 256,       // forward 1: cols k<nx multiply x_i[k]   (state lanes: A, input lanes: -Kinf)
-    TAB_MF2 = 512,       // forward 2: cols nx.. multiply u_i[k-nx] (state lanes: B)
-    TAB_PT = 768,        // terminal:  cols k<nx multiply Xref[k, N-1] (state lanes: Pinf[k][j])
-    TAB_VEC = 1024,      // 16-entry lane vectors, see VEC_* below
-    TAB_BOUNDS = 1024 + 16 * 16,
-};
+// ---- table layout shared with the host (batch_tables.hip builds it) -----------------------
+// All lane tables are [column k][lane j], doubles: four matrices of `cols` columns x `lw` lanes, the VEC_* lane vectors, the bounds
+// [lo | hi][N][lw], then the half-space blocks (below).  The one statement of the layout: every writer and reader of a table -- the
+// host builders, the Riccati epilogue, the coverage kernel's per-instance load, both register kernels -- takes its offsets from here.
 enum : int {
     VEC_CB = 0,          // backward constant: APf (state lanes), Quu_inv*BPf (input lanes)
     VEC_CF = 1,          // forward constant: fdyn (state lanes)
@@ -59,9 +53,29 @@ enum : int {
     VEC_SOCFLAG = 5,     // 1.0 when this lane's cone slack is enabled (admm.cpp:102-109)
     VEC_CONE_BASE = 6,   // first lane of the cone this lane belongs to, or -1
     VEC_CONE_MU = 7,     // cone coefficient (double; truncated to float as admm.cpp:39 does)
-    VEC_LINFLAG = 9,     // 1.0 when this lane has a static linear-constraint slack (admm.cpp:138-145); 8 = VEC_RHO
+    VEC_RHO = 8,         // per-instance tables only (HET; written by riccati_kernel.hip.h): the instance's rho on every lane
+    VEC_LINFLAG = 9,     // 1.0 when this lane has a static linear-constraint slack (admm.cpp:138-145)
     VEC_TLINFLAG = 10,   // same for the time-varying family (admm.cpp:176-183)
     VEC_COUNT = 16,
+};
+struct LaneTab {
+    int cols, lw;
+    constexpr int MB() const { return 0; }                    // backward:  cols k<nx multiply p_{i+1}[k], cols nx.. multiply r_i[k-nx]
+    constexpr int MF1() const { return cols * lw; }           // forward 1: cols k<nx multiply x_i[k]   (state lanes: A, input lanes: -Kinf)
+    constexpr int MF2() const { return 2 * cols * lw; }       // forward 2: cols nx.. multiply u_i[k-nx] (state lanes: B)
+    constexpr int PT() const { return 3 * cols * lw; }        // terminal:  cols k<nx multiply Xref[k, N-1] (state lanes: Pinf[k][j])
+    constexpr int VEC() const { return 4 * cols * lw; }       // lw-entry lane vectors, see VEC_* above
+    constexpr int BOUNDS() const { return VEC() + VEC_COUNT * lw; }
+    constexpr int het_doubles() const { return BOUNDS(); }    // a per-instance table: the matrix + vector part (bounds / cones / masks stay shared)
+    // half-space tables of the LIN variants behind the bounds: static [3][kmax][lw], then per slot [N][3][kmax][lw]
+    constexpr int lin_offset(int N) const { return BOUNDS() + 2 * N * lw; }
+    constexpr int tlin_offset(int N, int kmax) const { return lin_offset(N) + 3 * kmax * lw; }
+    constexpr int doubles(int N, int kmax) const { return tlin_offset(N, kmax) + 3 * N * kmax * lw; }
+};
+constexpr LaneTab ROW_TAB{16, 16};                            // the one-row kernel's tables (the tile kernel's: tile_kernel.hip.h TileTab<W>)
+enum : int {
+    TAB_MB = ROW_TAB.MB(), TAB_MF1 = ROW_TAB.MF1(), TAB_MF2 = ROW_TAB.MF2(), TAB_PT = ROW_TAB.PT(), TAB_VEC = ROW_TAB.VEC(),
+    TAB_BOUNDS = ROW_TAB.BOUNDS(),
 };
 // Half-space tables of the register-resident linear-constraint variant, appended after the bounds.  Each entry is
 // [constraint k < LIN_KMAX][16 lanes]: the coefficient of this lane's row (state lanes: Alin_x[k][j], input lanes:
@@ -77,9 +91,9 @@ enum : int {
     ATAB_DC2 = 1024,     // dC2_drho:   state lanes cols k<nx dC2[k][j]
     ATAB_DOUBLES = 1280,
 };
-static inline int tab_lin_offset(int N) { return TAB_BOUNDS + 2 * N * 16; }
-static inline int tab_tlin_offset(int N, int kmax = LIN_KMAX) { return tab_lin_offset(N) + 3 * kmax * 16; }
-static inline int tab_doubles(int N, int kmax = LIN_KMAX) { return tab_tlin_offset(N, kmax) + 3 * N * kmax * 16; }
+static inline int tab_lin_offset(int N) { return ROW_TAB.lin_offset(N); }
+static inline int tab_tlin_offset(int N, int kmax = LIN_KMAX) { return ROW_TAB.tlin_offset(N, kmax); }
+static inline int tab_doubles(int N, int kmax = LIN_KMAX) { return ROW_TAB.doubles(N, kmax); }
 
 struct SolveArgs {
     const double* tab;        // tab_doubles(N) doubles
@@ -1024,7 +1038,7 @@ void admm_solve_kernel(const SolveArgs P) {
                 cb = het[TAB_VEC + VEC_CB * 16 + j];
                 cf = het[TAB_VEC + VEC_CF * 16 + j];
                 qr = het[TAB_VEC + VEC_QR * 16 + j];
-                rho = het[TAB_VEC + 8 * 16 + j];               // VEC_RHO (riccati_kernel.hip.h)
+                rho = het[TAB_VEC + VEC_RHO * 16 + j];
             }
             if constexpr (ADAPT) {                             // this instance's own rho / Kinf / Pinf (they persist from solve to solve)
                 rho = P.arho[b];

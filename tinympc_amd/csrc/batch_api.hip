@@ -277,12 +277,11 @@ int tiny_batch_setup_hetero(TinyBatch** out, const double* Adyn, const double* B
     if (!has_regs(b) && !(b->tile && !b->no_jit)) { tiny_batch_destroy(b); *out = nullptr; return TINY_ERR_UNSUPPORTED; }
     const bool tile_layout = !has_regs(b);
     const int tab_cols = tile_layout ? 32 : 16, tab_lw = tile_layout ? 16 * std::max(1, b->tile->W) : 16;
-    static_assert(het_tab_doubles(16, 16) == (int)HET_TAB_DOUBLES && het_tab_doubles(32, 16) == TileTab<1>::BOUNDS && het_tab_doubles(32, 32) == TileTab<2>::BOUNDS, "per-instance table layouts");
     auto bail = [&](int code) { tiny_batch_destroy(b); *out = nullptr; return code; };
     const size_t xx = (size_t)nx * nx, xu = (size_t)nx * nu, uu = (size_t)nu * nu, B = batch;
     struct { double** p; size_t n; } bufs[] = {{&b->d_hA, B * xx}, {&b->d_hB, B * xu}, {&b->d_hf, B * nx}, {&b->d_hQw, B * nx},
         {&b->d_hRw, B * nu}, {&b->d_hrho, B}, {&b->d_hK, B * xu}, {&b->d_hP, B * xx}, {&b->d_hQuu, B * uu}, {&b->d_hAmBKt, B * xx},
-        {&b->d_hAPf, B * nx}, {&b->d_hBPf, B * nu}, {&b->d_het_tabs, B * (size_t)het_tab_doubles(tab_cols, tab_lw)}};
+        {&b->d_hAPf, B * nx}, {&b->d_hBPf, B * nu}, {&b->d_het_tabs, B * (size_t)LaneTab{tab_cols, tab_lw}.het_doubles()}};
     for (auto& u : bufs)
         if (hipMalloc(u.p, u.n * sizeof(double)) != hipSuccess) return bail(TINY_ERR_HIP);
     if (hipMalloc(&b->d_hiters, B * sizeof(int)) != hipSuccess) return bail(TINY_ERR_HIP);

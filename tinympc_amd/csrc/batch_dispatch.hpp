@@ -25,7 +25,6 @@ bool linear_active(const TinyBatch* b);
 int lin_variant(const TinyBatch* b);
 bool use_tile(const TinyBatch* b);
 bool use_general(const TinyBatch* b);
-bool box_is_uniform(const TinyBatch* b);     // the box is the same at every knot (from the host copies of the bounds)
 // ---- buffers and state the API calls create on demand
 int ensure_kpi(TinyBatch* b, double** p);
 int ensure_repack_buffers(TinyBatch* b);
@@ -33,10 +32,12 @@ int ensure_regroup_buffers(TinyBatch* b, bool second_stream);
 int ensure_adaptive(TinyBatch* b, bool need_tables = true);
 int adaptive_fresh_state(TinyBatch* b);
 // ---- lane tables (batch_tables.hip)
+bool box_is_uniform(const TinyBatch* b);     // the box is the same at every knot: the one place that decides it
 int lin_kmax(const TinyBatch* b);       // half-spaces per knot and family the LIN variants are built for (4, 8, 16, 32; 0: coverage kernel)
 void build_tables(TinyBatch* b);
 void build_tile_tables(TinyBatch* b);
 void build_general_tables(TinyBatch* b);
+std::vector<double> build_adaptive_table(const TinyBatch* b);   // the shared family's ATAB_* tables from dKinf ... dC2 (no HIP call)
 int upload_tables(TinyBatch* b);
 int upload_growing(TinyBatch* b, double** dev, size_t* capacity, const std::vector<double>& host);   // host table -> device buffer that grows
 // ---- helper kernels, cost model (batch_helpers.hip)

@@ -4,6 +4,7 @@
 // batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.
 #include "batch_impl.hpp"
 #include "batch_dispatch.hpp"
+#include "lane_tables.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -121,10 +122,8 @@ static __global__ __launch_bounds__(256) void expand_atabs_kernel(double* __rest
     const int e = threadIdx.x, k = e / 16, j = e % 16;
     for (int b = blockIdx.x; b < batch; b += gridDim.x) {
         double* t = atabs + (size_t)b * ATAB_DOUBLES;
-        double at = 0.0;
-        if (k < nx && j < nx) at = A[(size_t)b * nx * nx + k + nx * j];
-        else if (k < nx && j < nx + nu) at = B[(size_t)b * nx * nu + k + nx * (j - nx)];
-        t[ATAB_AT + e] = at;
+        const struct { ColMajor A, B; } view = {{A + (size_t)b * nx * nx, nx}, {B + (size_t)b * nx * nu, nx}};
+        t[ATAB_AT + e] = atab_at(view, nx, nu, j, k);
         for (int o = ATAB_DK; o < ATAB_DOUBLES; o += 256) t[o + e] = atab[o + e];
     }
 }
@@ -187,21 +186,7 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
     if (b->atab_dirty && need_tables) {
         if ((int)b->dKinf.size() != nu * nx || (int)b->dPinf.size() != nx * nx)
             return fail(b, TINY_ERR_DIM, "adaptive rho is on but the sensitivity tables are not set (tiny_batch_set_sensitivity / tiny_batch_compute_sensitivity)");
-        std::vector<double> t(ATAB_DOUBLES, 0.0);
-        auto at = [&](int base, int k, int j) -> double& { return t[(size_t)base + k * 16 + j]; };
-        for (int j = 0; j < nx; ++j) {                       // state lanes
-            for (int k = 0; k < nx; ++k) at(ATAB_AT, k, j) = b->A(k, j);                        // (A' g)_j = sum_k A[k][j] g_k
-            for (int k = 0; k < nu; ++k) at(ATAB_DK, k, j) = b->dKinf[k + (size_t)nu * j];      // dK[k][j]
-            for (int k = 0; k < nx; ++k) at(ATAB_DP, k, j) = b->dPinf[k + (size_t)nx * j];      // dP[k][j]
-            for (int k = 0; k < nx; ++k) at(ATAB_DC2, k, j) = b->dC2.empty() ? 0.0 : b->dC2[k + (size_t)nx * j];
-        }
-        for (int r = 0; r < nu; ++r) {                       // input lanes
-            const int j = nx + r;
-            for (int k = 0; k < nx; ++k) at(ATAB_AT, k, j) = b->B(k, r);                        // (B' g)_r = sum_k B[k][r] g_k
-            for (int k = 0; k < nx; ++k) at(ATAB_DK, k, j) = b->dKinf[r + (size_t)nu * k];      // dK[r][k]
-        }
-        for (int j = 0; j < nu; ++j)                          // C1 is nu x nu: its column j is kept by lane j
-            for (int k = 0; k < nu; ++k) at(ATAB_DC1, k, j) = b->dC1.empty() ? 0.0 : b->dC1[k + (size_t)nu * j];
+        const std::vector<double> t = build_adaptive_table(b);
         HIP_TRY(b, hipMemcpyAsync(b->d_atab, t.data(), t.size() * sizeof(double), hipMemcpyHostToDevice, b->stream));
         if (b->hetero) {
             hipLaunchKernelGGL(expand_atabs_kernel, dim3((unsigned)std::min<size_t>(B, 2048)), dim3(256), 0, b->stream, b->d_atabs, b->d_atab, b->d_hA, b->d_hB, nx, nu, b->batch);

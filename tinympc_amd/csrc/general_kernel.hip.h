@@ -18,6 +18,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "admm_kernel.hip.h"
+
 namespace tinympc_amd {
 
 struct GeneralArgs {
@@ -40,8 +42,8 @@ struct GeneralArgs {
     int o_mb, o_mf1, o_mf2, o_pt, o_cb, o_cf, o_qr, o_lo, o_hi, o_sc, o_ic, o_ax, o_bx, o_au, o_bu, o_tax, o_tbx,
         o_tau, o_tbu;
     // per-instance problem data (round 6): the tables tiny_batch_setup_hetero built for a register kernel -- [batch][het_stride]
-    // doubles, matrices [column k][het_lw lanes] in blocks of het_cols columns (MB, MF1, MF2, PT), then the lane vectors (CB, CF, QR,
-    // ... RHO) -- read TRANSPOSED into this kernel's row-major LDS matrices at the top of every instance.  null: one family (gtab)
+    // doubles in the layout LaneTab{het_cols, het_lw} (admm_kernel.hip.h) -- read TRANSPOSED into this kernel's row-major LDS
+    // matrices at the top of every instance.  null: one family (gtab)
     const double* het_tabs;
     int het_cols, het_lw, het_stride;
 };
@@ -97,8 +99,6 @@ struct GkLds {
     const double *CB, *CF, *QR;      // the lane vectors of the instance at hand (the family's, or its own: gk_load_instance)
     double rho;
 };
-// index of a lane vector in the register kernels' tables (admm_kernel.hip.h VEC_*; riccati_kernel.hip.h VEC_RHO)
-enum : int { GK_VEC_CB = 0, GK_VEC_CF = 1, GK_VEC_QR = 2, GK_VEC_RHO = 8 };
 __device__ __forceinline__ GkLds gk_carve(const GeneralArgs& P, double* lds) {
     const int nx = P.nx, nu = P.nu, N = P.N, nz = nx + nu, ld = nz + 1;
     GkLds L;
@@ -121,19 +121,20 @@ __device__ __forceinline__ void gk_load_instance(const GeneralArgs& P, GkLds& L,
     const int nz = P.nx + P.nu, ld = nz + 1;
     if (P.het_tabs) {
         const double* ht = P.het_tabs + (size_t)b * P.het_stride;
-        const int blk = P.het_cols * P.het_lw, lw = P.het_lw;
+        const LaneTab T{P.het_cols, P.het_lw};
+        const int lw = T.lw;
         __syncthreads();                                     // (the instance before is done with the matrices)
         for (int e = lane; e < nz * ld; e += 64) {
             const int j = e / ld, k = e % ld;
             const bool in = k < nz;
-            L.sMB[e] = in ? ht[k * lw + j] : 0.0;
-            L.sMF1[e] = in ? ht[blk + k * lw + j] : 0.0;
-            L.sMF2[e] = in ? ht[2 * blk + k * lw + j] : 0.0;
-            L.sPT[e] = in ? ht[3 * blk + k * lw + j] : 0.0;
+            L.sMB[e] = in ? ht[T.MB() + k * lw + j] : 0.0;
+            L.sMF1[e] = in ? ht[T.MF1() + k * lw + j] : 0.0;
+            L.sMF2[e] = in ? ht[T.MF2() + k * lw + j] : 0.0;
+            L.sPT[e] = in ? ht[T.PT() + k * lw + j] : 0.0;
         }
-        const double* vec = ht + 4 * blk;
-        L.CB = vec + GK_VEC_CB * lw; L.CF = vec + GK_VEC_CF * lw; L.QR = vec + GK_VEC_QR * lw;
-        L.rho = vec[GK_VEC_RHO * lw];
+        const double* vec = ht + T.VEC();
+        L.CB = vec + VEC_CB * lw; L.CF = vec + VEC_CF * lw; L.QR = vec + VEC_QR * lw;
+        L.rho = vec[VEC_RHO * lw];
         __syncthreads();
     } else if (first) {
         for (int e = lane; e < nz * ld; e += 64) {

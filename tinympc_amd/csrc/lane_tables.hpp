@@ -1,0 +1,81 @@
+// lane_tables.hpp -- WHAT goes where in a lane table: the one statement of which entry of the problem and its cache lane j keeps for
+// column k (the layout -- where that lands in memory -- is LaneTab, admm_kernel.hip.h).  Function templates over a "view": a struct
+// whose members are called as A(j,k), Kinf(m,j), Qw(j) ... and return the entry of that matrix / vector.  The host builders
+// (batch_tables.hip) view Mat / Cache, the Riccati and sensitivity epilogues view the column-major LDS and global arrays they hold,
+// so all of them write the same tables by construction.  The products Quu_inv B' (QBt) and Quu_inv BPf (QBPf) are inputs of the
+// mapping: each side computes them with its own matrix product.
+// Included by batch_tables.hip, batch_helpers.hip, riccati_kernel.hip.h and sensitivity_kernel.hip.h -- never by the two headers that
+// are instantiated at run time from their source text (admm_kernel.hip.h, tile_kernel.hip.h).
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace tinympc_amd {
+
+// entry (i, j) of a column-major array with leading dimension ld; a vector: ld = 0, entry (i)
+struct ColMajor {
+    const double* p;
+    int ld;
+    __host__ __device__ double operator()(int i, int j = 0) const { return p[i + ld * j]; }
+};
+
+struct LaneMatrices { double mb, mf1, mf2, pt; };     // TAB_MB / MF1 / MF2 / PT at (column k, lane j); 0.0 where the lane keeps nothing
+struct LaneVectors { double cb, cf, qr; };            // VEC_CB / CF / QR of lane j
+struct AtabEntries { double at, dk, dp, dc1, dc2; };  // ATAB_AT / DK / DP / DC1 / DC2 at (column k, lane j)
+
+// view: A, B, AmBKt, Pinf, Kinf, Quu_inv, QBt
+template <class V>
+__host__ __device__ inline LaneMatrices lane_matrices(const V& v, int nx, int nu, int j, int k) {
+    LaneMatrices m = {0.0, 0.0, 0.0, 0.0};
+    if (j < nx) {                                      // state lanes
+        if (k < nx) {
+            m.mb = v.AmBKt(j, k);                      // p_i += AmBKt p_{i+1}     (admm.cpp:18)
+            m.mf1 = v.A(j, k);                         // x_{i+1} = A x_i ...      (admm.cpp:30)
+            m.pt = v.Pinf(k, j);                       // (Xref' Pinf)[j]          (admm.cpp:292)
+        } else if (k < nx + nu) {
+            m.mb = -v.Kinf(k - nx, j);                 // - Kinf' r_i
+            m.mf2 = v.B(j, k - nx);                    // + B u_i
+        }
+    } else if (j < nx + nu) {                          // input lanes: d_i = Quu_inv (B' p_{i+1} + r_i + BPf)   (admm.cpp:17)
+        const int a = j - nx;
+        if (k < nx) {
+            m.mb = v.QBt(a, k);
+            m.mf1 = -v.Kinf(a, k);                     // u_i = -Kinf x_i - d_i     (admm.cpp:29)
+        } else if (k < nx + nu) {
+            m.mb = v.Quu_inv(a, k - nx);
+        }
+    }
+    return m;
+}
+
+// view: APf, f, Qw (state lanes), QBPf, Rw (input lanes)
+template <class V>
+__host__ __device__ inline LaneVectors lane_vectors(const V& v, int nx, int nu, int j) {
+    LaneVectors r = {0.0, 0.0, 0.0};
+    if (j < nx) { r.cb = v.APf(j); r.cf = v.f(j); r.qr = v.Qw(j); }
+    else if (j < nx + nu) { r.cb = v.QBPf(j - nx); r.qr = v.Rw(j - nx); }
+    return r;
+}
+
+// ATAB_AT alone (view: A, B): state lanes A[k][j] -- (A' g)_j = sum_k A[k][j] g_k --, input lanes B[k][j-nx]
+template <class V>
+__host__ __device__ inline double atab_at(const V& v, int nx, int nu, int j, int k) {
+    if (k < nx && j < nx) return v.A(k, j);
+    if (k < nx && j < nx + nu) return v.B(k, j - nx);
+    return 0.0;
+}
+
+// view: A, B, dK (nu x nx), dP (nx x nx), dC1 (nu x nu), dC2 (nx x nx)
+template <class V>
+__host__ __device__ inline AtabEntries atab_entries(const V& v, int nx, int nu, int j, int k) {
+    AtabEntries e = {atab_at(v, nx, nu, j, k), 0.0, 0.0, 0.0, 0.0};
+    if (j < nx) {
+        if (k < nx) { e.dp = v.dP(k, j); e.dc2 = v.dC2(k, j); }
+        if (k < nu) e.dk = v.dK(k, j);                 // (their -Kinf' entries)
+    } else if (j < nx + nu) {
+        if (k < nx) e.dk = v.dK(j - nx, k);
+    }
+    if (j < nu && k < nu) e.dc1 = v.dC1(k, j);         // C1 is nu x nu: its column j is kept by lane j
+    return e;
+}
+
+}  // namespace tinympc_amd

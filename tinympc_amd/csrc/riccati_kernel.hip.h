@@ -7,12 +7,13 @@
 //                  BEFORE Ptp1 = Pinf, left-to-right products).  Arithmetic is not FMA-contracted and every
 //                  dot product runs in the same order as the host code (cache.hpp): identical problem data give
 //                  the same Riccati step count and caches equal to ~1e-13 on both paths (tests/test_gpu_hetero.py).
-//                  Its epilogue turns the cache into the per-instance lane tables admm_solve_kernel reads (same
-//                  layout and the same pre-multiplied Quu_inv B', Quu_inv BPf as batch_tables.hip:build_tables).
+//                  Its epilogue turns the cache into the per-instance lane tables the solve kernels read: the layout (LaneTab)
+//                  and the entries (lane_tables.hpp) are the ones batch_tables.hip builds the shared tables from.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "admm_kernel.hip.h"
+#include "lane_tables.hpp"
 
 namespace tinympc_amd {
 
@@ -20,17 +21,11 @@ struct RiccatiArgs {
     const double *A, *B, *f, *Qw, *Rw, *rho;        // [batch][nx*nx], [batch][nx*nu], [batch][nx], [batch][nx], [batch][nu], [batch]
     double *Kinf, *Pinf, *Quu_inv, *AmBKt, *APf, *BPf;
     int* iters;                                      // Riccati steps taken (1000 = not converged)
-    double* tabs;                                    // [batch][tab_doubles] lane tables
+    double* tabs;                                    // [batch][het_doubles()] lane tables
     int nx, nu, batch;
-    // layout of the lane tables: matrices [column k (0 .. tab_cols-1)][tab_lw lanes] at 0 (MB), cols*lw (MF1), 2 cols*lw (MF2), 3 cols*lw
-    // (PT), the 16 lane vectors at 4 cols*lw.  One-row kernel (admm_kernel.hip.h TAB_*): cols = lw = 16; tile kernel
-    // (tile_kernel.hip.h TileTab<W>): cols = 32, lw = 16 W
+    // layout of the lane tables, LaneTab{tab_cols, tab_lw}: {16, 16} one-row kernel, {32, 16 W} tile kernel (per instance: het_doubles())
     int tab_cols, tab_lw;
 };
-constexpr int het_tab_doubles(int cols, int lw) { return 4 * cols * lw + 16 * lw; }
-
-// per-instance table = the matrix + vector part of the shared table (bounds / cones / masks stay shared)
-enum : int { HET_TAB_DOUBLES = TAB_BOUNDS, VEC_RHO = 8 };
 
 #ifdef TINYMPC_GENERAL_KERNEL_IMPL   // compiled into batch_dispatch.hip only
 
@@ -156,35 +151,27 @@ __global__ __launch_bounds__(64) void riccati_kernel(const RiccatiArgs P) {
         for (int e = lane; e < nu; e += 64) P.BPf[(size_t)b * nu + e] = T2[e];
         if (lane == 0) P.iters[b] = fail ? -1 : iters;
 
-        // ---- lane tables of this instance (layout of admm_kernel.hip.h / tile_kernel.hip.h; see batch_tables.hip:build_tables, build_tile_tables_w)
+        // ---- lane tables of this instance
         w_mm(nu, nu, nx, Gi, Bt, T1, lane);                                    // Quu_inv B'
         w_mm(nu, nu, 1, Gi, T2, G, lane);                                      // Quu_inv BPf  (BPf is in T2)
-        const int cols = P.tab_cols, lw = P.tab_lw, tdoubles = het_tab_doubles(cols, lw);
-        const int o_mb = 0, o_mf1 = cols * lw, o_mf2 = 2 * cols * lw, o_pt = 3 * cols * lw, o_vec = 4 * cols * lw;
-        double* tab = P.tabs + (size_t)b * tdoubles;
-        for (int e = lane; e < tdoubles; e += 64) tab[e] = 0.0;
+        const LaneTab T{P.tab_cols, P.tab_lw};
+        const int lw = T.lw;
+        double* tab = P.tabs + (size_t)b * T.het_doubles();
+        for (int e = lane; e < T.het_doubles(); e += 64) tab[e] = 0.0;
         __syncthreads();
-        for (int e = lane; e < cols * lw; e += 64) {
-            const int k = e / lw, j = e % lw;              // column k, lane j
-            double mb = 0.0, mf1 = 0.0, mf2 = 0.0, pt = 0.0;
-            if (j < nx) {
-                if (k < nx) { mb = T3[j + nx * k]; mf1 = A[j + nx * k]; pt = Pn[k + nx * j]; }
-                else if (k < nx + nu) { mb = -K[(k - nx) + nu * j]; mf2 = B[j + nx * (k - nx)]; }
-            } else if (j < nx + nu) {
-                const int a = j - nx;
-                if (k < nx) { mb = T1[a + nu * k]; mf1 = -K[a + nu * k]; }
-                else if (k < nx + nu) mb = Gi[a + nu * (k - nx)];
-            }
-            tab[o_mb + e] = mb; tab[o_mf1 + e] = mf1; tab[o_mf2 + e] = mf2; tab[o_pt + e] = pt;
+        // APf was overwritten in T1 by Quu_inv B': read from the output array written above
+        const struct {
+            ColMajor A, B, AmBKt, Pinf, Kinf, Quu_inv, QBt, APf, QBPf, f, Qw, Rw;
+        } view = {{A, nx}, {B, nx}, {T3, nx}, {Pn, nx}, {K, nu}, {Gi, nu}, {T1, nu}, {P.APf + (size_t)b * nx, 0}, {G, 0}, {fv, 0},
+                  {P.Qw + (size_t)b * nx, 0}, {P.Rw + (size_t)b * nu, 0}};
+        for (int e = lane; e < T.cols * lw; e += 64) {
+            const LaneMatrices m = lane_matrices(view, nx, nu, e % lw, e / lw);      // lane j = e % lw, column k = e / lw
+            tab[T.MB() + e] = m.mb; tab[T.MF1() + e] = m.mf1; tab[T.MF2() + e] = m.mf2; tab[T.PT() + e] = m.pt;
         }
         if (lane < lw) {
-            const int j = lane;
-            // APf was overwritten in T1 by Quu_inv B': re-read it from the output array written above
-            double cb = 0.0, cf = 0.0, qr = 0.0;
-            if (j < nx) { cb = P.APf[(size_t)b * nx + j]; cf = fv[j]; qr = P.Qw[(size_t)b * nx + j]; }
-            else if (j < nx + nu) { cb = G[j - nx]; qr = P.Rw[(size_t)b * nu + (j - nx)]; }
-            tab[o_vec + VEC_CB * lw + j] = cb; tab[o_vec + VEC_CF * lw + j] = cf;
-            tab[o_vec + VEC_QR * lw + j] = qr; tab[o_vec + VEC_RHO * lw + j] = rho;
+            const LaneVectors v = lane_vectors(view, nx, nu, lane);
+            double* vec = tab + T.VEC() + lane;
+            vec[VEC_CB * lw] = v.cb; vec[VEC_CF * lw] = v.cf; vec[VEC_QR * lw] = v.qr; vec[VEC_RHO * lw] = rho;
         }
         __syncthreads();
     }

@@ -14,14 +14,15 @@
 //                  equation is solved by squaring -- X <- X + M' X M, M <- M M, starting from X = 2 (I + K' K), M = Acl: after s
 //                  steps X holds 2^s terms of the series -- until the increment falls below 1e-15 of X (max norms, reduced over the
 //                  wave: every lane takes the same branch) or 64 squarings have run.  No FMA contraction; there is no host path.
-//                  Its epilogue writes the instance's ATAB_* lane tables (admm_kernel.hip.h) in the layout ensure_adaptive builds on
-//                  the host for a shared family, ATAB_AT from the instance's own A and B (shapes of the one-row kernel only).
+//                  Its epilogue writes the instance's ATAB_* lane tables (admm_kernel.hip.h) through the mapping the host uses for a
+//                  shared family (lane_tables.hpp), ATAB_AT from the instance's own A and B (shapes of the one-row kernel only).
 // LDS: five nx x nx matrices (Acl, M, X and two temporaries), five nx x nu ones (B, K, B' dP, its product, dK) and three nu x nu
 //                  ones.  At nx = 31, nu = 1: 5 * 7688 + 5 * 248 + 24 = 39 704 bytes, four blocks per CU of 160 KB; at the
 //                  quadrotor's (12,4): 8 064 bytes, LDS is not the limit.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "lane_tables.hpp"
 #include "riccati_kernel.hip.h"
 
 namespace tinympc_amd {
@@ -115,17 +116,16 @@ __global__ __launch_bounds__(64) void sensitivity_kernel(const SensitivityArgs P
         if (lane == 0) P.steps[b] = steps;
         if (P.atabs) {                                                         // (the host passes it for nx + nu <= 16 only)
             double* tab = P.atabs + (size_t)b * ATAB_DOUBLES;
+            const struct {                                                     // dC1 = -G, dC2 = -(B dK)': B dK is in T
+                ColMajor A, B, dK, dP;
+                const double *G, *T;
+                int nx, nu;
+                __device__ double dC1(int k, int j) const { return -G[k + nu * j]; }
+                __device__ double dC2(int k, int j) const { return -T[j + nx * k]; }
+            } view = {{Ag, nx}, {B, nx}, {dK, nu}, {X, nx}, G, T, nx, nu};
             for (int e = lane; e < 256; e += 64) {
-                const int k = e / 16, j = e % 16;                              // column k, lane j
-                double at = 0.0, dk = 0.0, dp = 0.0, dc1 = 0.0, dc2 = 0.0;
-                if (j < nx) {
-                    if (k < nx) { at = Ag[k + nx * j]; dp = X[k + nx * j]; dc2 = -T[j + nx * k]; }
-                    if (k < nu) dk = dK[k + nu * j];
-                } else if (j < nx + nu) {
-                    if (k < nx) { at = B[k + nx * (j - nx)]; dk = dK[(j - nx) + nu * k]; }
-                }
-                if (j < nu && k < nu) dc1 = -G[k + nu * j];
-                tab[ATAB_AT + e] = at; tab[ATAB_DK + e] = dk; tab[ATAB_DP + e] = dp; tab[ATAB_DC1 + e] = dc1; tab[ATAB_DC2 + e] = dc2;
+                const AtabEntries a = atab_entries(view, nx, nu, e % 16, e / 16);   // lane j = e % 16, column k = e / 16
+                tab[ATAB_AT + e] = a.at; tab[ATAB_DK + e] = a.dk; tab[ATAB_DP + e] = a.dp; tab[ATAB_DC1 + e] = a.dc1; tab[ATAB_DC2 + e] = a.dc2;
             }
         }
         __syncthreads();

@@ -22,11 +22,11 @@ namespace tinympc_amd {
 template <int W>
 struct TileTab {
     static constexpr int LW = 16 * W;
-    static constexpr int MB = 0, MF1 = 32 * LW, MF2 = 64 * LW, PT = 96 * LW, VEC = 128 * LW, BOUNDS = 128 * LW + 16 * LW;
-    // half-space tables of the LIN variants behind the bounds: static [3][kmax][LW], then per slot [N][3][kmax][LW]
-    static constexpr int lin_offset(int N) { return BOUNDS + 2 * N * LW; }
-    static constexpr int tlin_offset(int N, int kmax) { return lin_offset(N) + 3 * kmax * LW; }
-    static constexpr int doubles(int N, int kmax = LIN_KMAX) { return tlin_offset(N, kmax) + 3 * N * kmax * LW; }
+    static constexpr LaneTab tab() { return {32, LW}; }
+    static constexpr int MB = tab().MB(), MF1 = tab().MF1(), MF2 = tab().MF2(), PT = tab().PT(), VEC = tab().VEC(), BOUNDS = tab().BOUNDS();
+    static constexpr int lin_offset(int N) { return tab().lin_offset(N); }
+    static constexpr int tlin_offset(int N, int kmax) { return tab().tlin_offset(N, kmax); }
+    static constexpr int doubles(int N, int kmax = LIN_KMAX) { return tab().doubles(N, kmax); }
 };
 
 // (the half-row FMA chains -- THL / THH, ring1_half -- live in admm_kernel.hip.h: the one-row kernel's HALF variant shares them)
@@ -447,7 +447,7 @@ void admm_tile_kernel(const SolveArgs P) {
                 cb = het[T::VEC + VEC_CB * LW + jj];
                 cf = het[T::VEC + VEC_CF * LW + jj];
                 qr = het[T::VEC + VEC_QR * LW + jj];
-                rho = het[T::VEC + 8 * LW + jj];                   // VEC_RHO (riccati_kernel.hip.h)
+                rho = het[T::VEC + VEC_RHO * LW + jj];
             }
             // ---- load the instance record
             [[maybe_unused]] const bool cold = EXTF && P.cold;     // the warm-start records are known to be zero: not read
