@@ -20,13 +20,16 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "g
 
 
 def main():
-    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges   (--only: just those single-solve suites of section 2;
-    --soc-edges: just section 6, tests/golden/project_soc_edges.npz)"""
+    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges | --halfspace-edges   (--only: just those single-solve suites
+    of section 2; --soc-edges: just section 6, tests/golden/project_soc_edges.npz; --halfspace-edges: just section 7,
+    tests/golden/halfspace_edges.npz)"""
     if build_ref() is None:
         sys.exit("oracle/_ref/libtinympc_ref.so missing and /root/reference absent")
     os.makedirs(OUT, exist_ok=True)
     if "--soc-edges" in sys.argv:
         return project_soc_edges()
+    if "--halfspace-edges" in sys.argv:
+        return halfspace_edges()
     only = None
     if "--only" in sys.argv:
         only = set(sys.argv[sys.argv.index("--only") + 1].split(","))
@@ -170,6 +173,7 @@ def episode_and_phase_kats():
     s.close()
     np.savez_compressed(os.path.join(OUT, "phase_kat.npz"), **ph)
     project_soc_edges()
+    halfspace_edges()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes:", tot)
 
@@ -187,6 +191,34 @@ def project_soc_edges():
     s.close()
     np.savez_compressed(os.path.join(OUT, "project_soc_edges.npz"), s=S, mu=mus, out=P, label=labels, names=np.array(names))
     print("project_soc_edges: items", len(S), "bytes", os.path.getsize(os.path.join(OUT, "project_soc_edges.npz")))
+
+
+def halfspace_edges():
+    # 7. the half-space step of update_slack (admm.cpp:137-211) on the finite directed items of tests/halfspace_ref.py: x = u = 0, the
+    # items are the four duals, the reference's own update_slack gives vlnew, zlnew, vlnew_tv, zlnew_tv.  Inputs (the duals), their class
+    # labels and the outputs are stored: the generators solve small linear systems, whose last bits depend on the machine's BLAS, so
+    # tests/test_halfspace_ref_cpu.py reads the inputs back (and checks every one against its class) instead of drawing them again
+    sys.path.insert(0, os.path.join(OUT, ".."))
+    import halfspace_ref as hr
+    flat, count = {}, 0
+    for n_, (name, nx, nu, N, sets, duals, labels) in enumerate(hr.fixture_items()):
+        s = sc.make_solver(RefSolver, hr.family(nx, nu, N), hr.config(sets, nx, nu, N, 1))
+        out = {v: np.zeros_like(duals[g]) for v, g, _, _ in hr.FAMILIES}
+        for b in range(duals["gl"].shape[0]):
+            for k in ("x", "u"):
+                s[k] = np.zeros(s[k].shape)
+            for _, g, _, _ in hr.FAMILIES:
+                s[g] = duals[g][b]
+            s.phase("update_slack")
+            for v in out:
+                out[v][b] = s[v]
+        s.close()
+        for v, g, _, _ in hr.FAMILIES:
+            flat["%d.%s" % (n_, v)], flat["%d.%s" % (n_, g)], flat["%d.%s.label" % (n_, g)] = out[v], duals[g], labels[g]
+            count += out[v].shape[0] * out[v].shape[2]
+    path = os.path.join(OUT, "halfspace_edges.npz")
+    np.savez_compressed(path, **flat)
+    print("halfspace_edges: columns", count, "bytes", os.path.getsize(path))
 
 
 if __name__ == "__main__":

@@ -678,7 +678,9 @@ constexpr int solve_kernel_lin_waves(int nx, int nu, int n, bool soc, int lin, i
 }
 // One lane projects whole (knot, family) columns of a half-space slack: column c of instance `inst`, rows [R0, R0 + NF) -- the cells
 // pv[(inst * n + c) * csl + R0 ...] hold x + gl; the family's half-spaces are applied one after the other, only when violated
-// (admm.cpp:148-173, 186-211; project_hyperplane :70-73; a'z as the reference forms it: products rounded, summed in row order), vlnew
+// (admm.cpp:148-173, 186-211; project_hyperplane :70-73; a'z as the ORACLE forms it: products rounded, summed in row order -- the
+// reference's Eigen reductions pair the terms differently once a row has more than 3 entries, at most 2.5e-16 relative on the rocket
+// problem's slacks, none on a 3-row family; tests/test_halfspace_ref_cpu.py bounds that difference by the summation bound), vlnew
 // goes back to pv and gl = (x + gl) - vlnew (:239-254) to pg.  Lane t of the LPI lanes of an instance takes columns S0 + t, S0 + t +
 // LPI, ...; tab: [3][KMAX][LW] coefficient | offset | squared norm, + c * tab_stride for the time-varying family.
 template <int NF, int KMAX_, int LW_, int LPI_>
@@ -1345,7 +1347,11 @@ void admm_solve_kernel(const SolveArgs P) {
                                     ring1<0, NX>(cs, prod, ones);
                                     ring1<NX, NU>(ci, prod, ones);
                                     const double cv = is_state ? cs : ci;
-                                    if (cv > bk) z = z - ((cv - bk) / nn) * a;
+                                    if (cv > bk) {
+#pragma clang fp contract(off)
+                                        const double pr = ((cv - bk) / nn) * a;         // the product rounded, as in project_halfspace_columns
+                                        z = z - pr;
+                                    }
                                 }
                                 return z;
                             };

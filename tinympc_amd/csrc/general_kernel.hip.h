@@ -81,15 +81,18 @@ __device__ __forceinline__ void soc3_inplace(double* s, double mu_d) {
     } else { s[0] = 0.0; s[1] = 0.0; s[2] = 0.0; }
 }
 
-// one column z (n entries, stride 1) against the half-space a'z <= b (admm.cpp:150-157, project_hyperplane :70-73)
+// one column z (n entries, stride 1) against the half-space a'z <= b (admm.cpp:150-157, project_hyperplane :70-73): products rounded,
+// sums in row order, as the oracle forms them.  (__dmul_rn / __dadd_rn are plain * and + in HIP's headers and contract into FMAs once
+// inlined -- only the pragma keeps a product rounded.)
 __device__ __forceinline__ void halfspace_inplace(double* z, int n, const double* a, double b) {
+#pragma clang fp contract(off)
     double cv = 0.0;
-    for (int c = 0; c < n; ++c) cv = __dadd_rn(cv, __dmul_rn(a[c], z[c]));
+    for (int c = 0; c < n; ++c) { const double pr = a[c] * z[c]; cv = cv + pr; }
     if (cv > b) {
         double nn = 0.0;
-        for (int c = 0; c < n; ++c) nn = __dadd_rn(nn, __dmul_rn(a[c], a[c]));
+        for (int c = 0; c < n; ++c) { const double pr = a[c] * a[c]; nn = nn + pr; }
         const double dist = (cv - b) / nn;
-        for (int c = 0; c < n; ++c) z[c] = z[c] - dist * a[c];
+        for (int c = 0; c < n; ++c) { const double pr = dist * a[c]; z[c] = z[c] - pr; }
     }
 }
 
@@ -518,11 +521,12 @@ __global__ void project_soc_kernel(double* s, const int n, const float mu) {
     } else { for (int c = 0; c < n; ++c) s[c] = 0.0; }
 }
 __global__ void project_hyperplane_kernel(double* z, const double* a, const int n, const double b) {
+#pragma clang fp contract(off)
     if (threadIdx.x != 0) return;
     double az = 0.0, aa = 0.0;
-    for (int c = 0; c < n; ++c) { az = __dadd_rn(az, __dmul_rn(a[c], z[c])); aa = __dadd_rn(aa, __dmul_rn(a[c], a[c])); }
+    for (int c = 0; c < n; ++c) { const double p = a[c] * z[c], q = a[c] * a[c]; az = az + p; aa = aa + q; }
     const double dist = (az - b) / aa;                                                  // :71
-    for (int c = 0; c < n; ++c) z[c] = z[c] - dist * a[c];                              // :72
+    for (int c = 0; c < n; ++c) { const double pr = dist * a[c]; z[c] = z[c] - pr; }    // :72
 }
 
 #endif  // TINYMPC_GENERAL_KERNEL_IMPL

@@ -248,8 +248,10 @@ void admm_tile_kernel(const SolveArgs P) {
     // LIN: the half-space slacks live in LDS as well -- per set (static | time-varying) two planes of one cell per row and global
     // slot: V (x + gl between the forward sweep and the projection step, then vlnew) and G (gl); the backward sweep adds
     // -rho (V - G) (admm.cpp:272 ...).  The projections are TRANSPOSED like the cone step: one lane takes a whole (knot, family)
-    // column, applies the family's half-spaces to it one after the other in its registers (a'z as the reference forms it: products
-    // rounded, summed in row order; project_hyperplane only when violated, admm.cpp:148-173, 186-211) and writes vlnew and
+    // column, applies the family's half-spaces to it one after the other in its registers (a'z as the ORACLE forms it: products
+    // rounded, summed in row order -- the reference's Eigen reductions pair the terms differently beyond 3 rows, at most 2.5e-16
+    // relative on the rocket problem's slacks, bounded in tests/test_halfspace_ref_cpu.py; project_hyperplane only when violated,
+    // admm.cpp:148-173, 186-211) and writes vlnew and
     // gl = (x + gl) - vlnew back -- N + N - 1 columns per instance and set instead of two DPP chains per knot, half-space and slot.
     constexpr int CSL = LIN ? ((NZ + 1) | 1) : 1;                        // cells of a slot (+ the pad of the lanes beyond nx+nu), odd
     __shared__ double sLV[LS ? IPW * N * CSL : 1], sLG[LS ? IPW * N * CSL : 1];
