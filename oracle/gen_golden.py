@@ -20,9 +20,9 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "g
 
 
 def main():
-    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges | --halfspace-edges   (--only: just those single-solve suites
-    of section 2; --soc-edges: just section 6, tests/golden/project_soc_edges.npz; --halfspace-edges: just section 7,
-    tests/golden/halfspace_edges.npz)"""
+    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges | --halfspace-edges | --termination-edges   (--only: just those
+    single-solve suites of section 2; --soc-edges: just section 6, tests/golden/project_soc_edges.npz; --halfspace-edges: just section 7,
+    tests/golden/halfspace_edges.npz; --termination-edges: just section 8, tests/golden/termination_edges.npz)"""
     if build_ref() is None:
         sys.exit("oracle/_ref/libtinympc_ref.so missing and /root/reference absent")
     os.makedirs(OUT, exist_ok=True)
@@ -30,6 +30,8 @@ def main():
         return project_soc_edges()
     if "--halfspace-edges" in sys.argv:
         return halfspace_edges()
+    if "--termination-edges" in sys.argv:
+        return termination_edges()
     only = None
     if "--only" in sys.argv:
         only = set(sys.argv[sys.argv.index("--only") + 1].split(","))
@@ -174,6 +176,7 @@ def episode_and_phase_kats():
     np.savez_compressed(os.path.join(OUT, "phase_kat.npz"), **ph)
     project_soc_edges()
     halfspace_edges()
+    termination_edges()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes:", tot)
 
@@ -219,6 +222,41 @@ def halfspace_edges():
     path = os.path.join(OUT, "halfspace_edges.npz")
     np.savez_compressed(path, **flat)
     print("halfspace_edges: columns", count, "bytes", os.path.getsize(path))
+
+
+def termination_edges():
+    # 8. the termination test (admm.cpp:310-328) on the batches of tests/termination_ref.py for (4,2,10): every (row, knot, residual kind)
+    # as the only entry that keeps a solve open, and a residual EQUAL to its tolerance | one double below it.  Stored: the inputs that
+    # are not zero (the warm v | z are the reference's own iteration-1 slacks) and the reference's scalar outputs at max_iter 1 and 40 --
+    # no trajectories.  tests/test_oracle_golden.py holds the oracle to them
+    sys.path.insert(0, os.path.join(OUT, ".."))
+    import termination_ref as tr
+    dims = (4, 2, 10)
+    flat = {"dims": np.array(dims)}
+
+    def record(tag, suite, table):
+        flat[tag + ".table"] = table
+        for k in ("x0", "g", "y", "v", "z"):
+            if np.any(suite["cases"][k]):
+                flat["%s.%s" % (tag, k)] = suite["cases"][k]
+
+    def outputs(tag, suite):
+        for max_iter in (1, 40):
+            out = sc.run_cases(RefSolver, tr.with_config(suite, max_iter=max_iter), fields=())
+            for k in tr.SCALARS:
+                flat["%s.out%d.%s" % (tag, max_iter, k)] = out[k]
+    suite, table = tr.position_suite(*dims, cls=RefSolver)
+    record("pos", suite, table)
+    outputs("pos", suite)
+    for kind in (tr.PRI, tr.DUA):
+        for above in (False, True):
+            suite, table = tr.strict_suite(*dims, kind, above)
+            tag = "strict_%s" % tr.KIND[kind]
+            record(tag, suite, table)
+            outputs("%s.%s" % (tag, "above" if above else "equal"), suite)
+    path = os.path.join(OUT, "termination_edges.npz")
+    np.savez_compressed(path, **flat)
+    print("termination_edges: instances", len(flat["pos.table"]), "bytes", os.path.getsize(path))
 
 
 if __name__ == "__main__":

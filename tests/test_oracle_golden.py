@@ -17,7 +17,7 @@ from cpu_solvers import OracleSolver, RefSolver, have_ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SUITES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz"))
-                if os.path.basename(p)[:-4] not in ("cache_kat", "project_soc_kat", "project_soc_edges", "halfspace_edges", "phase_kat", "tracking_episode"))
+                if os.path.basename(p)[:-4] not in ("cache_kat", "project_soc_kat", "project_soc_edges", "halfspace_edges", "termination_edges", "phase_kat", "tracking_episode"))
 RTOL = 1e-9
 
 
@@ -107,6 +107,46 @@ def test_phase_known_answers():
         "primal_residual_state", "dual_residual_state", "primal_residual_input", "dual_residual_input")]
     np.testing.assert_allclose(t, ph["termination"], rtol=1e-12)
     s.close()
+
+
+def test_termination_edges_known_answers():
+    """tests/golden/termination_edges.npz (oracle/gen_golden.py section 8): the REAL reference on the (4,2,10) batches of
+    tests/termination_ref.py -- every (row, knot, residual kind) as the only entry that keeps a solve open, and a residual equal to its
+    tolerance | one double below it -- at max_iter 1 and 40.  The oracle reproduces iter / solved / status exactly and the four residuals
+    to 1e-12; the stored inputs are the builder's (the warm v | z: the reference's iteration-1 slacks against the oracle's)."""
+    import termination_ref as tr
+    z = np.load(os.path.join(GOLDEN, "termination_edges.npz"))
+    dims = tuple(int(v) for v in z["dims"])
+    built = {"pos": tr.position_suite(*dims)}
+    tags = [("pos", "pos")]
+    for kind in (tr.PRI, tr.DUA):
+        for above in (False, True):
+            tag = "strict_%s" % tr.KIND[kind]
+            built[tag + (".above" if above else ".equal")] = tr.strict_suite(*dims, kind, above)
+            tags.append((tag, tag + (".above" if above else ".equal")))
+    checked = 0
+    for tag, run in tags:
+        suite, table = built[run]
+        assert np.array_equal(table, z[tag + ".table"])
+        for k in ("x0", "g", "y", "v", "z"):
+            stored = z["%s.%s" % (tag, k)] if "%s.%s" % (tag, k) in z.files else np.zeros_like(suite["cases"][k])
+            assert np.allclose(stored, suite["cases"][k], rtol=0, atol=1e-12), (tag, k)
+            suite["cases"][k] = stored                                   # run what the reference ran
+        for max_iter in (1, 40):
+            out = sc.run_cases(OracleSolver, tr.with_config(suite, max_iter=max_iter), fields=())
+            for k in ("iter", "sol_solved", "status"):
+                assert np.array_equal(out[k].astype(int), z["%s.out%d.%s" % (run, max_iter, k)].astype(int)), (run, max_iter, k)
+            for k in tr.RESIDUALS:
+                ref = z["%s.out%d.%s" % (run, max_iter, k)]
+                assert np.all(np.abs(out[k] - ref) <= 1e-12 * np.maximum(1.0, np.abs(ref))), (run, max_iter, k)
+            checked += len(table)
+    off = z["pos.table"][:, 0] != tr.CTL
+    assert np.all(z["pos.out1.iter"] == 1) and np.array_equal(z["pos.out1.sol_solved"] == 1, ~off)
+    assert np.all(z["pos.out40.sol_solved"] == 1) and np.all(z["pos.out40.iter"][off] >= 2) and np.all(z["pos.out40.iter"][~off] == 1)
+    for kind in ("pri", "dua"):
+        o = z["strict_%s.table" % kind][:, 0] != tr.CTL
+        assert np.all(z["strict_%s.equal.out40.iter" % kind][o] == 2) and np.all(z["strict_%s.above.out40.iter" % kind][o] == 1)
+    assert checked == 2 * (145 + 2 * 5 + 2 * 73)
 
 
 def test_hover_episode_sequence():
