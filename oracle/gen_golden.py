@@ -20,9 +20,10 @@ OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "g
 
 
 def main():
-    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges | --halfspace-edges | --termination-edges   (--only: just those
-    single-solve suites of section 2; --soc-edges: just section 6, tests/golden/project_soc_edges.npz; --halfspace-edges: just section 7,
-    tests/golden/halfspace_edges.npz; --termination-edges: just section 8, tests/golden/termination_edges.npz)"""
+    """python oracle/gen_golden.py [--only name,name,...] | --soc-edges | --halfspace-edges | --termination-edges | --box-edges   (--only:
+    just those single-solve suites of section 2; --soc-edges: just section 6, tests/golden/project_soc_edges.npz; --halfspace-edges: just
+    section 7, tests/golden/halfspace_edges.npz; --termination-edges: just section 8, tests/golden/termination_edges.npz; --box-edges:
+    just section 9, tests/golden/box_edges.npz)"""
     if build_ref() is None:
         sys.exit("oracle/_ref/libtinympc_ref.so missing and /root/reference absent")
     os.makedirs(OUT, exist_ok=True)
@@ -32,6 +33,8 @@ def main():
         return halfspace_edges()
     if "--termination-edges" in sys.argv:
         return termination_edges()
+    if "--box-edges" in sys.argv:
+        return box_edges()
     only = None
     if "--only" in sys.argv:
         only = set(sys.argv[sys.argv.index("--only") + 1].split(","))
@@ -177,6 +180,7 @@ def episode_and_phase_kats():
     project_soc_edges()
     halfspace_edges()
     termination_edges()
+    box_edges()
     tot = sum(os.path.getsize(os.path.join(OUT, f)) for f in os.listdir(OUT))
     print("golden bytes:", tot)
 
@@ -257,6 +261,41 @@ def termination_edges():
     path = os.path.join(OUT, "termination_edges.npz")
     np.savez_compressed(path, **flat)
     print("termination_edges: instances", len(flat["pos.table"]), "bytes", os.path.getsize(path))
+
+
+def box_edges():
+    # 9. the box step of update_slack + update_dual (admm.cpp:85-98, 222-225) on the class rounds of tests/box_ref.py for one small
+    # shape: every (row, knot) under every kind of bound pair -- ordinary, equal, crossed, infinite, the default +-1e17, subnormal, a
+    # zero of either sign, NaN -- with t = x + g on, one ulp inside and outside, and far from each bound, t = NaN and +-inf included.
+    # The reference's own update_slack, then update_dual, on x, u, g, y set directly.  Stored: the bounds, the four inputs, the four
+    # outputs and the class labels of every round; tests/test_box_ref_cpu.py holds the numpy model and the oracle to them
+    sys.path.insert(0, os.path.join(OUT, ".."))
+    import box_ref as br
+    flat, count = {"dims": np.array(br.FIXTURE_DIMS)}, 0
+    for tag, suite, labels in br.fixture_rounds():
+        s = sc.make_solver(RefSolver, suite["problem"], suite["config"])
+        ins = dict(zip(("x", "u", "g", "y"), br.phase_inputs(suite)))
+        out = {k: np.zeros_like(ins[src]) for k, src in (("vnew", "g"), ("znew", "y"), ("g", "g"), ("y", "y"))}
+        for b in range(ins["g"].shape[0]):
+            for k, v in ins.items():
+                s[k] = v[b]
+            s.phase("update_slack")
+            out["vnew"][b], out["znew"][b] = s["vnew"], s["znew"]
+            s.phase("update_dual")
+            out["g"][b], out["y"][b] = s["g"], s["y"]
+        s.close()
+        for k in ("x_min", "x_max", "u_min", "u_max"):
+            flat["%s.%s" % (tag, k)] = suite["config"][k]
+        for k, v in ins.items():
+            flat["%s.in.%s" % (tag, k)] = v
+        for k, v in out.items():
+            flat["%s.out.%s" % (tag, k)] = v
+        for k, v in labels.items():
+            flat["%s.label.%s" % (tag, k)] = v
+        count += ins["g"].size + ins["y"].size
+    path = os.path.join(OUT, "box_edges.npz")
+    np.savez_compressed(path, **flat)
+    print("box_edges: entries", count, "bytes", os.path.getsize(path))
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ from cpu_solvers import OracleSolver, RefSolver, have_ref
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SUITES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "*.npz"))
-                if os.path.basename(p)[:-4] not in ("cache_kat", "project_soc_kat", "project_soc_edges", "halfspace_edges", "termination_edges", "phase_kat", "tracking_episode"))
+                if os.path.basename(p)[:-4] not in ("cache_kat", "project_soc_kat", "project_soc_edges", "halfspace_edges", "termination_edges", "box_edges", "phase_kat", "tracking_episode"))
 RTOL = 1e-9
 
 

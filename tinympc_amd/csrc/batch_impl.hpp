@@ -123,6 +123,7 @@ struct TinyBatch {
     int *d_repack_index = nullptr, *d_repack_count = nullptr;
     bool use_ub = true;                            // option "uniform_bounds": take the UB kernel variant when the box allows it
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
+    bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off
