@@ -866,14 +866,14 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "prefetch_static")) { if (value < -1 || value > 100) return fail(b, TINY_ERR_ARG, "prefetch_static: percent, 0 ... 100, or -1 (by rule: 75 warm, 50 cold)"); b->prefetch_static = (int)value; }
     else if (!strcmp(name, "prefetch_waves")) { if (value < 0) return fail(b, TINY_ERR_ARG, "prefetch_waves >= 0"); b->prefetch_waves = (int)value; }
     else if (!strcmp(name, "launch_order")) { if (value < 0 || value > 2) return fail(b, TINY_ERR_ARG, "launch_order: 0 (ascending), 1 (alternating), 2 (descending)"); b->launch_order = (int)value; }
-    else if (!strcmp(name, "step_regroup")) { if (value < -1) return fail(b, TINY_ERR_ARG, "step_regroup: K > 0 (stretches of K MPC steps), 0 (never) or -1 (automatic)"); b->step_regroup = (int)value; b->regroup_verdict = 0; b->regroup_since = 0; b->ls_pending = false; }
+    else if (!strcmp(name, "step_regroup")) { if (value < -1) return fail(b, TINY_ERR_ARG, "step_regroup: K > 0 (stretches of K MPC steps), 0 (never) or -1 (automatic)"); b->step_regroup = (int)value; b->learn.step_regroup_set(); b->ls_pending = false; }
     else if (!strcmp(name, "step_regroup_streams")) { if (value < 1 || value > 2) return fail(b, TINY_ERR_ARG, "step_regroup_streams: 1 or 2"); b->regroup_streams = (int)value; }
     else if (!strcmp(name, "auto_cold")) b->auto_cold = value != 0;       // 0: always read the warm-start records, also right after a reset
     else if (!strcmp(name, "uniform_bounds")) b->use_ub = value != 0;
     else if (!strcmp(name, "one_shot")) { if (value < 0 || value > 2) return fail(b, TINY_ERR_ARG, "one_shot: 0, 1 or 2"); b->one_shot = (int)value; }
-    else if (!strcmp(name, "repack_after")) { if (value < -1) return fail(b, TINY_ERR_ARG, "repack_after: K > 0, 0 (never) or -1 (automatic)"); b->repack_after = (int)value; b->auto_cap = 0; b->hist_copy.clear(); b->hist_pending = false; b->auto_verdict = 0; b->growth_verdict = 0; b->auto_plain_rate = b->auto_split_rate = 0.0; b->auto_probes = 0; if (value < 0 && b->plan_opt) { b->plan_tried = false; b->plan_shipped = false; } }    // (automatic again: the shipped plan is looked up afresh)
+    else if (!strcmp(name, "repack_after")) { if (value < -1) return fail(b, TINY_ERR_ARG, "repack_after: K > 0, 0 (never) or -1 (automatic)"); b->repack_after = (int)value; b->learn.repack_after_set(); b->hist_pending = false; if (value < 0 && b->plan_opt) { b->plan_tried = false; b->plan_shipped = false; } }    // (automatic again: the shipped plan is looked up afresh)
     else if (!strcmp(name, "repack_waves_per_cu")) b->repack_waves_per_cu = (int)std::max(1L, value);
-    else if (!strcmp(name, "repack_growth")) { b->repack_growth = (int)value; b->growth_verdict = 0; }
+    else if (!strcmp(name, "repack_growth")) { b->repack_growth = (int)value; b->learn.repack_growth_set(); }
     else if (!strcmp(name, "repack_sort")) { if (value < -1 || value > 1) return fail(b, TINY_ERR_ARG, "repack_sort: 1, 0 or -1 (automatic)"); b->repack_sort = (int)value; }
     else if (!strcmp(name, "repack_dynamic")) b->repack_dynamic = value != 0;   // follow-up stages: tiles off a counter (1) or a fixed grid stride (0)
     else if (!strcmp(name, "traj_step")) b->traj_step = value;
@@ -964,7 +964,9 @@ int tiny_jit_used(char* out, int out_len) {
 // best split / plain launch.  What launch_solve consults with the histogram of the previous solve.
 int tiny_predict_split(const unsigned* hist, int nx, int nu, int N, int max_iter, int check_termination, int num_cus, double* ratio) {
     if (!hist || nx <= 0 || nu <= 0 || N < 2 || max_iter <= 0) return 0;
-    return choose_split_for(nx, nu, N, false, max_iter, std::max(1, check_termination), 0, num_cus > 0 ? num_cus : 256, hist, ratio);
+    const SplitChoice c = choose_split_for(nx, nu, N, solve_kernel_waves_per_simd(nx + nu, N, false), max_iter, std::max(1, check_termination), 0, num_cus > 0 ? num_cus : 256, hist);
+    if (ratio) *ratio = c.ratio;
+    return c.k;
 }
 
 // The schedule "step_regroup" cuts a fused launch of `steps` MPC steps into (host arithmetic, no GPU): k > 0 = stretches of k steps,
@@ -991,20 +993,15 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "auto_split_k")) {
         if (b->hist_pending && hipEventSynchronize(b->hist_ev) == hipSuccess) {      // (a diagnostic may wait; a solve never does)
             b->hist_pending = false;
-            b->probe_was_tile = b->probe_was_growth = false;   // (the probe's clock reading is dropped with it: the next probe starts clean)
-            if (b->auto_verdict == 0) {                        // (a decided batch keeps its K AND the stage schedule the clock chose)
-                b->auto_cap = choose_split(b, b->h_hist, &b->auto_gain);
-                b->auto_cap_max_iter = b->set.max_iter;
-                b->hist_copy.assign(b->h_hist, b->h_hist + TinyBatch::HIST_BINS);
-            }
+            b->learn.histogram_read_back(b->h_hist, b->set.max_iter, split_model(b));
         }
-        return b->auto_cap;
+        return b->learn.auto_cap;
     }
-    if (!strcmp(name, "auto_split_growth_verdict")) return b->growth_verdict;
-    if (!strcmp(name, "auto_split_growth")) return b->auto_growth;               // the stage schedule that goes with auto_split_k: K, g K, g^2 K, ...
-    if (!strcmp(name, "auto_split_permille")) return (long)(b->auto_gain * 1000.0 + 0.5);
-    if (!strcmp(name, "auto_split_verdict")) return b->auto_verdict;
-    if (!strcmp(name, "tile_alt_verdict")) return b->tile_verdict;              // 1: the one-row shape runs on the tile kernel's dynamic form (the clock said so), -1: it does not
+    if (!strcmp(name, "auto_split_growth_verdict")) return b->learn.growth_verdict;
+    if (!strcmp(name, "auto_split_growth")) return b->learn.auto_growth;         // the stage schedule that goes with auto_split_k: K, g K, g^2 K, ...
+    if (!strcmp(name, "auto_split_permille")) return (long)(b->learn.auto_gain * 1000.0 + 0.5);
+    if (!strcmp(name, "auto_split_verdict")) return b->learn.auto_verdict;
+    if (!strcmp(name, "tile_alt_verdict")) return b->learn.tile_verdict;             // 1: the one-row shape runs on the tile kernel's dynamic form (the clock said so), -1: it does not
     if (!strcmp(name, "last_prefetch_grid")) return b->last_pf_grid;         // ... its persistent grid (waves) and its tile buffer (bytes of dynamic LDS)
     if (!strcmp(name, "last_prefetch_lds")) return (long)b->last_pf_lds;
     if (!strcmp(name, "last_tail_tile")) return b->last_tail_tile ? 1 : 0;     // the last split solve ran its tail on the tile kernel's dynamic form
@@ -1014,14 +1011,14 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_tile_form")) return b->last_tile_form;          // W * 1e6 + R * 1e3 + LM of the tile_dims.txt entry the last tile launch took (-1: run-time instantiated)
     if (!strcmp(name, "last_tile_dyn")) return b->last_tile_dyn ? 1 : 0;      // the last tile-kernel launch took the dynamic slot form
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
-    if (!strcmp(name, "auto_split_measured_permille")) return (b->auto_plain_rate > 0.0 && b->auto_split_rate > 0.0) ? (long)(1000.0 * b->auto_split_rate / b->auto_plain_rate + 0.5) : 0;
+    if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;
     if (!strcmp(name, "repack_sorted_stages")) return b->last_sorted_stages;       // follow-up stages of the last split solve that took a sorted list
     if (!strcmp(name, "step_regroup")) return b->step_regroup;
     if (!strcmp(name, "step_regroup_stretches")) return b->last_regroup_stretches;   // launches the last fused solve was cut into (1: not cut)
     if (!strcmp(name, "step_regroup_verdict") || !strcmp(name, "lockstep_permille")) {
         if (b->ls_pending && hipEventSynchronize(b->ls_ev) == hipSuccess) read_lockstep_estimate(b);      // (a diagnostic may wait; a solve never does)
-        return name[0] == 's' ? (long)b->regroup_verdict : (long)(b->lockstep_ratio * 1000.0 + 0.5);
+        return name[0] == 's' ? (long)b->learn.regroup_verdict : (long)(b->learn.lockstep_ratio * 1000.0 + 0.5);
     }
     return fail(b, TINY_ERR_ARG, "unknown option %s", name);
 }
@@ -1041,16 +1038,7 @@ int tiny_batch_get_plan(TinyBatch* b, TinyBatchPlan* out) {
     out->magic = TINY_PLAN_MAGIC; out->version = TINY_PLAN_VERSION; out->bytes = (int)sizeof(TinyBatchPlan);
     out->nx = b->nx; out->nu = b->nu; out->N = b->N; out->batch = b->batch;
     out->max_iter = b->set.max_iter; out->check_termination = b->set.check_termination;
-    out->auto_verdict = b->auto_verdict; out->auto_cap = b->auto_cap; out->auto_cap_max_iter = b->auto_cap_max_iter;
-    out->auto_growth = b->auto_growth; out->growth_verdict = b->growth_verdict; out->auto_probes = b->auto_probes;
-    out->auto_plain_rate = b->auto_plain_rate; out->auto_split_rate = b->auto_split_rate; out->auto_gain = b->auto_gain;
-    out->tile_verdict = b->tile_verdict; out->tile_rate = b->tile_rate;
-    out->regroup_verdict = b->regroup_verdict; out->lockstep_ratio = b->lockstep_ratio;
-    out->hist_valid = b->hist_copy.size() == (size_t)TinyBatch::HIST_BINS ? 1 : 0;
-    if (out->hist_valid) memcpy(out->hist, b->hist_copy.data(), sizeof(out->hist));
-    // open questions: plain-or-split undecided (while a split is on the table), the other stage schedule of a kept split untried
-    out->open_questions = ((b->auto_verdict == 0 && !(b->auto_plain_rate > 0.0 && b->auto_cap == 0)) ? 1 : 0) +
-                          ((b->auto_verdict == 1 && b->growth_verdict == 0 && b->repack_growth < 2) ? 1 : 0);
+    b->learn.to_plan(out, b->repack_growth);
     return TINY_OK;
 }
 
@@ -1060,37 +1048,21 @@ int tiny_batch_set_plan(TinyBatch* b, const TinyBatchPlan* in) {
         return fail(b, TINY_ERR_ARG, "not a TinyBatchPlan of this library version");
     if (in->nx != b->nx || in->nu != b->nu || in->N != b->N)
         return fail(b, TINY_ERR_DIM, "the plan was made for (nx,nu,N)=(%d,%d,%d), this batch is (%d,%d,%d)", in->nx, in->nu, in->N, b->nx, b->nu, b->N);
-    // every field is checked (a plan is a POD read from a file): verdicts in {-1, 0, 1}, counts non-negative, clock
-    // readings finite and non-negative.  A plan is advice only -- results never depend on it -- but a corrupt one must not pin a launch form
-    auto verdict = [](int v) { return v >= -1 && v <= 1; };
-    auto rate = [](double v) { return v >= 0.0 && v < 1e300; };
-    if (!verdict(in->auto_verdict) || !verdict(in->tile_verdict) || !verdict(in->regroup_verdict) || !verdict(in->growth_verdict) ||
-        in->auto_cap < 0 || in->auto_cap >= TinyBatch::HIST_BINS || (in->auto_growth != 2 && in->auto_growth != 4) || in->auto_cap_max_iter < 0 ||
-        in->auto_probes < 0 || in->batch <= 0 || !rate(in->auto_plain_rate) || !rate(in->auto_split_rate) || !rate(in->auto_gain) || !rate(in->tile_rate) ||
-        !rate(in->lockstep_ratio) || (in->hist_valid != 0 && in->hist_valid != 1))
-        return fail(b, TINY_ERR_ARG, "TinyBatchPlan: field out of range");
+    if (!LaunchLearner::plan_in_range(in)) return fail(b, TINY_ERR_ARG, "TinyBatchPlan: field out of range");
     HIP_TRY(b, hipSetDevice(b->device));
     // (a plan is advice about launch forms, never about results: every form is bit-identical.  It applies to solves with the
     // max_iter it was made for -- auto_cap_max_iter -- exactly as a plan learnt in this process would)
-    // A verdict whose supporting clock reading is missing, or that was made under other settings than the handle's, counts as OPEN
     const bool same_settings = in->max_iter == b->set.max_iter && in->check_termination == b->set.check_termination;
     const bool far_batch = in->batch > 4L * b->batch || b->batch > 4L * in->batch;       // (the plan of a batch of another order of magnitude)
-    b->auto_verdict = (same_settings && !far_batch && in->auto_plain_rate > 0.0 && (in->auto_verdict != 1 || in->auto_split_rate > 0.0)) ? in->auto_verdict : 0;
-    b->auto_cap = in->auto_cap; b->auto_cap_max_iter = in->auto_cap_max_iter;
-    b->auto_growth = in->auto_growth; b->growth_verdict = b->auto_verdict == 1 ? in->growth_verdict : 0; b->auto_probes = std::max(2, in->auto_probes);
-    b->auto_plain_rate = in->auto_plain_rate; b->auto_split_rate = in->auto_split_rate; b->auto_gain = in->auto_gain;
-    b->tile_verdict = (same_settings && !far_batch && (in->tile_verdict != 1 || in->tile_rate > 0.0)) ? in->tile_verdict : 0; b->tile_rate = in->tile_rate;
-    b->regroup_verdict = far_batch ? 0 : in->regroup_verdict; b->lockstep_ratio = in->lockstep_ratio;
-    if (in->hist_valid) b->hist_copy.assign(in->hist, in->hist + TinyBatch::HIST_BINS); else b->hist_copy.clear();
-    b->auto_since = b->tile_since = b->regroup_since = 0;
+    b->learn.from_plan(in, same_settings, far_batch);
     b->plan_tried = true;                            // (an imported plan stands: the shipped one is not looked up behind it)
-    b->hist_pending = false; b->ls_pending = false; b->probe_was_tile = false; b->probe_was_growth = false; b->auto_last_cap = 0;
+    b->hist_pending = false; b->ls_pending = false;
     // what the first launch of an imported form would otherwise allocate inside its solve call
-    if (b->auto_verdict == 1 && b->auto_cap > 0) {
+    if (b->learn.auto_verdict == 1 && b->learn.auto_cap > 0) {
         if (int rc = ensure_repack_buffers(b)) return rc;
         if (b->repack_sort != 0) { if (int rc = ensure_regroup_buffers(b, false)) return rc; }
     }
-    if (b->regroup_verdict == 1) { if (int rc = ensure_regroup_buffers(b, true)) return rc; }
+    if (b->learn.regroup_verdict == 1) { if (int rc = ensure_regroup_buffers(b, true)) return rc; }
     return TINY_OK;
 }
 

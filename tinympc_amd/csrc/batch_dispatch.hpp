@@ -1,5 +1,5 @@
 // batch_dispatch.hpp -- what batch_api.hip (the C ABI), batch_dispatch.hip (kernel selection, launch forms), batch_tables.hip (lane
-// tables) and batch_helpers.hip (helper kernels, cost model, on-demand buffers) share.
+// tables) and batch_helpers.hip (helper kernels, on-demand buffers) share.
 #pragma once
 #include "batch_impl.hpp"
 
@@ -40,9 +40,8 @@ void build_general_tables(TinyBatch* b);
 std::vector<double> build_adaptive_table(const TinyBatch* b);   // the shared family's ATAB_* tables from dKinf ... dC2 (no HIP call)
 int upload_tables(TinyBatch* b);
 int upload_growing(TinyBatch* b, double** dev, size_t* capacity, const std::vector<double>& host);   // host table -> device buffer that grows
-// ---- helper kernels, cost model (batch_helpers.hip)
+// ---- helper kernels (batch_helpers.hip)
 constexpr int REGROUP_AUTO_MIN_STEPS = 16, REGROUP_AUTO_MIN_BATCH = 4096;
-double wave_iteration_us(int nx, int nu, int N, int wps);
 int enqueue_iteration_histogram(TinyBatch* b);
 int enqueue_regroup_sort(TinyBatch* b, hipStream_t st, int half, int first, int count);
 int enqueue_repack_sort(TinyBatch* b, const int* list, const int* count);
@@ -51,12 +50,8 @@ int enqueue_lockstep_estimate(TinyBatch* b);
 int launch_general(TinyBatch* b, int phase = 0);
 int launch_riccati(TinyBatch* b, const RiccatiArgs& r, size_t lds_bytes, int grid);
 int launch_sensitivity(hipStream_t stream, const SensitivityArgs& s, int grid);
-// ---- the clock-checked dispatch: what probes left behind, the cost models as host arithmetic
+// ---- the clock-checked dispatch: what probes left behind goes to b->learn (launch_learner.hpp: the rules and the cost models)
 void learn_from_probe(TinyBatch* b, int max_iter, bool auto_split);
 void read_lockstep_estimate(TinyBatch* b);
-int choose_split(const TinyBatch* b, const unsigned* hist, double* ratio);
-int choose_split_for(int nx, int nu, int N, bool soc, int M, int ct, int gr, int num_cus, const unsigned* hist, double* ratio, int* growth_out = nullptr);
-std::vector<int> regroup_stretches(int steps, int K, int lead);
-int regroup_auto_k(int steps);
-bool regroup_two_streams_apply(int steps, int lead, int K);
+SplitModel split_model(const TinyBatch* b);          // the cost model's view of the batch as it is configured now
 }  // namespace tinympc_amd

@@ -1,5 +1,5 @@
-// batch_helpers.hip -- what the clock-checked dispatch needs besides the solve kernels: the iteration histogram of a solve and the cost
-// model of the split solve (host arithmetic), the counting sorts behind step_regroup / repack_sort and the lock-step estimate (small
+// batch_helpers.hip -- what the clock-checked dispatch needs besides the solve kernels: the iteration histogram of a solve (its cost
+// model is host arithmetic: launch_learner.hpp), the counting sorts behind step_regroup / repack_sort and the lock-step estimate (small
 // device kernels of this unit), the per-instance state of adaptive rho, and the buffers all of them allocate on demand.  Split off
 // batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.
 #include "batch_impl.hpp"
@@ -26,88 +26,9 @@ static __global__ __launch_bounds__(256) void iter_hist_kernel(const int4* __res
     for (int e = threadIdx.x; e < TinyBatch::HIST_BINS; e += blockDim.x)
         if (h[e]) atomicAdd(&hist[e], h[e]);
 }
-
-// Predicted launch time (arbitrary units: wave-iterations per wave slot) of a solve whose instances need hist[i] iterations,
-// four instances per wave in lock step (a wave runs to the slowest of its rows: E[max of 4] under independence), split at
-// `cap` (0 = plain) with the stage schedule of launch_solve (cap, 2 cap, 4 cap, ... max_iter).  A stage costs its work
-// spread over the wave slots, or -- when it has fewer waves than slots -- the depth of its longest wave at a lone wave's
-// pace (half the paired pace), plus a launch and one record reload / store per instance it carries.
-static double predicted_time(const unsigned* hist, int max_iter, int cap, int growth, double slots, double launch_iters, double reload_iters, bool dynamic = false) {
-    const int M = std::min(max_iter, (int)TinyBatch::HIST_BINS - 1);
-    std::vector<double> cum(M + 2, 0.0);                     // cum[i] = instances with iter <= i
-    double n = 0.0;
-    for (int i = 0; i <= M; ++i) { n += hist[i]; cum[i] = n; }
-    if (n <= 0.0) return 0.0;
-    auto stage = [&](int lo, int hi, bool first) {           // iterations lo+1 .. hi for the instances with iter > lo
-        const double open = first ? n : n - cum[lo];
-        if (open <= 0.0) return 0.0;
-        double work = 0.0, second = 0.0;                     // E[d], E[d^2] of a wave's depth d: sum_j P(d > j), sum_j (2j+1) P(d > j)
-        int depth = 0;
-        for (int i = lo; i < hi; ++i) {
-            const double F = (cum[i] - (first ? 0.0 : cum[lo])) / open;          // P(iter <= i | open)
-            const double p = 1.0 - F * F * F * F;
-            work += p;
-            second += (2.0 * (i - lo) + 1.0) * p;
-            if (p > 1e-12) depth = i + 1 - lo;
-        }
-        const double waves = open / 4.0, per_slot = waves / slots;
-        // a follow-up stage that walks its list with a fixed grid stride: a slot's time is the SUM of its waves' depths, the stage
-        // ends with the slowest slot (mean + 2.5 sigma of that sum); the first stage is balanced by the dispatcher, a follow-up
-        // stage whose waves draw their tiles from a counter (`dynamic`) ends at most one wave's depth after the mean
-        const double imbalance = first ? 0.0 : (dynamic ? std::min(0.5 * depth, 2.5 * sqrt(std::max(second - work * work, 0.0)))
-                                                        : 2.5 * sqrt(std::max(per_slot, 1e-9) * std::max(second - work * work, 0.0)));
-        const double t = std::max(work * per_slot + imbalance, 0.5 * depth);
-        return t + launch_iters + (first ? 0.0 : reload_iters * std::max(1.0, waves / slots));
-    };
-    if (cap <= 0 || cap >= M) return stage(0, M, true);
-    double t = stage(0, cap, true);
-    for (long base = cap; base < M; base *= growth) {
-        const int hi = (int)std::min<long>(M, base * growth);
-        t += stage((int)base, hi, false);
-        if (hi >= M) break;
-    }
-    return t;
-}
-
-// one wave-iteration (4 instances) of the one-row kernel in microseconds: its FLOPs at ~75 % of a SIMD's FP64 issue rate (76.8 GFLOP/s
-// per SIMD), shared by the waves of the SIMD -- 1.7 us for the quadrotor at two waves (measured 1.64)
-double wave_iteration_us(int nx, int nu, int N, int wps) {
-    const double S = (double)nx * N + (double)nu * (N - 1);
-    const double fl = 4.0 * S + 2.0 * nx * nx + 3.0 * nx + (N - 1.0) * (4.0 * nx * nx + 8.0 * nx * nu + 2.0 * nu * nu + 4.0 * nu + 5.0 * nx) + 11.0 * S;
-    return 4.0 * fl * wps / (76.8e3 * (wps == 2 ? 0.75 : 0.45));
-}
-// the K (multiple of check_termination) with the smallest predicted time, 0 when a plain launch is within 5 % of it
-int choose_split_for(int nx, int nu, int N, bool soc, int M, int ct, int gr, int num_cus, const unsigned* hist, double* ratio, int* growth_out) {
-    const int wps = solve_kernel_waves_per_simd(nx + nu, N, soc);
-    const double slots = (double)num_cus * 4.0 * wps;         // wave slots of the chip
-    // one wave-iteration in microseconds (above); the fixed costs of a stage in that unit: ~8 us of launch latency, and the record
-    // reload + store (2.45 us per wave for the quadrotor's 156 slots)
-    const double S = (double)nx * N + (double)nu * (N - 1);
-    const double t_it = wave_iteration_us(nx, nu, N, wps);
-    const double launch_iters = 8.0 / t_it, reload_iters = 2.45 * (S / 156.0) / t_it;
-    const double plain = predicted_time(hist, M, 0, 2, slots, launch_iters, reload_iters);
-    double best = plain;
-    int best_k = 0, best_gr = gr > 0 ? gr : 2;
-    // gr <= 0: the stage schedule is part of the question -- K, 2K, 4K, ... or K, 4K, 16K, ... (fewer launches, deeper lock step)
-    const int grs[2] = {gr > 0 ? gr : 2, gr > 0 ? gr : 4};
-    for (int gi = 0; gi < (gr > 0 ? 1 : 2); ++gi) {
-        for (int k = std::max(ct, 4 - 4 % ct); k <= M / 2; k += ct) {
-            if (k > 64 && k % 8) continue;                    // coarser steps far out
-            const double t = predicted_time(hist, M, k, grs[gi], slots, launch_iters, reload_iters);
-            if (t < best) { best = t; best_k = k; best_gr = grs[gi]; }
-        }
-    }
-    // One check interval of margin: the histogram is the LAST solve's, and being a step late costs next to nothing (measured on config 3,
-    // mode 8-9 of 262 144: K = 10 ... 14 within 3 %) while being a step early sends the whole mode through a second launch (K = 9
-    // +6 %, K = 8 +60 %)
-    if (best_k > 0 && best_k + ct <= M / 2 && predicted_time(hist, M, best_k + ct, best_gr, slots, launch_iters, reload_iters) <= 1.01 * best) best_k += ct;
-    if (ratio) *ratio = plain > 0.0 ? best / plain : 1.0;
-    if (growth_out) *growth_out = best_gr;
-    return (plain > 0.0 && best < 0.95 * plain) ? best_k : 0;
-}
-int choose_split(const TinyBatch* b, const unsigned* hist, double* ratio) {
-    return choose_split_for(b->nx, b->nu, b->N, soc_active(b), b->set.max_iter, std::max(1, b->set.check_termination), b->repack_growth >= 2 ? b->repack_growth : 0,
-                            b->num_cus, hist, ratio, &const_cast<TinyBatch*>(b)->auto_growth);
+SplitModel split_model(const TinyBatch* b) {
+    return {b->nx, b->nu, b->N, solve_kernel_waves_per_simd(b->nx + b->nu, b->N, soc_active(b)), b->set.max_iter, std::max(1, b->set.check_termination),
+            b->repack_growth >= 2 ? b->repack_growth : 0, b->num_cus};
 }
 
 // ---- adaptive rho: per-instance cache state + the lane tables of the adaptation step -----------------------------------
@@ -390,26 +311,8 @@ int enqueue_lockstep_estimate(TinyBatch* b) {
 }
 void read_lockstep_estimate(TinyBatch* b) {
     b->ls_pending = false;
-    b->lockstep_ratio = b->h_ls[1] > 0ull ? (double)b->h_ls[0] / (double)b->h_ls[1] : 1.0;
-    if (b->regroup_verdict == 0) b->regroup_verdict = b->lockstep_ratio >= 1.05 ? 1 : -1;
+    b->learn.lockstep_estimate_arrived(b->h_ls[0], b->h_ls[1]);
 }
-// stretches of `steps` MPC steps: `lead` steps first (0: none), then K steps each; a short remainder joins the stretch before it
-std::vector<int> regroup_stretches(int steps, int K, int lead) {
-    std::vector<int> out;
-    int left = steps;
-    if (lead > 0 && left > lead) { out.push_back(lead); left -= lead; }
-    while (left > 0) {
-        int n = std::min(K, left);
-        if (left - n > 0 && left - n < (K + 1) / 2) n = left;
-        out.push_back(n);
-        left -= n;
-    }
-    return out;
-}
-int regroup_auto_k(int steps) { return std::max(8, (steps + 3) / 4); }
-// the two-stream form (halves of the batch half a stretch out of step) only makes sense when more than one stretch is left after the
-// lead step: the condition the launch and tiny_step_regroup_plan share
-bool regroup_two_streams_apply(int steps, int lead, int K) { return steps - lead > K; }
 
 // index lists + per-stage counters of the split solve: [stage] list lengths, [32 + stage] tile counters
 int ensure_repack_buffers(TinyBatch* b) {

@@ -13,6 +13,7 @@
 #include "sensitivity_kernel.hip.h"
 #include "tile_kernel.hip.h"
 #include "cache.hpp"
+#include "launch_learner.hpp"
 
 namespace tinympc_amd {
 
@@ -37,9 +38,7 @@ struct TinyBatch {
     bool tile_is_jit = false, tile_soc_failed = false;
     bool redispatch = false;                     // launch_solve re-entered by itself after a failed instantiation (not a caller-side change)
     bool no_jit = false, jit_failed = false, variant_jit_failed = false;     // run-time instantiation of the one-row kernel for shapes outside kernel_dims.txt (jit.hpp)
-    int tile_verdict = 0, tile_since = 0;        // the dynamic tile form tried on a one-row shape: 1 kept, -1 rejected, 0 open (batch_dispatch.hip launch_solve)
-    double tile_rate = 0.0;
-    bool probe_was_tile = false;
+    tinympc_amd::LaunchLearner learn;            // what the clock has settled about this batch's launch form (launch_learner.hpp)
     int tile_w = -1;                             // option "tile_w"
     int tile_lm = -1;                            // option "tile_lm"
     int tile_dyn_opt = -1;                       // option "tile_dyn"
@@ -94,31 +93,21 @@ struct TinyBatch {
     // instance no longer holds a wave by itself).  Results are bit-identical to the unsplit solve.
     int repack_after = -1;               // K > 0: split at K; 0: never; -1 (default): K picked from the previous solve's iteration histogram
     // automatic split: histogram of the per-instance iteration counts of the last eligible solve (device -> pinned host,
-    // asynchronous), and the K the cost model derived from it (0 = a plain launch is predicted to be as fast)
+    // asynchronous); the K the cost model derives from it is learn.auto_cap
     enum { HIST_BINS = 1024 };
     unsigned *d_hist = nullptr, *h_hist = nullptr;
     hipEvent_t hist_ev = nullptr;
     bool hist_pending = false;
-    int auto_cap = 0, auto_cap_max_iter = 0;
     // the model's proposal is then checked against the clock: time per instance-iteration of the last plain and the last split
     // launch (HIP events around the launches of an eligible solve, read when the histogram arrives)
     hipEvent_t auto_ev0 = nullptr, auto_ev1 = nullptr;
-    int auto_last_cap = 0;               // the cap the timed launch ran with
-    int auto_probes = 0;                 // timed solves so far (the first one carries one-time costs -- code object load -- and is not used)
-    double auto_plain_rate = 0.0, auto_split_rate = 0.0;
-    int auto_since = 0;                  // eligible solves since the last verdict: every 32nd one re-opens the question (plain + split timed again)
-    int auto_verdict = 0;                // 0 undecided, 1 the split was measured faster (kept), -1 measured slower (plain launches from now on)
-    double auto_gain = 0.0;              // predicted time of the split solve / plain solve (diagnostics)
     bool repack_dynamic = false;                 // follow-up stages of a split solve take their tiles off a per-stage counter (measured on config 3: 1-2 % SLOWER than the grid stride)
     int repack_waves_per_cu = 8, repack_growth = 0;   // grid of the follow-up stages; stage s runs to K * growth^s (0: the cost model picks 2 or 4 with K)
-    int auto_growth = 2, growth_alt = 2, growth_verdict = 0;   // the stage schedule in use; the one on trial; 1 = the clock has compared the two
-    bool probe_was_growth = false;
     // repack_sort: the list of open instances a stage of a split solve takes is ordered by how far each is from its tolerances
     // (largest residual / tolerance ratio first; 16 bins per octave, a counting sort between the stages): ADMM converges at a roughly
     // geometric rate, so rows that are equally far out leave their wave together.  1: every follow-up stage; 0: never; -1 (default):
     // the stages that the last iteration histogram predicts to run for at least 60 us
     int repack_sort = -1;
-    std::vector<unsigned> hist_copy;     // the histogram the schedule in use was derived from (h_hist is overwritten asynchronously)
     int last_sorted_stages = 0;
     int *d_repack_index = nullptr, *d_repack_count = nullptr;
     bool use_ub = true;                            // option "uniform_bounds": take the UB kernel variant when the box allows it
@@ -177,7 +166,6 @@ struct TinyBatch {
     // it will need at the next ones.  K > 0: stretches of K steps; 0: never; -1 (default): on when the iteration totals of the
     // previous fused launch of this batch (d_accum, grouped four by four as the waves take them) say that lock step costs >= 5 %.
     int step_regroup = -1;
-    int regroup_verdict = 0, regroup_since = 0;    // 0 open, 1 on, -1 off (the estimate of the last fused launch decided)
     bool status_valid = false;                     // d_status holds this episode's last iteration counts (not after setup / reset)
     int* d_perm = nullptr;
     // option "step_regroup_streams": 2 (default) = the batch in two halves on two streams, their stretches half a stretch apart (a
@@ -191,7 +179,6 @@ struct TinyBatch {
     unsigned long long *d_ls = nullptr, *h_ls = nullptr;   // {4 x sum over waves of the largest total, sum of the totals}
     hipEvent_t ls_ev = nullptr;
     bool ls_pending = false;
-    double lockstep_ratio = 0.0;                   // the last estimate (1.0 = rows of a wave agree)
     int last_regroup_stretches = 0;                // launches the last fused solve was cut into (1: not cut)
     int store_primal = 1;                // false: launches do not write x|u back (no consumer between closed-loop steps when the plant step runs on the device)
     bool records_zero = false, auto_cold = true; // every warm-start record is known to be zero (after tiny_batch_reset / setup): launches skip reading them
