@@ -99,7 +99,8 @@ int tiny_batch_setup(TinyBatch** out, const double* Adyn, const double* Bdyn, co
 /* Heterogeneous batch: instance i has its OWN (A_i, B_i, f_i, Q_i, R_i, rho_i) -- arrays with a leading batch
  * axis ([batch][nx*nx] column-major, [batch][nx*nu], [batch][nx] (may be NULL), [batch][nx], [batch][nu], [batch]).
  * tiny_precompute_and_set_cache (tiny_api.cpp:307-381) runs on the GPU for all instances at once; the solve kernel
- * then streams each instance's own cache.  Bounds, cones and settings stay shared.  Any nx + nu <= 32, nu <= 16 (round 5): shapes the
+ * then streams each instance's own cache.  Cones and settings stay shared; the box is shared unless tiny_batch_set_instance_bounds gives every
+ * instance its own.  Any nx + nu <= 32, nu <= 16 (round 5): shapes the
  * one-row kernel holds run its HET variant, wide and long shapes the tile kernel's per-instance form on the shape's fastest box form
  * (run-time instantiated: needs hipRTC or the prebuilt store); TINY_ERR_UNSUPPORTED when neither kernel holds the shape.  Round 6: cones
  * that share rows, more half-spaces per knot than the register variants hold, or a variant hipRTC cannot make send a heterogeneous
@@ -117,6 +118,24 @@ int tiny_batch_destroy(TinyBatch* b);
  * column-major, shared by every instance. */
 int tiny_batch_set_bound_constraints(TinyBatch* b, const double* x_min, const double* x_max,
                                      const double* u_min, const double* u_max);
+/* every instance its own box: x_min / x_max are [batch][N][nx] (per instance nx x N column-major, like Xref),
+ * u_min / u_max [batch][N-1][nu].  flags: TINY_HOST or TINY_DEVICE (copied; the caller may free); TINY_BROADCAST is TINY_ERR_ARG (one box
+ * for all: the shared setter above).  The latest setter wins: this one replaces a shared box, a later tiny_batch_set_bound_constraints
+ * replaces this one; en_state_bound / en_input_bound act as on the shared box (a disabled family is (-inf, +inf)); tiny_batch_reset leaves
+ * the box alone.  Works on tiny_batch_setup and tiny_batch_setup_hetero batches.  Synchronous.  Read-backs (tiny_batch_get_option):
+ * "instance_bounds" 1 while such a box is installed, "last_instance_bounds" 1 when the last solve's kernel read one;
+ * "last_uniform_bounds" keeps its meaning -- a UB form ran, which here means EVERY instance's box is knot-invariant for the enabled families.
+ * Where it runs: the one-row kernel's PB forms (run-time instantiated, full rows, no prefetch: "last_half_rows" and "last_prefetch" read
+ * 0) for the plain box variants of the shapes that kernel holds, with every launch form of those; the coverage kernel -- correct, not
+ * fast, tiny_batch_kernel_path says so -- for tile-kernel shapes (nx + nu > 16 or a horizon beyond the one-row kernel), an enabled cone
+ * or half-space family, "debug", "force_general", "no_jit" or a missing hipRTC.  Adaptive rho with a per-instance box fails the solve
+ * with TINY_ERR_UNSUPPORTED.  Out of scope: the tile kernel, the cone and half-space register variants, tiny_codegen and
+ * tiny_solve_batch (which goes on taking solvers[0]'s bounds for all solvers). */
+int tiny_batch_set_instance_bounds(TinyBatch* b, const double* x_min, const double* x_max,
+                                   const double* u_min, const double* u_max, int flags);
+/* what instance `instance` is bound by, as set (whatever the enable switches say); on a shared box: the shared one ((-inf, +inf) when
+ * none was ever set).  any pointer may be NULL */
+int tiny_batch_get_instance_bounds(TinyBatch* b, int instance, double* x_min, double* x_max, double* u_min, double* u_max);
 /* == tiny_set_cone_constraints (tiny_api.cpp:176-208): STATE triple first (the definition's
  * positional order).  Cones have dimension 3 (admm.cpp:53).  Cones of one family may share rows: the reference projects them
  * one after the other (admm.cpp:111-135) and so does this library -- on the coverage kernel (single-step launches, shared
@@ -394,6 +413,8 @@ int tiny_group_uses_rccl(TinyGroup* g);                       /* 1: the exchange
 const char* tiny_group_last_error(TinyGroup* g);
 /* problem-family setters and options: forwarded to every shard (same meaning as the tiny_batch_* functions) */
 int tiny_group_set_bound_constraints(TinyGroup* g, const double* x_min, const double* x_max, const double* u_min, const double* u_max);
+int tiny_group_set_instance_bounds(TinyGroup* g, const double* x_min, const double* x_max,
+                                   const double* u_min, const double* u_max);   /* host, full batch axis, caller order */
 int tiny_group_set_cone_constraints(TinyGroup* g, int n_state_cones, const int* Acx, const int* qcx, const double* cx,
                                     int n_input_cones, const int* Acu, const int* qcu, const double* cu);
 int tiny_group_set_linear_constraints(TinyGroup* g, int n_state, const double* Alin_x, const double* blin_x,

@@ -37,7 +37,7 @@ PLAN_BYTES = 19 * 4 + 4 + 5 * 8 + 1024 * 4      # sizeof(TinyBatchPlan): 19 ints
 # every extern "C" symbol include/tinympc_amd.h declares (checked by tests/test_abi_symbols.py)
 BATCH_SYMBOLS = (
     "tiny_batch_device_count", "tiny_batch_setup", "tiny_batch_setup_hetero", "tiny_batch_get_cache_instance",
-    "tiny_batch_destroy", "tiny_batch_set_bound_constraints",
+    "tiny_batch_destroy", "tiny_batch_set_bound_constraints", "tiny_batch_set_instance_bounds", "tiny_batch_get_instance_bounds",
     "tiny_batch_set_cone_constraints", "tiny_batch_set_linear_constraints", "tiny_batch_set_tv_linear_constraints",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
@@ -49,7 +49,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_compute_sensitivity", "tiny_batch_get_sensitivity", "tiny_batch_get_sensitivity_instance")
 GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
-    "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_cone_constraints",
+    "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
@@ -164,6 +164,8 @@ def lib():
         L.tiny_batch_get_cache_instance.argtypes = [C.c_void_p, C.c_int, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_destroy.argtypes = [C.c_void_p]
         L.tiny_batch_set_bound_constraints.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.tiny_batch_set_instance_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_instance_bounds.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
         L.tiny_batch_set_cone_constraints.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp]
         L.tiny_batch_set_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_batch_set_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
@@ -225,6 +227,7 @@ def lib():
         L.tiny_group_last_error.argtypes = [C.c_void_p]
         L.tiny_group_last_error.restype = C.c_char_p
         L.tiny_group_set_bound_constraints.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
+        L.tiny_group_set_instance_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp]
         L.tiny_group_set_cone_constraints.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp]
         L.tiny_group_set_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
@@ -374,6 +377,28 @@ class TinyBatchSolver:
              _colmajor(u_max, (nu, N - 1))]
         self._check(lib().tiny_batch_set_bound_constraints(self._h, *[v.ctypes.data_as(_dp) for v in a]),
                     "set_bound_constraints")
+
+    def _instance_boxes(self, x_min, x_max, u_min, u_max):
+        """[batch, nx, N] x 2, [batch, nu, N-1] x 2 -> flat [batch][knot][row] doubles (per instance column-major)"""
+        shapes = [(self.batch, self.nx, self.N)] * 2 + [(self.batch, self.nu, self.N - 1)] * 2
+        return [np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), s).transpose(0, 2, 1)).ravel()
+                for v, s in zip((x_min, x_max, u_min, u_max), shapes)]
+
+    def set_instance_bounds(self, x_min, x_max, u_min, u_max):
+        """every instance its own box: x_min / x_max [batch, nx, N], u_min / u_max [batch, nu, N-1]"""
+        a = self._instance_boxes(x_min, x_max, u_min, u_max)
+        self._check(lib().tiny_batch_set_instance_bounds(self._h, *[v.ctypes.data_as(C.c_void_p) for v in a], HOST), "set_instance_bounds")
+
+    def set_instance_bounds_device(self, x_min, x_max, u_min, u_max):
+        """the same from device pointers (ints) to [batch][N][nx] | [batch][N-1][nu] doubles resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_instance_bounds(self._h, *[C.c_void_p(int(p)) for p in (x_min, x_max, u_min, u_max)], DEVICE),
+                    "set_instance_bounds_device")
+
+    def instance_bounds(self, i):
+        """(x_min, x_max [nx, N], u_min, u_max [nu, N-1]) instance i is bound by, as set; on a shared box: the shared one"""
+        out = [np.zeros((self.N, self.nx)), np.zeros((self.N, self.nx)), np.zeros((self.N - 1, self.nu)), np.zeros((self.N - 1, self.nu))]
+        self._check(lib().tiny_batch_get_instance_bounds(self._h, int(i), *[v.ctypes.data_as(_dp) for v in out]), "instance_bounds")
+        return tuple(v.T.copy() for v in out)
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         """STATE triple first (the positional order of the reference's definition, tiny_api.cpp:176-178)."""
@@ -702,6 +727,11 @@ class TinyGroupSolver:
         um, uM = _colmajor(u_min, (nu, N - 1)), _colmajor(u_max, (nu, N - 1))
         self._check(lib().tiny_group_set_bound_constraints(self._h, xm.ctypes.data_as(_dp), xM.ctypes.data_as(_dp),
                                                            um.ctypes.data_as(_dp), uM.ctypes.data_as(_dp)), "set_bound_constraints")
+
+    def set_instance_bounds(self, x_min, x_max, u_min, u_max):
+        """every instance its own box, the full batch axis in the caller's order: [batch, nx, N] x 2, [batch, nu, N-1] x 2"""
+        a = TinyBatchSolver._instance_boxes(self, x_min, x_max, u_min, u_max)
+        self._check(lib().tiny_group_set_instance_bounds(self._h, *[v.ctypes.data_as(_dp) for v in a]), "set_instance_bounds")
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         ai = lambda v: np.ascontiguousarray(v, dtype=np.int32)

@@ -32,7 +32,8 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data).  kernel_dims.txt lists the shapes
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box; see
+//     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -66,7 +67,7 @@ struct LaneTab {
     constexpr int PT() const { return 3 * cols * lw; }        // terminal:  cols k<nx multiply Xref[k, N-1] (state lanes: Pinf[k][j])
     constexpr int VEC() const { return 4 * cols * lw; }       // lw-entry lane vectors, see VEC_* above
     constexpr int BOUNDS() const { return VEC() + VEC_COUNT * lw; }
-    constexpr int het_doubles() const { return BOUNDS(); }    // a per-instance table: the matrix + vector part (bounds / cones / masks stay shared)
+    constexpr int het_doubles() const { return BOUNDS(); }    // a per-instance table: the matrix + vector part (cones / masks stay shared; a per-instance box is an array of its own: SolveArgs::inst_bounds)
     // half-space tables of the LIN variants behind the bounds: static [3][kmax][lw], then per slot [N][3][kmax][lw]
     constexpr int lin_offset(int N) const { return BOUNDS() + 2 * N * lw; }
     constexpr int tlin_offset(int N, int kmax) const { return lin_offset(N) + 3 * kmax * lw; }
@@ -125,7 +126,8 @@ struct SolveArgs {
     int traj_points, traj_step0;
     int reset_duals;          // 1: g = 0, y = 0 before every solve (examples/quadrotor_tracking.cpp:92-93)
     // Heterogeneous problem families (riccati_kernel.hip.h): per-instance matrix/vector tables
-    // ([batch][TAB_BOUNDS] doubles, same layout as `tab`); bounds, cones and masks stay shared.
+    // ([batch][TAB_BOUNDS] doubles, same layout as `tab`); cones and masks stay shared, and so do the bounds unless the launch is a
+    // PB form (inst_bounds below), which composes with this one.
     const double* het_tabs;
     // register-resident linear constraints (LIN variants): KPI records of vlnew|zlnew, gl|yl, vlnew_tv|zlnew_tv,
     // gl_tv|yl_tv and the number of half-spaces applied per knot (max over the state / input families)
@@ -190,7 +192,13 @@ struct SolveArgs {
     // would take 0.7 ms).  The counters are never reset: a shard's waves draw exactly (its ticketed tiles) + (its waves) tickets per
     // launch, pf_base[x] is where this launch's begin (the host keeps the sums)
     int pf_mask, pf_shards, pf_static;
-    unsigned* pf_counter;
+    // one-row kernel, PB forms: every instance its own box -- [batch][lo | hi][N slots][16 lanes], the slot convention of the shared table's
+    // bounds block (lane_tables.hpp box_entry; built by batch_helpers.hip from the caller's arrays).  PB and PF exclude each other, so the
+    // pointer takes the place of the PREFETCH form's ticket counters: the argument block of every other form keeps its size and offsets
+    union {
+        unsigned* pf_counter;
+        const double* inst_bounds;
+    };
     unsigned pf_base[8];
 };
 
@@ -717,12 +725,22 @@ __device__ __forceinline__ void project_halfspace_columns(const int t, const int
 // HALF: nx+nu <= 8 -- TWO instances per DPP row (lanes 0-7 | 8-15), eight per wave: every lane-local instruction and every register
 // serves twice the instances; a mat-vec column is a pair of bank-masked FMAs (fused_*_step_half).  Plain box variants only.
 // PF: the PREFETCH form (SolveArgs::pf_mask): plain box variants, plain launches (no index / perm / trajectory window)
-template <int NX, int NU, int N, bool SOC, bool DBG, int MODE, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
+// PB: every instance its own box (SolveArgs::inst_bounds) -- the bounds are per-ROW quantities, reloaded for each tile: with UB (every
+// instance's box is knot-invariant) four doubles per lane next to the HET table loads, no LDS and the UB form's register count; without
+// it the row's block of sLo / sHi [IPW][N * 16], filled at the top of the tile by the row's own lanes.  The iteration loop is the one of
+// the shared-box form: the bounds were operands of its step blocks already.  Box variants on full rows, not the PREFETCH form; with
+// HET and every MODE.  Instantiated at run time only (jit.hip).  The flag travels as bit 2 of the sixth template argument (MODE_PB =
+// MODE | 4): a template parameter of its own, even one with a default, would lengthen the mangled name of EVERY instantiation, and those
+// names are what the registry, the register-budget tests and tools/isa_diff.py know the compiled-in kernels by.
+template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
 __attribute__((amdgpu_waves_per_eu(LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT),
                                    LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT))))
 void admm_solve_kernel(const SolveArgs P) {
+    constexpr int MODE = MODE_PB & 3;
+    constexpr bool PB = (MODE_PB & 4) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 8, "MODE 0 | 1 | 2, + 4: per-instance box");
     constexpr bool LS = (LIN & 1) != 0, LT = (LIN & 2) != 0;
     constexpr int NZ = NX + NU;
     static_assert(NZ <= 16, "one instance per 16-lane DPP row");
@@ -731,6 +749,13 @@ void admm_solve_kernel(const SolveArgs P) {
     // (12,4,10) + 2 + 2 half-spaces 5.31 ms either way; what the variant pays is its projection step and 208 B/lane of scratch)
     static_assert(!HALF || (NZ <= 8 && FUSED && !SOC && !DBG && !HET && !ADAPT), "half rows: nx+nu <= 8, the plain box kernel on its fused step blocks");
     static_assert(!PF || (MODE == 2 && !SOC && !DBG && LIN == 0 && !HET && !ADAPT), "prefetch form: the plain box kernel");
+    static_assert(!PB || (!HALF && !PF), "per-instance box: full rows, not the prefetch form");
+    // PB without UB: a wave's static LDS is sPt + the four rows' blocks, 128 NX + 1024 N bytes.  Every shape the kernel holds keeps its
+    // waves per SIMD under that: two waves need 6 N + 2 (NX + NU) <= 100, so N <= 16 and eight waves of a CU take at most 8 x 18 KB of its
+    // 160 KB; one wave per SIMD ends at N = 37 (the 512-register file), four waves x 38 KB
+    static_assert(!PB || UB || 4L * solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT) * (128 * NX + 1024 * N) <= 160 * 1024,
+                  "per-instance box: the rows' bound blocks must leave the shape its waves per SIMD");
+    static_assert(!PB || (!SOC && LIN == 0 && !ADAPT), "per-instance box: the box variants (cones, half-spaces and adaptive rho run on the coverage kernel / are refused)");
     constexpr int RL = HALF ? 8 : 16;                                  // lanes of one instance
     constexpr int IPW = 64 / RL;                                       // instances per wave
     constexpr int RECD = N * NZ;                                       // doubles of one instance's record
@@ -745,8 +770,8 @@ void admm_solve_kernel(const SolveArgs P) {
 
     // per-wave LDS copies of the tables that are read with a dynamic index or only once per solve
     __shared__ double sPt[NX * 16];
-    __shared__ double sLo[UB ? 1 : N * 16];                    // (UB: the two bounds of a lane live in registers, read from the table once)
-    __shared__ double sHi[UB ? 1 : N * 16];
+    __shared__ double sLo[UB ? 1 : (PB ? IPW : 1) * N * 16];   // (UB: the two bounds of a lane live in registers, read from the table once;
+    __shared__ double sHi[UB ? 1 : (PB ? IPW : 1) * N * 16];   //  PB: one block per row, filled for every tile)
     __shared__ double sLin[LS ? 3 * KMAX * 16 : 1];
     __shared__ double sTLin[LT ? 3 * N * KMAX * 16 : 1];
     // SOC: the cone slack lives in LDS, not in registers.  Per row and slot three planes of CS cells (lane j: cell j; the lanes beyond
@@ -791,7 +816,7 @@ void admm_solve_kernel(const SolveArgs P) {
     if constexpr (LT) for (int e = lane; e < 3 * N * KMAX * 16; e += 64) sTLin[e] = P.tab[TAB_BOUNDS + 2 * N * 16 + 3 * KMAX * 16 + e];
     for (int e = lane; e < NX * 16; e += 64) sPt[e] = P.tab[TAB_PT + e];
     for (int e = lane; e < N * 16; e += 64) {
-        if constexpr (!UB) {
+        if constexpr (!UB && !PB) {
             sLo[e] = P.tab[TAB_BOUNDS + e];
             sHi[e] = P.tab[TAB_BOUNDS + N * 16 + e];
         }
@@ -807,8 +832,11 @@ void admm_solve_kernel(const SolveArgs P) {
     double cb = P.tab[TAB_VEC + VEC_CB * 16 + j];
     double cf = P.tab[TAB_VEC + VEC_CF * 16 + j];
     double qr = P.tab[TAB_VEC + VEC_QR * 16 + j];
-    const double smask = P.tab[TAB_VEC + VEC_SMASK * 16 + j];
-    const double nim = P.tab[TAB_VEC + VEC_NIM * 16 + j];
+    // (PB: the two masks are formed from the lane index -- the very numbers the table holds, batch_tables.hip -- so that the compiler may
+    // form them again where it would otherwise carry or spill them: the per-instance-data form sits at the 256-register limit, and the
+    // bounds of a PB form, loaded per tile, cannot be parked in scratch before the tile loop the way the shared ones are)
+    const double smask = PB ? (is_state ? 1.0 : 0.0) : P.tab[TAB_VEC + VEC_SMASK * 16 + j];
+    const double nim = PB ? (is_input ? -1.0 : 0.0) : P.tab[TAB_VEC + VEC_NIM * 16 + j];
     bool soc_lane = false, proj_lane = false;
     int cone_base = -1, cone_c = 0;
     double socmask = 0.0;
@@ -878,8 +906,10 @@ void admm_solve_kernel(const SolveArgs P) {
     __builtin_amdgcn_wave_barrier();   // LDS tables were written by other lanes of this wave
 
     // UB: slot 1 speaks for every slot (slot 0 of an input lane is the neutral dummy: its box stays (-inf, +inf))
-    const double lo_u = P.tab[TAB_BOUNDS + (N > 1 ? 16 : 0) + j], hi_u = P.tab[TAB_BOUNDS + N * 16 + (N > 1 ? 16 : 0) + j];
-    const double lo_u0 = P.tab[TAB_BOUNDS + j], hi_u0 = P.tab[TAB_BOUNDS + N * 16 + j];
+    // (PB: the row's instance has its own, loaded for every tile: rlo_u ... below)
+    const double lo_u = PB ? 0.0 : P.tab[TAB_BOUNDS + (N > 1 ? 16 : 0) + j], hi_u = PB ? 0.0 : P.tab[TAB_BOUNDS + N * 16 + (N > 1 ? 16 : 0) + j];
+    const double lo_u0 = PB ? 0.0 : P.tab[TAB_BOUNDS + j], hi_u0 = PB ? 0.0 : P.tab[TAB_BOUNDS + N * 16 + j];
+    const int sbox = PB ? grp * (N * 16) : 0;                  // PB && !UB: this row's block of sLo / sHi
     // (PF: a plain single-step launch over the whole batch -- no index list, no permutation, no trajectory window: those paths are
     // compiled OUT of the form, because a register-returning load on ANY path between a tile's hand-over and its stores makes the
     // compiler wait for the whole VMEM queue at the join, the next tile's pieces included)
@@ -1041,6 +1071,24 @@ void admm_solve_kernel(const SolveArgs P) {
                 cf = het[TAB_VEC + VEC_CF * 16 + j];
                 qr = het[TAB_VEC + VEC_QR * 16 + j];
                 rho = het[TAB_VEC + VEC_RHO * 16 + j];
+            }
+            // the row's box of a UB form: the wave's (shared box), or -- PB -- this instance's own: [lo | hi][N slots][16 lanes]
+            double rlo_u = lo_u, rhi_u = hi_u, rlo_u0 = lo_u0, rhi_u0 = hi_u0;
+            if constexpr (PB) {
+                // (this lane's entry of slot 0, as ONE offset formed here: split into a per-lane part and a per-instance part, the former
+                // is hoisted out of the tile loop and held -- or spilled -- from the kernel's first instruction to its last)
+                size_t ib_at = (size_t)b * (2 * N * 16) + j;
+                asm volatile("" : "+v"(ib_at));
+                const double* ib = P.inst_bounds + ib_at;
+                if constexpr (UB) {                            // slot 1 speaks for every slot but an input lane's dummy slot 0
+                    rlo_u0 = ib[0]; rhi_u0 = ib[N * 16];
+                    rlo_u = ib[N > 1 ? 16 : 0]; rhi_u = ib[N * 16 + (N > 1 ? 16 : 0)];
+                } else {                                       // one 128-byte segment per slot and bound, by the row's own lanes
+#pragma unroll
+                    for (int s = 0; s < N; ++s) { sLo[sbox + s * 16 + j] = ib[s * 16]; sHi[sbox + s * 16 + j] = ib[N * 16 + s * 16]; }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
             }
             if constexpr (ADAPT) {                             // this instance's own rho / Kinf / Pinf (they persist from solve to solve)
                 rho = P.arho[b];
@@ -1374,7 +1422,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     // Software pipeline: the box bounds of slot i+1 are read from LDS one whole step before
                     // they are used (sched_barrier pins the reads above the step), and slot i's update is
                     // scheduled together with the FMA chain of step i -- both only need x_i.
-                    double lo_c = UB ? lo_u0 : sLo[j], hi_c = UB ? hi_u0 : sHi[j];
+                    double lo_c = UB ? rlo_u0 : sLo[sbox + j], hi_c = UB ? rhi_u0 : sHi[sbox + j];
                     double gr[SOC ? SPR : 1];                   // SOC: gc of slot i, read from its plane SPD steps ahead
                     if constexpr (SOC) {
 #pragma unroll
@@ -1392,7 +1440,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     double tt_d = 0.0, vn_d = 0.0;              // TIGHT: x + g and vnew of the step before (its g is formed one step late)
 #pragma unroll
                     for (int i = 0; i < N - 1; ++i) {
-                        const double lo_n = UB ? lo_u : sLo[(i + 1) * 16 + j], hi_n = UB ? hi_u : sHi[(i + 1) * 16 + j];
+                        const double lo_n = UB ? rlo_u : sLo[sbox + (i + 1) * 16 + j], hi_n = UB ? rhi_u : sHi[sbox + (i + 1) * 16 + j];
                         if constexpr (SOC) { if (i + SPD < N) gr[(i + SPD) % SPR] = sC[cw + (i + SPD) * SLOT_D + PL_GC]; }
                         if constexpr (LSP) { if (i + SPD < N) glr[(i + SPD) % SPR] = sLG[cl + (i + SPD) * CSL]; }
                         if constexpr (LTP) { if (i + SPD < N) gtr[(i + SPD) % SPR] = sTG[cl + (i + SPD) * CSL]; }

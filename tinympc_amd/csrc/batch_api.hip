@@ -346,7 +346,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_iter_log, b->d_u0_log, b->d_lslack, b->d_ldual, b->d_tlslack, b->d_tldual, b->d_gtab, b->d_traj,
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
-                    b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
     if (b->h_wire) hipHostFree(b->h_wire);
@@ -377,7 +377,65 @@ int tiny_batch_set_bound_constraints(TinyBatch* b, const double* x_min, const do
     b->x_min.assign(x_min, x_min + ns); b->x_max.assign(x_max, x_max + ns);
     b->u_min.assign(u_min, u_min + ni); b->u_max.assign(u_max, u_max + ni);
     b->have_bounds = true;
+    if (b->inst_bounds || b->d_inst_bounds || b->d_ib_src[0]) {
+        // the latest setter wins: the shared box replaces a per-instance one, whose device arrays (at 65 536 quadrotors: 168 MB + the
+        // caller's four) go once the stream has run dry of their readers
+        b->inst_bounds = false; b->inst_bounds_dirty = false;
+        HIP_TRY(b, hipSetDevice(b->device));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        for (double*& p : b->d_ib_src) { if (p) (void)hipFree(p); p = nullptr; }
+        if (b->d_inst_bounds) (void)hipFree(b->d_inst_bounds);
+        b->d_inst_bounds = nullptr;
+    }
     b->tab_dirty = true;
+    return TINY_OK;
+}
+
+// every instance its own box.  The caller's arrays are kept on the device as given; what the kernels read is built from them at once
+// (ensure_instance_bounds: synchronous, it reads the knot-invariance flag back) and again when an enable switch changes.  The shared box
+// is given up only once that has succeeded: a call that fails leaves the batch on the shared box it had (a per-instance box it had
+// before is gone: its arrays were being overwritten)
+int tiny_batch_set_instance_bounds(TinyBatch* b, const double* x_min, const double* x_max, const double* u_min, const double* u_max, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    if (!x_min || !x_max || !u_min || !u_max) return fail(b, TINY_ERR_NULL, "null bound pointer");
+    if (flags & TINY_BROADCAST) return fail(b, TINY_ERR_ARG, "one box for every instance: tiny_batch_set_bound_constraints");
+    HIP_TRY(b, hipSetDevice(b->device));
+    const size_t n[4] = {(size_t)b->batch * b->N * b->nx, (size_t)b->batch * b->N * b->nx, (size_t)b->batch * (b->N - 1) * b->nu, (size_t)b->batch * (b->N - 1) * b->nu};
+    const double* src[4] = {x_min, x_max, u_min, u_max};
+    b->inst_bounds = false;
+    for (int i = 0; i < 4; ++i) {
+        if (!b->d_ib_src[i]) HIP_TRY(b, hipMalloc(&b->d_ib_src[i], std::max<size_t>(n[i], 1) * sizeof(double)));
+        HIP_TRY(b, hipMemcpyAsync(b->d_ib_src[i], src[i], n[i] * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
+    }
+    b->inst_bounds = true; b->inst_bounds_dirty = true;
+    b->tab_dirty = true;
+    if (int rc = ensure_instance_bounds(b)) { b->inst_bounds = false; return rc; }
+    b->have_bounds = false;                          // (the latest setter wins: the shared box is gone)
+    b->x_min.clear(); b->x_max.clear(); b->u_min.clear(); b->u_max.clear();
+    return TINY_OK;
+}
+
+int tiny_batch_get_instance_bounds(TinyBatch* b, int instance, double* x_min, double* x_max, double* u_min, double* u_max) {
+    if (!b) return TINY_ERR_NULL;
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    const size_t ns = (size_t)b->N * b->nx, ni = (size_t)(b->N - 1) * b->nu;
+    double* dst[4] = {x_min, x_max, u_min, u_max};
+    if (b->inst_bounds) {
+        HIP_TRY(b, hipSetDevice(b->device));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        for (int i = 0; i < 4; ++i) {
+            const size_t n = i < 2 ? ns : ni;
+            if (dst[i]) HIP_TRY(b, hipMemcpy(dst[i], b->d_ib_src[i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return TINY_OK;
+    }
+    const std::vector<double>* shared[4] = {&b->x_min, &b->x_max, &b->u_min, &b->u_max};
+    for (int i = 0; i < 4; ++i) {
+        if (!dst[i]) continue;
+        const size_t n = i < 2 ? ns : ni;
+        const double none = (i & 1) ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity();
+        for (size_t e = 0; e < n; ++e) dst[i][e] = b->have_bounds ? (*shared[i])[e] : none;      // (never set: (-inf, +inf))
+    }
     return TINY_OK;
 }
 
@@ -421,6 +479,7 @@ int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_
     b->set.en_state_linear = en_state_linear; b->set.en_input_linear = en_input_linear;
     b->set.en_tv_state_linear = en_tv_state_linear; b->set.en_tv_input_linear = en_tv_input_linear;
     b->tab_dirty = true;
+    if (b->inst_bounds) b->inst_bounds_dirty = true;   // (a disabled family is (-inf, +inf) in the array the kernels read)
     return TINY_OK;
 }
 
@@ -1010,6 +1069,8 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_half_rows")) return b->last_half ? 1 : 0;       // the last one-row launch took the HALF form (two instances per DPP row)
     if (!strcmp(name, "last_tile_form")) return b->last_tile_form;          // W * 1e6 + R * 1e3 + LM of the tile_dims.txt entry the last tile launch took (-1: run-time instantiated)
     if (!strcmp(name, "last_tile_dyn")) return b->last_tile_dyn ? 1 : 0;      // the last tile-kernel launch took the dynamic slot form
+    if (!strcmp(name, "instance_bounds")) return b->inst_bounds ? 1 : 0;        // a per-instance box is installed (tiny_batch_set_instance_bounds)
+    if (!strcmp(name, "last_instance_bounds")) return b->last_inst_bounds ? 1 : 0;   // the last solve's kernel read a per-instance box
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;
@@ -1145,7 +1206,7 @@ int tiny_batch_kernel_path(TinyBatch* b) {
     if (!b) return TINY_ERR_NULL;
     if (use_tile(b)) return b->tile_is_jit ? 4 : 1;
     if (use_general(b)) return 2;
-    return b->kernel ? 0 : 3;                          // 3: the one-row kernel, instantiated at run time
+    return (b->kernel && !b->inst_bounds) ? 0 : 3;     // 3: the one-row kernel, instantiated at run time (every form with a per-instance box is)
 }
 
 long tiny_batch_algorithmic_bytes(TinyBatch* b, int cold) {

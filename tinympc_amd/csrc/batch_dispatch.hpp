@@ -31,6 +31,7 @@ int ensure_repack_buffers(TinyBatch* b);
 int ensure_regroup_buffers(TinyBatch* b, bool second_stream);
 int ensure_adaptive(TinyBatch* b, bool need_tables = true);
 int adaptive_fresh_state(TinyBatch* b);
+int ensure_instance_bounds(TinyBatch* b);   // the per-instance box the kernels read, rebuilt from the caller's arrays when it is out of date (synchronous then)
 // ---- lane tables (batch_tables.hip)
 bool box_is_uniform(const TinyBatch* b);     // the box is the same at every knot: the one place that decides it
 int lin_kmax(const TinyBatch* b);       // half-spaces per knot and family the LIN variants are built for (4, 8, 16, 32; 0: coverage kernel)

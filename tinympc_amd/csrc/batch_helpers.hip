@@ -119,6 +119,50 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
     return TINY_OK;
 }
 
+// ---- every instance its own box (tiny_batch_set_instance_bounds): the caller's arrays -> [batch][lo | hi][N slots][lw lanes], one thread
+// per (instance, slot, lane); which element lands there: box_entry (lane_tables.hpp), nothing else.  The same pass reduces ONE flag,
+// box_is_uniform's rule over every instance: an enabled entry that differs from its family's first knot (slot 0 of a state lane, slot 1 of
+// an input lane) -- or is a NaN, which differs from itself -- makes the batch not uniform
+static __global__ __launch_bounds__(256) void fill_instance_bounds_kernel(double* __restrict__ out, const double* __restrict__ x_min, const double* __restrict__ x_max,
+                                                                          const double* __restrict__ u_min, const double* __restrict__ u_max, int batch, int nx, int nu,
+                                                                          int N, int lw, int state_on, int input_on, int* __restrict__ not_uniform) {
+    const size_t total = (size_t)batch * N * lw;
+    bool differs = false;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % lw), slot = (int)((e / lw) % N);
+        const size_t b = e / ((size_t)N * lw);
+        const double *xl = x_min + b * N * nx, *xh = x_max + b * N * nx, *ul = u_min + b * (N - 1) * nu, *uh = u_max + b * (N - 1) * nu;
+        const BoxEntry v = box_entry(xl, xh, ul, uh, nx, nu, slot, lane, state_on != 0, input_on != 0);
+        out[(b * 2 * N + slot) * lw + lane] = v.lo;
+        out[(b * 2 * N + N + slot) * lw + lane] = v.hi;
+        const int family = box_source(nx, nu, slot, lane, state_on != 0, input_on != 0).family;
+        if (family >= 0) {
+            const BoxEntry first = box_entry(xl, xh, ul, uh, nx, nu, family == 0 ? 0 : 1, lane, state_on != 0, input_on != 0);
+            differs |= (v.lo != first.lo) | (v.hi != first.hi);
+        }
+    }
+    if (differs) atomicOr(not_uniform, 1);
+}
+int ensure_instance_bounds(TinyBatch* b) {
+    if (!b->inst_bounds || !b->inst_bounds_dirty) return TINY_OK;
+    const int lw = box_lanes(b->nx, b->nu);
+    const size_t total = (size_t)b->batch * b->N * lw;
+    if (!b->d_inst_bounds) HIP_TRY(b, hipMalloc(&b->d_inst_bounds, 2 * total * sizeof(double)));
+    if (!b->d_ib_flag) HIP_TRY(b, hipMalloc(&b->d_ib_flag, sizeof(int)));
+    HIP_TRY(b, hipMemsetAsync(b->d_ib_flag, 0, sizeof(int), b->stream));
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
+    hipLaunchKernelGGL(fill_instance_bounds_kernel, dim3(grid), dim3(256), 0, b->stream, b->d_inst_bounds, b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2],
+                       b->d_ib_src[3], b->batch, b->nx, b->nu, b->N, lw, b->set.en_state_bound ? 1 : 0, b->set.en_input_bound ? 1 : 0, b->d_ib_flag);
+    HIP_TRY(b, hipGetLastError());
+    int not_uniform = 1;
+    HIP_TRY(b, hipMemcpyAsync(&not_uniform, b->d_ib_flag, sizeof(int), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    b->inst_bounds_uniform = b->N >= 2 && not_uniform == 0;
+    b->inst_bounds_dirty = false;
+    b->tab_dirty = true;                              // (the UB decision rides on the lane table's flag: box_is_uniform)
+    return TINY_OK;
+}
+
 // histogram of the iteration counts the solve just enqueued leaves in d_status -> pinned host memory, asynchronously (hist_ev)
 int enqueue_iteration_histogram(TinyBatch* b) {
     if (!b->d_hist) {

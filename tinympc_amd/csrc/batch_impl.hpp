@@ -113,6 +113,15 @@ struct TinyBatch {
     bool use_ub = true;                            // option "uniform_bounds": take the UB kernel variant when the box allows it
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
+    // every instance its own box (tiny_batch_set_instance_bounds): the caller's four arrays as given (d_ib_src: x_min, x_max [batch][N][nx],
+    // u_min, u_max [batch][N-1][nu]) and what the kernels read, built from them by batch_helpers.hip: d_inst_bounds [batch][lo | hi][N][box_lanes]
+    // (lane_tables.hpp box_entry; rebuilt when the box or an enable switch changes: inst_bounds_dirty).  inst_bounds_uniform: EVERY
+    // instance's box is knot-invariant for the enabled families (box_is_uniform's rule, reduced by the same kernel) -- the UB forms
+    bool inst_bounds = false, inst_bounds_dirty = false, inst_bounds_uniform = false;
+    bool last_inst_bounds = false;                 // the last solve's kernel read a per-instance box
+    double* d_ib_src[4] = {nullptr, nullptr, nullptr, nullptr};
+    double* d_inst_bounds = nullptr;
+    int* d_ib_flag = nullptr;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

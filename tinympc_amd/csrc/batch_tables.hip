@@ -39,6 +39,7 @@ int lin_kmax(const TinyBatch* b) {
 // (-inf, +inf) everywhere; every knot is compared with knot 0, knot 0 included: a NaN bound equals nothing and is not uniform
 bool box_is_uniform(const TinyBatch* b) {
     if (b->N < 2) return false;
+    if (b->inst_bounds) return b->inst_bounds_uniform;   // (the same rule over every instance's box, reduced on the device: batch_helpers.hip)
     if (!b->have_bounds) return true;
     auto same = [](const std::vector<double>& v, int knots, int n) {
         for (int i = 0; i < knots; ++i)
@@ -131,15 +132,16 @@ static void fill_lane_tables(TinyBatch* b, const LaneTab T, std::vector<double>&
             fill(blk, b->ntil, b->tvA_u.data() + (size_t)(s - 1) * b->ntil * nu, b->tvb_u.data() + (size_t)(s - 1) * b->ntil, nu, nx, b->set.en_tv_input_linear);
     }
     // bounds (admm.cpp:91-98): a disabled or never-set box is (-inf, +inf)
+    // (which element lands in which slot and lane: box_entry, lane_tables.hpp -- the rule of the per-instance box, too; with one of
+    // those installed this block is not read)
     double* lo = &t[T.BOUNDS()];
     double* hi = lo + N * lw;
-    for (int e = 0; e < N * lw; ++e) { lo[e] = -inf; hi[e] = inf; }
-    if (b->set.en_state_bound && b->have_bounds)
-        for (int i = 0; i < N; ++i)
-            for (int j = 0; j < nx; ++j) { lo[i * lw + j] = b->x_min[(size_t)i * nx + j]; hi[i * lw + j] = b->x_max[(size_t)i * nx + j]; }
-    if (b->set.en_input_bound && b->have_bounds)     // input lanes keep knot i in slot i+1 (admm_kernel.hip.h); their slot 0 is a dummy
-        for (int i = 0; i < N - 1; ++i)
-            for (int a = 0; a < nu; ++a) { lo[(i + 1) * lw + nx + a] = b->u_min[(size_t)i * nu + a]; hi[(i + 1) * lw + nx + a] = b->u_max[(size_t)i * nu + a]; }
+    const bool state_on = b->set.en_state_bound && b->have_bounds, input_on = b->set.en_input_bound && b->have_bounds;
+    for (int s = 0; s < N; ++s)
+        for (int j = 0; j < lw; ++j) {
+            const BoxEntry e = box_entry(b->x_min.data(), b->x_max.data(), b->u_min.data(), b->u_max.data(), nx, nu, s, j, state_on, input_on);
+            lo[s * lw + j] = e.lo; hi[s * lw + j] = e.hi;
+        }
     b->bounds_uniform = box_is_uniform(b);
 }
 

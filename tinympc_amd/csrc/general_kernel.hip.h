@@ -46,6 +46,10 @@ struct GeneralArgs {
     // matrices at the top of every instance.  null: one family (gtab)
     const double* het_tabs;
     int het_cols, het_lw, het_stride;
+    // every instance its own box: [batch][lo | hi][N slots][ib_lw lanes] in the register kernels' slot convention (lane_tables.hpp
+    // box_entry: row j of knot i sits in slot i + (j >= nx), lane j).  null: the family's box (o_lo / o_hi)
+    const double* inst_bounds;
+    int ib_lw;
 };
 
 // phases of admm_phase_kernel (the batched form of the reference's exported phase functions, admm.hpp:12-17)
@@ -94,6 +98,19 @@ __device__ __forceinline__ void halfspace_inplace(double* z, int n, const double
         const double dist = (cv - b) / nn;
         for (int c = 0; c < n; ++c) { const double pr = dist * a[c]; z[c] = z[c] - pr; }
     }
+}
+
+// the box of (knot i, row j) of instance b: its own (GeneralArgs::inst_bounds) or the family's
+struct GkBox {
+    const double *lo, *hi;
+    int lw, nx, nz;                  // lw > 0: a per-instance block
+    __device__ __forceinline__ double LO(int i, int j) const { return lw ? lo[(i + (j >= nx)) * lw + j] : lo[i * nz + j]; }
+    __device__ __forceinline__ double HI(int i, int j) const { return lw ? hi[(i + (j >= nx)) * lw + j] : hi[i * nz + j]; }
+};
+__device__ __forceinline__ GkBox gk_box(const GeneralArgs& P, const int b) {
+    if (!P.inst_bounds) return {P.gtab + P.o_lo, P.gtab + P.o_hi, 0, P.nx, P.nx + P.nu};
+    const double* ib = P.inst_bounds + (size_t)b * (2 * P.N * P.ib_lw);
+    return {ib, ib + P.N * P.ib_lw, P.ib_lw, P.nx, P.nx + P.nu};
 }
 
 // LDS carve-up shared by the solve kernel and the single-phase kernel
@@ -259,13 +276,12 @@ __global__ __launch_bounds__(64) void admm_general_kernel(const GeneralArgs P) {
     const int nx = P.nx, nu = P.nu, N = P.N, nz = nx + nu, ld = nz + 1;
     GkLds L = gk_carve(P, lds);
     double *sPT = L.sPT, *sPX = L.sPX, *sX = L.sX, *sQR = L.sQR, *sPD = L.sPD;
-    const double* LO = P.gtab + P.o_lo;
-    const double* HI = P.gtab + P.o_hi;
     const bool is_state = lane < nx;
     const int rec_n = N * nz;
 
     for (int b = blockIdx.x; b < P.batch; b += gridDim.x) {
         gk_load_instance(P, L, b, lane, b == (int)blockIdx.x);
+        const GkBox box = gk_box(P, b);
         const double* QR = L.QR;
         const double rho = L.rho;
         const size_t rec = (size_t)b * rec_n;
@@ -332,7 +348,7 @@ __global__ __launch_bounds__(64) void admm_general_kernel(const GeneralArgs P) {
                 if (!st && i == N - 1) continue;
                 const double xv = sX[e];
                 const double t = xv + P.dual[rec + e];
-                const double vn = fmin(HI[i * nz + j], fmax(LO[i * nz + j], t));
+                const double vn = fmin(box.HI(i, j), fmax(box.LO(i, j), t));
                 const double pr = fabs(xv - vn), du = fabs(P.slack_prev[rec + e] - vn);
                 if (st) { m_ps = fmax(m_ps, pr); m_ds = fmax(m_ds, du); }
                 else { m_pi = fmax(m_pi, pr); m_di = fmax(m_di, du); }
@@ -412,11 +428,10 @@ __global__ __launch_bounds__(64) void admm_phase_kernel(const GeneralArgs P, con
     const int lane = threadIdx.x;
     const int nx = P.nx, nu = P.nu, N = P.N, nz = nx + nu, ld = nz + 1;
     GkLds L = gk_carve(P, lds);
-    const double* LO = P.gtab + P.o_lo;
-    const double* HI = P.gtab + P.o_hi;
     const int rec_n = N * nz;
     for (int b = blockIdx.x; b < P.batch; b += gridDim.x) {
         gk_load_instance(P, L, b, lane, b == (int)blockIdx.x);
+        const GkBox box = gk_box(P, b);
         const double* QR = L.QR;
         const double rho = L.rho;
         const size_t rec = (size_t)b * rec_n;
@@ -455,7 +470,7 @@ __global__ __launch_bounds__(64) void admm_phase_kernel(const GeneralArgs P, con
                 if (!st && i == N - 1) continue;
                 const double xv = L.sX[e];
                 const double t = xv + P.dual[rec + e];                                            // :85 / :88
-                P.slack[rec + e] = fmin(HI[i * nz + j], fmax(LO[i * nz + j], t));                 // :91-98 (+-inf when disabled)
+                P.slack[rec + e] = fmin(box.HI(i, j), fmax(box.LO(i, j), t));                     // :91-98 (+-inf when disabled)
                 if (st ? P.soc_s : P.soc_i) P.cslack[rec + e] = xv + P.cdual[rec + e];            // :102-109
                 if (st ? P.lin_s : P.lin_i) P.lslack[rec + e] = xv + P.ldual[rec + e];            // :138-145
                 if (st ? P.tlin_s : P.tlin_i) P.tlslack[rec + e] = xv + P.tldual[rec + e];        // :176-183

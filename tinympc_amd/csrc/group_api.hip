@@ -259,6 +259,28 @@ int tiny_group_set_bound_constraints(TinyGroup* g, const double* x_min, const do
     if (!g) return TINY_ERR_NULL;
     return for_shards(g, [&](TinyBatch* b) { return tiny_batch_set_bound_constraints(b, x_min, x_max, u_min, u_max); });
 }
+// every instance its own box: the full batch axis in host memory, the caller's instance order; each shard gets its instances' boxes
+int tiny_group_set_instance_bounds(TinyGroup* g, const double* x_min, const double* x_max, const double* u_min, const double* u_max) {
+    if (!g) return TINY_ERR_NULL;
+    if (!x_min || !x_max || !u_min || !u_max) return gfail(g, TINY_ERR_NULL, "null bound pointer");
+    const double* src[4] = {x_min, x_max, u_min, u_max};
+    const size_t per[4] = {(size_t)g->N * g->nx, (size_t)g->N * g->nx, (size_t)(g->N - 1) * g->nu, (size_t)(g->N - 1) * g->nu};
+    std::vector<double> stage[4];
+    for (int k = 0; k < g->n; ++k) {
+        const double* from[4];
+        for (int a = 0; a < 4; ++a) {
+            from[a] = src[a] + (size_t)first_of(g, k) * per[a];
+            if (g->interleaved) {
+                stage[a].resize((size_t)g->count[k] * per[a]);
+                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
+                from[a] = stage[a].data();
+            }
+        }
+        if (int rc = tiny_batch_set_instance_bounds(g->shard[k], from[0], from[1], from[2], from[3], TINY_HOST))
+            return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
 int tiny_group_set_cone_constraints(TinyGroup* g, int nsc, const int* Acx, const int* qcx, const double* cx, int nic,
                                     const int* Acu, const int* qcu, const double* cu) {
     if (!g) return TINY_ERR_NULL;

@@ -78,4 +78,27 @@ __host__ __device__ inline AtabEntries atab_entries(const V& v, int nx, int nu, 
     return e;
 }
 
+// ---- the box: which element of the caller's bounds lands in (slot, lane) of a bounds block [lo | hi][N slots][lw lanes] -- the block of a
+// lane table (LaneTab::BOUNDS) and every instance's block of a per-instance box (SolveArgs::inst_bounds, GeneralArgs::inst_bounds).
+// State lanes keep knot `slot` in slot `slot`; input lanes keep knot `slot - 1` (their slot 0 is the neutral dummy of the register
+// kernels' slot convention); lanes from nx + nu on, a disabled family and the dummy hold (-inf, +inf).
+// family: 0 x_min | x_max [N][nx], 1 u_min | u_max [N - 1][nu], -1 nothing; index: into that family's arrays
+struct BoxSource { int family, index; };
+__host__ __device__ inline BoxSource box_source(int nx, int nu, int slot, int lane, bool state_on, bool input_on) {
+    if (lane < nx) return state_on ? BoxSource{0, slot * nx + lane} : BoxSource{-1, 0};
+    if (lane < nx + nu && slot >= 1 && input_on) return BoxSource{1, (slot - 1) * nu + (lane - nx)};
+    return BoxSource{-1, 0};
+}
+struct BoxEntry { double lo, hi; };
+// ... and the pair it holds (the four arrays: one instance's, or the family's)
+__host__ __device__ inline BoxEntry box_entry(const double* x_min, const double* x_max, const double* u_min, const double* u_max, int nx, int nu, int slot, int lane,
+                                              bool state_on, bool input_on) {
+    const BoxSource s = box_source(nx, nu, slot, lane, state_on, input_on);
+    if (s.family == 0) return {x_min[s.index], x_max[s.index]};
+    if (s.family == 1) return {u_min[s.index], u_max[s.index]};
+    return {-__builtin_huge_val(), __builtin_huge_val()};
+}
+// lanes of a per-instance bounds block: whole DPP rows (16 for the shapes of the one-row kernel, 32 for the wide ones of the coverage kernel)
+__host__ __device__ constexpr int box_lanes(int nx, int nu) { return 16 * ((nx + nu + 15) / 16); }
+
 }  // namespace tinympc_amd
