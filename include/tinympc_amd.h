@@ -152,6 +152,34 @@ int tiny_batch_set_linear_constraints(TinyBatch* b, int n_state, const double* A
  * n_state x N; tv_Alin_u (n_input*(N-1)) x nu, tv_blin_u n_input x (N-1). */
 int tiny_batch_set_tv_linear_constraints(TinyBatch* b, int n_state, const double* tv_Alin_x, const double* tv_blin_x,
                                          int n_input, const double* tv_Alin_u, const double* tv_blin_u);
+/* every instance its own half-spaces: every array is the shared setter's array with a leading batch axis -- instance i's block has
+ * exactly the shape and column-major layout documented above (static: Alin_x [batch][n_state x nx], blin_x [batch][n_state]; time-varying:
+ * tv_Alin_x [batch][(n_state*N) x nx], tv_blin_x [batch][n_state x N], the inputs likewise over N-1 knots).  The counts (per knot for the
+ * time-varying set) are the same for all instances: an instance that needs fewer half-spaces pads with a row of zeros and b = +inf, which
+ * is inert (cv = 0 > +inf is false).  flags: TINY_HOST or TINY_DEVICE (copied; the caller may free); TINY_BROADCAST is TINY_ERR_ARG (one
+ * set for all: the shared setters above).  The latest setter wins, per set: the static and the time-varying set are independent, one may be
+ * per instance while the other is shared; a later shared setter of the same set replaces the per-instance one and frees its arrays.  A
+ * failed call leaves what was installed.  The en_*_linear switches act as on shared sets; tiny_batch_reset leaves the constraints alone.
+ * Works on tiny_batch_setup and tiny_batch_setup_hetero batches.
+ * Offsets-only update (the closed-loop pattern: only b moves from step to step): with a per-instance set of the same counts installed, a
+ * NULL coefficient array keeps that family's coefficients and rewrites only its offsets -- when every family with a positive count passes
+ * NULL, nothing is uploaded or squared again but the offsets; NULL with nothing installed, or with other counts, is TINY_ERR_ARG.
+ * Read-backs (tiny_batch_get_option): "instance_linear" is a bit mask, 1 static, 2 time-varying, of the sets installed per instance;
+ * "last_instance_linear" the same mask for what the last solve's kernel read.
+ * Where it runs: the one-row kernel's PL forms (run-time instantiated, at KMAX = the smallest power of two that holds the enabled counts,
+ * 1 and 2 included; tiny_batch_kernel_path 3) for the shapes that kernel holds, with a disjoint cone, per-instance problem data and every
+ * launch form of those, where the slack planes and the four rows' tables fit a wave's LDS; the coverage kernel -- correct, not fast,
+ * tiny_batch_kernel_path says so -- for tile-kernel shapes (nx + nu > 16 or a horizon beyond the one-row kernel), planes that do not fit
+ * (long horizons with a time-varying set), cones that share rows, a per-instance box at the same time, "debug", "force_general", "no_jit"
+ * or a missing hipRTC.  Adaptive rho fails the solve with TINY_ERR_UNSUPPORTED, as it does with shared half-spaces.  Out of scope: the tile
+ * kernel, tiny_codegen, tiny_solve_batch and the drop-in structs (which go on taking one set for all solvers). */
+int tiny_batch_set_instance_linear_constraints(TinyBatch* b, int n_state, const double* Alin_x, const double* blin_x,
+                                               int n_input, const double* Alin_u, const double* blin_u, int flags);
+int tiny_batch_set_instance_tv_linear_constraints(TinyBatch* b, int n_state, const double* tv_Alin_x, const double* tv_blin_x,
+                                                  int n_input, const double* tv_Alin_u, const double* tv_blin_u, int flags);
+/* what instance `instance` is held to by the static (tv = 0) or the time-varying (tv = 1) set, as set (whatever the enable switches say),
+ * in the shared setter's layout; on a shared set: the shared one.  any pointer may be NULL */
+int tiny_batch_get_instance_linear_constraints(TinyBatch* b, int instance, int tv, double* A_x, double* b_x, double* A_u, double* b_u);
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -421,6 +449,11 @@ int tiny_group_set_linear_constraints(TinyGroup* g, int n_state, const double* A
                                       int n_input, const double* Alin_u, const double* blin_u);
 int tiny_group_set_tv_linear_constraints(TinyGroup* g, int n_state, const double* tv_Alin_x, const double* tv_blin_x,
                                          int n_input, const double* tv_Alin_u, const double* tv_blin_u);
+/* every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): host, full batch axis, caller order */
+int tiny_group_set_instance_linear_constraints(TinyGroup* g, int n_state, const double* Alin_x, const double* blin_x,
+                                               int n_input, const double* Alin_u, const double* blin_u);
+int tiny_group_set_instance_tv_linear_constraints(TinyGroup* g, int n_state, const double* tv_Alin_x, const double* tv_blin_x,
+                                                  int n_input, const double* tv_Alin_u, const double* tv_blin_u);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

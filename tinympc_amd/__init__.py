@@ -39,6 +39,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_device_count", "tiny_batch_setup", "tiny_batch_setup_hetero", "tiny_batch_get_cache_instance",
     "tiny_batch_destroy", "tiny_batch_set_bound_constraints", "tiny_batch_set_instance_bounds", "tiny_batch_get_instance_bounds",
     "tiny_batch_set_cone_constraints", "tiny_batch_set_linear_constraints", "tiny_batch_set_tv_linear_constraints",
+    "tiny_batch_set_instance_linear_constraints", "tiny_batch_set_instance_tv_linear_constraints", "tiny_batch_get_instance_linear_constraints",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -50,7 +51,8 @@ BATCH_SYMBOLS = (
 GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
-    "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_update_settings",
+    "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -169,6 +171,9 @@ def lib():
         L.tiny_batch_set_cone_constraints.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp]
         L.tiny_batch_set_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_batch_set_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
+        L.tiny_batch_set_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -231,6 +236,8 @@ def lib():
         L.tiny_group_set_cone_constraints.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp]
         L.tiny_group_set_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
+        L.tiny_group_set_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
+        L.tiny_group_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.tiny_group_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -430,6 +437,57 @@ class TinyBatchSolver:
         self._check(lib().tiny_batch_set_tv_linear_constraints(self._h, bx.shape[0], a[0].ctypes.data_as(_dp), a[1].ctypes.data_as(_dp),
                                                                bu.shape[0], a[2].ctypes.data_as(_dp), a[3].ctypes.data_as(_dp)),
                     "set_tv_linear_constraints")
+
+    def _instance_halfspaces(self, tv, A_x, b_x, A_u, b_u):
+        """[batch, rows, n] coefficients (None: keep them, the offsets-only update), [batch, n_s(, knots)] offsets -> (n_s, n_i, the four
+        flat arrays with a leading batch axis, per instance column-major as the shared setter takes them; None stays None)"""
+        ks, ki = (self.N, self.N - 1) if tv else (1, 1)
+        bx = np.asarray(b_x, dtype=np.float64).reshape(self.batch, -1, ks)
+        bu = np.asarray(b_u, dtype=np.float64).reshape(self.batch, -1, ki)
+        ns, ni = bx.shape[1], bu.shape[1]
+        col = lambda v, rows, n: None if v is None else np.ascontiguousarray(
+            np.asarray(v, dtype=np.float64).reshape(self.batch, rows, n).transpose(0, 2, 1)).ravel()
+        return ns, ni, [col(A_x, ns * ks, self.nx), np.ascontiguousarray(bx.transpose(0, 2, 1)).ravel(),
+                        col(A_u, ni * ki, self.nu), np.ascontiguousarray(bu.transpose(0, 2, 1)).ravel()]
+
+    def _set_instance_halfspaces(self, tv, A_x, b_x, A_u, b_u, what):
+        ns, ni, a = self._instance_halfspaces(tv, A_x, b_x, A_u, b_u)
+        p = [None if v is None else v.ctypes.data_as(C.c_void_p) for v in a]
+        f = lib().tiny_batch_set_instance_tv_linear_constraints if tv else lib().tiny_batch_set_instance_linear_constraints
+        self._check(f(self._h, ns, p[0], p[1], ni, p[2], p[3], HOST), what)
+
+    def set_instance_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
+        """every instance its own static half-spaces: Alin_x [batch, n_s, nx], blin_x [batch, n_s], Alin_u [batch, n_i, nu], blin_u
+        [batch, n_i].  Alin_x / Alin_u = None: keep the installed coefficients, rewrite the offsets only."""
+        self._set_instance_halfspaces(0, Alin_x, blin_x, Alin_u, blin_u, "set_instance_linear_constraints")
+
+    def set_instance_tv_linear_constraints(self, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u):
+        """every instance its own time-varying half-spaces: tv_Alin_x [batch, n_s*N, nx] (row n_s*i+k = constraint k at knot i), tv_blin_x
+        [batch, n_s, N], tv_Alin_u [batch, n_i*(N-1), nu], tv_blin_u [batch, n_i, N-1].  None coefficients: the offsets-only update."""
+        self._set_instance_halfspaces(1, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u, "set_instance_tv_linear_constraints")
+
+    def set_instance_linear_constraints_device(self, n_state, Alin_x, blin_x, n_input, Alin_u, blin_u):
+        """the same from device pointers (ints; 0: none) to the arrays in the C layout, resident in HBM (copied)"""
+        p = [C.c_void_p(int(v)) if v else None for v in (Alin_x, blin_x, Alin_u, blin_u)]
+        self._check(lib().tiny_batch_set_instance_linear_constraints(self._h, int(n_state), p[0], p[1], int(n_input), p[2], p[3], DEVICE),
+                    "set_instance_linear_constraints_device")
+
+    def set_instance_tv_linear_constraints_device(self, n_state, tv_Alin_x, tv_blin_x, n_input, tv_Alin_u, tv_blin_u):
+        p = [C.c_void_p(int(v)) if v else None for v in (tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u)]
+        self._check(lib().tiny_batch_set_instance_tv_linear_constraints(self._h, int(n_state), p[0], p[1], int(n_input), p[2], p[3], DEVICE),
+                    "set_instance_tv_linear_constraints_device")
+
+    def instance_linear_constraints(self, i, tv=0):
+        """(A_x, b_x, A_u, b_u) instance i is held to by the static (tv = 0) or time-varying (tv = 1) set, as set, in the shapes the
+        shared setters take; on a shared set: the shared one"""
+        ns = self.get_option("n_tv_state_linear" if tv else "n_state_linear")
+        ni = self.get_option("n_tv_input_linear" if tv else "n_input_linear")
+        ks, ki = (self.N, self.N - 1) if tv else (1, 1)
+        out = [np.zeros((self.nx, ns * ks)), np.zeros((ks, ns)), np.zeros((self.nu, ni * ki)), np.zeros((ki, ni))]
+        self._check(lib().tiny_batch_get_instance_linear_constraints(self._h, int(i), int(tv), *[v.ctypes.data_as(_dp) for v in out]),
+                    "instance_linear_constraints")
+        Ax, bx, Au, bu = (v.T.copy() for v in out)
+        return (Ax, bx, Au, bu) if tv else (Ax, bx.ravel(), Au, bu.ravel())
 
     def update_settings(self, abs_pri_tol=1e-3, abs_dua_tol=1e-3, max_iter=1000, check_termination=1,
                         en_state_bound=1, en_input_bound=1, en_state_soc=0, en_input_soc=0, en_state_linear=0,
@@ -732,6 +790,19 @@ class TinyGroupSolver:
         """every instance its own box, the full batch axis in the caller's order: [batch, nx, N] x 2, [batch, nu, N-1] x 2"""
         a = TinyBatchSolver._instance_boxes(self, x_min, x_max, u_min, u_max)
         self._check(lib().tiny_group_set_instance_bounds(self._h, *[v.ctypes.data_as(_dp) for v in a]), "set_instance_bounds")
+
+    def _set_instance_halfspaces(self, tv, A_x, b_x, A_u, b_u, what):
+        ns, ni, a = TinyBatchSolver._instance_halfspaces(self, tv, A_x, b_x, A_u, b_u)
+        p = [None if v is None else v.ctypes.data_as(_dp) for v in a]
+        f = lib().tiny_group_set_instance_tv_linear_constraints if tv else lib().tiny_group_set_instance_linear_constraints
+        self._check(f(self._h, ns, p[0], p[1], ni, p[2], p[3]), what)
+
+    def set_instance_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
+        """every instance its own static half-spaces, the full batch axis in the caller's order (TinyBatchSolver's shapes)"""
+        self._set_instance_halfspaces(0, Alin_x, blin_x, Alin_u, blin_u, "set_instance_linear_constraints")
+
+    def set_instance_tv_linear_constraints(self, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u):
+        self._set_instance_halfspaces(1, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u, "set_instance_tv_linear_constraints")
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         ai = lambda v: np.ascontiguousarray(v, dtype=np.int32)

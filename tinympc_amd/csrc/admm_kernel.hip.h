@@ -32,7 +32,7 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box; see
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces; see
 //     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
@@ -195,12 +195,18 @@ struct SolveArgs {
     // one-row kernel, PB forms: every instance its own box -- [batch][lo | hi][N slots][16 lanes], the slot convention of the shared table's
     // bounds block (lane_tables.hpp box_entry; built by batch_helpers.hip from the caller's arrays).  PB and PF exclude each other, so the
     // pointer takes the place of the PREFETCH form's ticket counters: the argument block of every other form keeps its size and offsets
+    // PL forms: every instance its own half-spaces -- [batch][the blocks of the form's LIN sets: static [3][KMAX][16], then [N][3][KMAX][16]]
+    // (lane_tables.hpp halfspace_entry; built by batch_helpers.hip).  PL excludes PF and PB alike, so it shares their place
     union {
         unsigned* pf_counter;
         const double* inst_bounds;
+        const double* inst_lin;
     };
     unsigned pf_base[8];
 };
+// (the PB / PL pointers share the ticket counters' place: the argument block every compiled-in form was built against stays what it was)
+static_assert(sizeof(SolveArgs) == 472 && __builtin_offsetof(SolveArgs, het_tabs) == 208 && __builtin_offsetof(SolveArgs, pf_mask) == 416 &&
+              __builtin_offsetof(SolveArgs, pf_counter) == 432 && __builtin_offsetof(SolveArgs, pf_base) == 440, "SolveArgs: size and offsets are fixed");
 
 // ---- DPP row-broadcast FMA blocks ------------------------------------------------------------
 // One asm statement per block so that the two wait states a DPP read needs after a VALU write of
@@ -669,20 +675,21 @@ constexpr int solve_kernel_waves_per_simd(int nz, int n, bool soc, bool lin = fa
 #define TINYMPC_LIN_WAVES 0                        // (experiments: 1 / 2 instead of the rule)
 #endif
 // static LDS of a half-space variant with its slack planes: the tables, two planes per set, the cone slack's three, Pinf', the bounds
-constexpr long solve_kernel_lin_lds(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub) {
-    const int nz = nx + nu, csl = (nz + 1) | 1, cs = (nz + 1) | 1;
-    return 8L * (nx * 16 + (ub ? 2 : 2 * n * 16) + ((lin & 1) ? 3 * kmax * 16 + 2 * 4 * n * csl : 0) +
-                 ((lin & 2) ? 3 * n * kmax * 16 + 2 * 4 * n * csl : 0) + (soc ? (4 * n + 1) * 3 * cs : 0));
+// (pl: the tables are per-ROW quantities -- every instance its own half-spaces --, one copy for each of the wave's four rows)
+constexpr long solve_kernel_lin_lds(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub, bool pl = false) {
+    const int nz = nx + nu, csl = (nz + 1) | 1, cs = (nz + 1) | 1, tabs = pl ? 4 : 1;
+    return 8L * (nx * 16 + (ub ? 2 : 2 * n * 16) + ((lin & 1) ? tabs * 3 * kmax * 16 + 2 * 4 * n * csl : 0) +
+                 ((lin & 2) ? tabs * 3 * n * kmax * 16 + 2 * 4 * n * csl : 0) + (soc ? (4 * n + 1) * 3 * cs : 0));
 }
 // ... which must fit a wave's 64 KiB of static LDS; a variant whose planes do not (long horizons with time-varying tables) keeps its
 // slacks in register arrays and projects per knot, as every half-space variant did before round 4 (one wave per SIMD)
-constexpr bool solve_kernel_lin_planes(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub) {
-    return lin != 0 && solve_kernel_lin_lds(nx, nu, n, soc, lin, kmax, ub) <= 64 * 1024 - 512;
+constexpr bool solve_kernel_lin_planes(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub, bool pl = false) {
+    return lin != 0 && solve_kernel_lin_lds(nx, nu, n, soc, lin, kmax, ub, pl) <= 64 * 1024 - 512;
 }
-constexpr int solve_kernel_lin_waves(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub) {
-    if (!solve_kernel_lin_planes(nx, nu, n, soc, lin, kmax, ub)) return 1;
+constexpr int solve_kernel_lin_waves(int nx, int nu, int n, bool soc, int lin, int kmax, bool ub, bool pl = false) {
+    if (!solve_kernel_lin_planes(nx, nu, n, soc, lin, kmax, ub, pl)) return 1;
     if (TINYMPC_LIN_WAVES > 0) return TINYMPC_LIN_WAVES;
-    return (solve_kernel_waves_per_simd(nx + nu, n, soc) == 2 && 8 * solve_kernel_lin_lds(nx, nu, n, soc, lin, kmax, ub) <= 158 * 1024) ? 2 : 1;
+    return (solve_kernel_waves_per_simd(nx + nu, n, soc) == 2 && 8 * solve_kernel_lin_lds(nx, nu, n, soc, lin, kmax, ub, pl) <= 158 * 1024) ? 2 : 1;
 }
 // One lane projects whole (knot, family) columns of a half-space slack: column c of instance `inst`, rows [R0, R0 + NF) -- the cells
 // pv[(inst * n + c) * csl + R0 ...] hold x + gl; the family's half-spaces are applied one after the other, only when violated
@@ -732,15 +739,31 @@ __device__ __forceinline__ void project_halfspace_columns(const int t, const int
 // HET and every MODE.  Instantiated at run time only (jit.hip).  The flag travels as bit 2 of the sixth template argument (MODE_PB =
 // MODE | 4): a template parameter of its own, even one with a default, would lengthen the mangled name of EVERY instantiation, and those
 // names are what the registry, the register-budget tests and tools/isa_diff.py know the compiled-in kernels by.
+// PL: every instance its own half-spaces (SolveArgs::inst_lin) -- sLin / sTLin are per-ROW tables: one block per row of the wave, filled
+// at the top of every tile by the row's own lanes from the instance's blocks; project_halfspace_columns takes the row's base instead of
+// the wave's, the sweeps and the iteration loop are the shared form's.  LIN != 0 on the slack-plane form only (solve_kernel_lin_planes
+// with the four rows' tables -- which is why these forms are instantiated at KMAX 1 and 2 as well: four [N][3][4][16] tables at N = 10
+// are 61 KB); with SOC, HET and every launch form; not HALF, PF, ADAPT or PB.  Run-time instantiated only; bit 3 of the sixth template
+// argument (MODE | 8), for the reason given at PB.
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
-__attribute__((amdgpu_waves_per_eu(LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT),
-                                   LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT))))
+__attribute__((amdgpu_waves_per_eu(LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB, (MODE_PB & 8) != 0) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT),
+                                   LIN != 0 ? solve_kernel_lin_waves(NX, NU, N, SOC, LIN, KMAX, UB, (MODE_PB & 8) != 0) : solve_kernel_waves_per_simd(NX + NU, N, SOC, false, ADAPT))))
 void admm_solve_kernel(const SolveArgs P) {
     constexpr int MODE = MODE_PB & 3;
     constexpr bool PB = (MODE_PB & 4) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 8, "MODE 0 | 1 | 2, + 4: per-instance box");
+    constexpr bool PL = (MODE_PB & 8) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 16, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces");
+    static_assert(!PL || LIN != 0, "per-instance half-spaces: a half-space variant (LIN != 0)");
+    static_assert(!PL || !HALF, "per-instance half-spaces: not the half-row form");
+    static_assert(!PL || !PF, "per-instance half-spaces: not the prefetch form");
+    static_assert(!PL || !ADAPT, "per-instance half-spaces: not with adaptive rho (refused, as on shared half-spaces)");
+    static_assert(!PL || !PB, "per-instance half-spaces: not with a per-instance box (that combination runs on the coverage kernel)");
+    // the one LDS rule, with the tables counted once per row: a PL form exists where its slack planes and the four rows' tables fit a
+    // wave's static LDS; there is no per-knot register form of it (the dispatcher consults the same rule: coverage kernel otherwise)
+    static_assert(!PL || solve_kernel_lin_planes(NX, NU, N, SOC, LIN, KMAX, UB, true),
+                  "per-instance half-spaces: the slack planes and the four rows' tables must fit the wave's static LDS");
     constexpr bool LS = (LIN & 1) != 0, LT = (LIN & 2) != 0;
     constexpr int NZ = NX + NU;
     static_assert(NZ <= 16, "one instance per 16-lane DPP row");
@@ -772,8 +795,8 @@ void admm_solve_kernel(const SolveArgs P) {
     __shared__ double sPt[NX * 16];
     __shared__ double sLo[UB ? 1 : (PB ? IPW : 1) * N * 16];   // (UB: the two bounds of a lane live in registers, read from the table once;
     __shared__ double sHi[UB ? 1 : (PB ? IPW : 1) * N * 16];   //  PB: one block per row, filled for every tile)
-    __shared__ double sLin[LS ? 3 * KMAX * 16 : 1];
-    __shared__ double sTLin[LT ? 3 * N * KMAX * 16 : 1];
+    __shared__ double sLin[LS ? (PL ? IPW : 1) * 3 * KMAX * 16 : 1];            // (PL: one block per row, filled for every tile from the
+    __shared__ double sTLin[LT ? (PL ? IPW : 1) * 3 * N * KMAX * 16 : 1];       //  row's instance: SolveArgs::inst_lin)
     // SOC: the cone slack lives in LDS, not in registers.  Per row and slot three planes of CS cells (lane j: cell j; the lanes beyond
     // NZ share cell NZ):
     //   W   what the next backward sweep adds to the linear cost: vcnew - gc (admm.cpp:269 | :282 | :295).  Between the forward
@@ -812,8 +835,8 @@ void admm_solve_kernel(const SolveArgs P) {
             const int t = e / (16 * AKC), r = e % (16 * AKC);
             sTab[e] = P.atab[t * 256 + (r % AKC) * 16 + r / AKC];              // ATAB_AT / ATAB_DK / ATAB_DP = 0 / 256 / 512
         }
-    if constexpr (LS) for (int e = lane; e < 3 * KMAX * 16; e += 64) sLin[e] = P.tab[TAB_BOUNDS + 2 * N * 16 + e];
-    if constexpr (LT) for (int e = lane; e < 3 * N * KMAX * 16; e += 64) sTLin[e] = P.tab[TAB_BOUNDS + 2 * N * 16 + 3 * KMAX * 16 + e];
+    if constexpr (LS && !PL) for (int e = lane; e < 3 * KMAX * 16; e += 64) sLin[e] = P.tab[TAB_BOUNDS + 2 * N * 16 + e];
+    if constexpr (LT && !PL) for (int e = lane; e < 3 * N * KMAX * 16; e += 64) sTLin[e] = P.tab[TAB_BOUNDS + 2 * N * 16 + 3 * KMAX * 16 + e];
     for (int e = lane; e < NX * 16; e += 64) sPt[e] = P.tab[TAB_PT + e];
     for (int e = lane; e < N * 16; e += 64) {
         if constexpr (!UB && !PB) {
@@ -890,7 +913,7 @@ void admm_solve_kernel(const SolveArgs P) {
     // ...), read two steps ahead like the cone slack.  The projections are transposed (project_halfspace_columns): a lane holds
     // the box kernel's arrays, nothing per slot but one LDS write, and the variant runs two waves per SIMD.
     // (LSP / LTP: the set's slack in planes; LSR / LTR: in register arrays, projected per knot -- the variant whose planes do not fit)
-    constexpr bool LPL = solve_kernel_lin_planes(NX, NU, N, SOC, LIN, KMAX, UB);
+    constexpr bool LPL = solve_kernel_lin_planes(NX, NU, N, SOC, LIN, KMAX, UB, PL);
     constexpr bool LSP = LS && LPL, LTP = LT && LPL, LSR = LS && !LPL, LTR = LT && !LPL;
     constexpr int CSL = LPL ? ((NZ + 1) | 1) : 1;
     __shared__ double sLV[LSP ? 4 * N * CSL : 1], sLG[LSP ? 4 * N * CSL : 1];
@@ -910,6 +933,9 @@ void admm_solve_kernel(const SolveArgs P) {
     const double lo_u = PB ? 0.0 : P.tab[TAB_BOUNDS + (N > 1 ? 16 : 0) + j], hi_u = PB ? 0.0 : P.tab[TAB_BOUNDS + N * 16 + (N > 1 ? 16 : 0) + j];
     const double lo_u0 = PB ? 0.0 : P.tab[TAB_BOUNDS + j], hi_u0 = PB ? 0.0 : P.tab[TAB_BOUNDS + N * 16 + j];
     const int sbox = PB ? grp * (N * 16) : 0;                  // PB && !UB: this row's block of sLo / sHi
+    // PL: this row's blocks of sLin / sTLin (the shared forms: the wave's one)
+    const double* const rLin = sLin + (PL ? grp * (3 * KMAX * 16) : 0);
+    const double* const rTLin = sTLin + (PL ? grp * (3 * N * KMAX * 16) : 0);
     // (PF: a plain single-step launch over the whole batch -- no index list, no permutation, no trajectory window: those paths are
     // compiled OUT of the form, because a register-returning load on ANY path between a tile's hand-over and its stores makes the
     // compiler wait for the whole VMEM queue at the join, the next tile's pieces included)
@@ -1089,6 +1115,25 @@ void admm_solve_kernel(const SolveArgs P) {
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
                 }
+            }
+            if constexpr (PL) {
+                // the row's own half-space tables, by the row's own lanes: one 128-byte segment per table row, the instance's blocks in
+                // the order the form's sets have them (static, then one per slot).  A row without an instance (a partial last tile) is
+                // not here: it reads nothing
+                constexpr int LBLK = 3 * KMAX * 16;
+                size_t il_at = (size_t)b * ((LS ? LBLK : 0) + (LT ? N * LBLK : 0)) + j;
+                asm volatile("" : "+v"(il_at));
+                const double* il = P.inst_lin + il_at;
+                if constexpr (LS) {
+#pragma unroll
+                    for (int e = 0; e < 3 * KMAX; ++e) sLin[grp * LBLK + e * 16 + j] = il[e * 16];
+                }
+                if constexpr (LT) {
+                    const double* ilt = il + (LS ? LBLK : 0);
+                    for (int e = 0; e < 3 * KMAX * N; ++e) sTLin[grp * (N * LBLK) + e * 16 + j] = ilt[e * 16];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
             }
             if constexpr (ADAPT) {                             // this instance's own rho / Kinf / Pinf (they persist from solve to solve)
                 rho = P.arho[b];
@@ -1406,14 +1451,14 @@ void admm_solve_kernel(const SolveArgs P) {
                             if constexpr (LSR) {
                                 const bool on = lin_lane && (is_state || s >= 1);
                                 double vl = on ? (xi + GL[s]) : 0.0;                    // :139 / :144
-                                vl = halfspaces(vl, sLin, P.n_lin);
+                                vl = halfspaces(vl, rLin, P.n_lin);
                                 GL[s] = on ? ((GL[s] + xi) - vl) : 0.0;                 // :239 / :244
                                 VL[s] = on ? vl : 0.0;
                             }
                             if constexpr (LTR) {
                                 const bool on = tlin_lane && (is_state || s >= 1);
                                 double vt = on ? (xi + GT[s]) : 0.0;                    // :177 / :182
-                                vt = halfspaces(vt, sTLin + s * 3 * KMAX * 16, P.n_tlin);
+                                vt = halfspaces(vt, rTLin + s * 3 * KMAX * 16, P.n_tlin);
                                 GT[s] = on ? ((GT[s] + xi) - vt) : 0.0;                 // :249 / :254
                                 VT[s] = on ? vt : 0.0;
                             }
@@ -1493,12 +1538,12 @@ void admm_solve_kernel(const SolveArgs P) {
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_wave_barrier();
                         if constexpr (LSP) {
-                            if (lin_x_on) project_halfspace_columns<NX, KMAX, 16, 16>(j, grp, N, CSL, 0, 0, sLV, sLG, sLin, 0, P.n_lin);
-                            if (lin_u_on) project_halfspace_columns<NU, KMAX, 16, 16>(j, grp, N, CSL, NX, 1, sLV, sLG, sLin, 0, P.n_lin);
+                            if (lin_x_on) project_halfspace_columns<NX, KMAX, 16, 16>(j, grp, N, CSL, 0, 0, sLV, sLG, rLin, 0, P.n_lin);
+                            if (lin_u_on) project_halfspace_columns<NU, KMAX, 16, 16>(j, grp, N, CSL, NX, 1, sLV, sLG, rLin, 0, P.n_lin);
                         }
                         if constexpr (LTP) {
-                            if (tlin_x_on) project_halfspace_columns<NX, KMAX, 16, 16>(j, grp, N, CSL, 0, 0, sTV, sTG, sTLin, 3 * KMAX * 16, P.n_tlin);
-                            if (tlin_u_on) project_halfspace_columns<NU, KMAX, 16, 16>(j, grp, N, CSL, NX, 1, sTV, sTG, sTLin, 3 * KMAX * 16, P.n_tlin);
+                            if (tlin_x_on) project_halfspace_columns<NX, KMAX, 16, 16>(j, grp, N, CSL, 0, 0, sTV, sTG, rTLin, 3 * KMAX * 16, P.n_tlin);
+                            if (tlin_u_on) project_halfspace_columns<NU, KMAX, 16, 16>(j, grp, N, CSL, NX, 1, sTV, sTG, rTLin, 3 * KMAX * 16, P.n_tlin);
                         }
                         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                         __builtin_amdgcn_wave_barrier();

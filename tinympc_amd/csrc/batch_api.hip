@@ -346,7 +346,8 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_iter_log, b->d_u0_log, b->d_lslack, b->d_ldual, b->d_tlslack, b->d_tldual, b->d_gtab, b->d_traj,
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
-                    b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_il_src[0][0], b->d_il_src[0][1], b->d_il_src[0][2], b->d_il_src[0][3],
+                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
     if (b->h_wire) hipHostFree(b->h_wire);
@@ -480,6 +481,7 @@ int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_
     b->set.en_tv_state_linear = en_tv_state_linear; b->set.en_tv_input_linear = en_tv_input_linear;
     b->tab_dirty = true;
     if (b->inst_bounds) b->inst_bounds_dirty = true;   // (a disabled family is (-inf, +inf) in the array the kernels read)
+    b->il_full = true;                                 // (... and blank in a per-instance set's blocks, whose stride follows the enabled counts)
     return TINY_OK;
 }
 
@@ -490,11 +492,119 @@ static void rows_of(const double* colmajor, int n, int cols, std::vector<double>
         for (int c = 0; c < cols; ++c) (*out)[(size_t)k * cols + c] = colmajor[(size_t)c * n + k];
 }
 
+// a shared setter of set `set` (0 static, 1 time-varying) is about to install one set for all: a per-instance set goes, its arrays
+// freed once the stream has run dry of their readers; the other set, if it is per instance, has its blocks rebuilt (they hold both)
+static int drop_instance_linear(TinyBatch* b, int set) {
+    if (b->inst_lin[set]) {
+        HIP_TRY(b, hipSetDevice(b->device));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        for (double*& p : b->d_il_src[set]) { if (p) (void)hipFree(p); p = nullptr; }
+        b->inst_lin[set] = false;
+        if (!b->inst_lin[1 - set]) {
+            if (b->d_inst_lin) (void)hipFree(b->d_inst_lin);
+            if (b->d_il_stage) (void)hipFree(b->d_il_stage);
+            b->d_inst_lin = nullptr; b->d_il_stage = nullptr; b->il_doubles = 0; b->il_stage_doubles = 0;
+        }
+    }
+    b->il_full = true; b->il_offsets = 0;
+    return TINY_OK;
+}
+
+// every instance its own half-spaces, set 0 (static) or 1 (time-varying).  The caller's arrays are kept on the device as given; what
+// the kernels read is built from them in front of the next launch (ensure_instance_linear).  Everything that can fail -- the checks,
+// the allocations, the copies -- happens before anything installed is touched: a failed call leaves what was installed.
+// A == NULL for every family with a positive count: the offsets-only update (the counts must be the installed ones)
+static int set_instance_linear(TinyBatch* b, int set, int n_state, const double* A_x, const double* b_x, int n_input, const double* A_u, const double* b_u,
+                               int flags) {
+    if (n_state < 0 || n_input < 0) return fail(b, TINY_ERR_DIM, "negative constraint count");
+    if (flags & TINY_BROADCAST)
+        return fail(b, TINY_ERR_ARG, "one set for every instance: %s", set ? "tiny_batch_set_tv_linear_constraints" : "tiny_batch_set_linear_constraints");
+    if ((n_state > 0 && !b_x) || (n_input > 0 && !b_u)) return fail(b, TINY_ERR_NULL, "null offsets with a positive count");
+    const int cnt[2] = {n_state, n_input};
+    const double* src[4] = {A_x, b_x, A_u, b_u};
+    const int have[2] = {set ? b->ntsl : b->nsl, set ? b->ntil : b->nil};
+    bool offsets_only[2];
+    for (int fam = 0; fam < 2; ++fam) {
+        offsets_only[fam] = cnt[fam] > 0 && !src[2 * fam];
+        if (offsets_only[fam] && (!b->inst_lin[set] || have[0] != n_state || have[1] != n_input))
+            return fail(b, TINY_ERR_ARG, "null coefficients: the offsets-only update needs a per-instance set of the same counts installed (%d, %d)", n_state, n_input);
+    }
+    HIP_TRY(b, hipSetDevice(b->device));
+    const size_t knots[2] = {set ? (size_t)b->N : 1, set ? (size_t)b->N - 1 : 1};
+    double* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipError_t err = hipSuccess;
+    for (int i = 0; i < 4 && err == hipSuccess; ++i) {
+        const int fam = i / 2;
+        if (!src[i] || cnt[fam] == 0) continue;
+        const size_t n = (size_t)b->batch * cnt[fam] * knots[fam] * ((i & 1) ? 1 : (fam ? b->nu : b->nx));
+        err = hipMalloc(&fresh[i], std::max<size_t>(n, 1) * sizeof(double));
+        if (err == hipSuccess) err = hipMemcpyAsync(fresh[i], src[i], n * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);      // (the caller may free its arrays; nothing reads the old ones any more)
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        for (double* p : fresh) if (p) (void)hipFree(p);
+        return fail(b, TINY_ERR_HIP, "per-instance half-spaces: %s", hipGetErrorString(err));
+    }
+    for (int i = 0; i < 4; ++i) {
+        if (offsets_only[i / 2] && !(i & 1)) continue;                   // (this family keeps its coefficients)
+        if (b->d_il_src[set][i]) (void)hipFree(b->d_il_src[set][i]);
+        b->d_il_src[set][i] = fresh[i];
+    }
+    const bool all_offsets = (offsets_only[0] || cnt[0] == 0) && (offsets_only[1] || cnt[1] == 0) && (cnt[0] > 0 || cnt[1] > 0);
+    if (all_offsets) b->il_offsets |= ((offsets_only[0] ? 1 : 0) | (offsets_only[1] ? 2 : 0)) << (2 * set);
+    else b->il_full = true;
+    b->inst_lin[set] = true;
+    if (set) { b->ntsl = n_state; b->ntil = n_input; b->tvA_x.clear(); b->tvb_x.clear(); b->tvA_u.clear(); b->tvb_u.clear(); }
+    else { b->nsl = n_state; b->nil = n_input; b->Alin_x.clear(); b->blin_x.clear(); b->Alin_u.clear(); b->blin_u.clear(); }
+    b->tab_dirty = true;
+    return TINY_OK;
+}
+int tiny_batch_set_instance_linear_constraints(TinyBatch* b, int n_state, const double* Alin_x, const double* blin_x, int n_input,
+                                               const double* Alin_u, const double* blin_u, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    return set_instance_linear(b, 0, n_state, Alin_x, blin_x, n_input, Alin_u, blin_u, flags);
+}
+int tiny_batch_set_instance_tv_linear_constraints(TinyBatch* b, int n_state, const double* tv_Alin_x, const double* tv_blin_x, int n_input,
+                                                  const double* tv_Alin_u, const double* tv_blin_u, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    return set_instance_linear(b, 1, n_state, tv_Alin_x, tv_blin_x, n_input, tv_Alin_u, tv_blin_u, flags);
+}
+// what instance `instance` is held to by set `tv` (0 static, 1 time-varying), as set -- whatever the switches say -- in the shared
+// setter's layout; on a shared set: the shared one.  any pointer may be NULL
+int tiny_batch_get_instance_linear_constraints(TinyBatch* b, int instance, int tv, double* A_x, double* b_x, double* A_u, double* b_u) {
+    if (!b) return TINY_ERR_NULL;
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    if (tv != 0 && tv != 1) return fail(b, TINY_ERR_ARG, "set %d: 0 static, 1 time-varying", tv);
+    const int cnt[2] = {tv ? b->ntsl : b->nsl, tv ? b->ntil : b->nil};
+    const size_t rows[2] = {(size_t)cnt[0] * (tv ? b->N : 1), (size_t)cnt[1] * (tv ? b->N - 1 : 1)};
+    double* dst[4] = {A_x, b_x, A_u, b_u};
+    if (b->inst_lin[tv]) {
+        HIP_TRY(b, hipSetDevice(b->device));
+        HIP_TRY(b, hipStreamSynchronize(b->stream));
+        for (int i = 0; i < 4; ++i) {
+            const size_t n = rows[i / 2] * ((i & 1) ? 1 : (i / 2 ? b->nu : b->nx));
+            if (dst[i] && n) HIP_TRY(b, hipMemcpy(dst[i], b->d_il_src[tv][i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
+        }
+        return TINY_OK;
+    }
+    const std::vector<double>* shared[4] = {tv ? &b->tvA_x : &b->Alin_x, tv ? &b->tvb_x : &b->blin_x, tv ? &b->tvA_u : &b->Alin_u, tv ? &b->tvb_u : &b->blin_u};
+    for (int i = 0; i < 4; ++i) {
+        if (!dst[i]) continue;
+        const size_t r = rows[i / 2], cols = i / 2 ? b->nu : b->nx;
+        if (i & 1) { for (size_t k = 0; k < r; ++k) dst[i][k] = (*shared[i])[k]; }
+        else for (size_t k = 0; k < r; ++k)                                 // (the host copies are row-major: rows_of)
+            for (size_t c = 0; c < cols; ++c) dst[i][c * r + k] = (*shared[i])[k * cols + c];
+    }
+    return TINY_OK;
+}
+
 int tiny_batch_set_linear_constraints(TinyBatch* b, int n_state, const double* Alin_x, const double* blin_x, int n_input,
                                       const double* Alin_u, const double* blin_u) {
     if (!b) { printf("Error in tiny_set_linear_constraints: solver is nullptr\n"); return 1; }   // tiny_api.cpp:213-216
     if (n_state < 0 || n_input < 0) return fail(b, TINY_ERR_DIM, "negative constraint count");
     if ((n_state > 0 && (!Alin_x || !blin_x)) || (n_input > 0 && (!Alin_u || !blin_u))) return fail(b, TINY_ERR_NULL, "null constraint table with a positive count");
+    if (int rc = drop_instance_linear(b, 0)) return rc;      // (the latest setter wins: one set for all replaces a per-instance one)
     b->nsl = n_state; b->nil = n_input;
     rows_of(Alin_x, n_state, b->nx, &b->Alin_x); b->blin_x.assign(blin_x, blin_x + n_state);
     rows_of(Alin_u, n_input, b->nu, &b->Alin_u); b->blin_u.assign(blin_u, blin_u + n_input);
@@ -508,6 +618,7 @@ int tiny_batch_set_tv_linear_constraints(TinyBatch* b, int n_state, const double
     if (n_state < 0 || n_input < 0) return fail(b, TINY_ERR_DIM, "negative constraint count");
     if ((n_state > 0 && (!tv_Alin_x || !tv_blin_x)) || (n_input > 0 && (!tv_Alin_u || !tv_blin_u))) return fail(b, TINY_ERR_NULL, "null constraint table with a positive count");
     const int N = b->N;
+    if (int rc = drop_instance_linear(b, 1)) return rc;
     b->ntsl = n_state; b->ntil = n_input;
     // tv_Alin_x is (n_state*N) x nx column-major with row n_state*i + k = constraint k at knot i (admm.cpp:189):
     // row-major it is already [knot][k][nx]; tv_blin_x is n_state x N column-major = [knot][k]
@@ -1071,6 +1182,12 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_tile_dyn")) return b->last_tile_dyn ? 1 : 0;      // the last tile-kernel launch took the dynamic slot form
     if (!strcmp(name, "instance_bounds")) return b->inst_bounds ? 1 : 0;        // a per-instance box is installed (tiny_batch_set_instance_bounds)
     if (!strcmp(name, "last_instance_bounds")) return b->last_inst_bounds ? 1 : 0;   // the last solve's kernel read a per-instance box
+    if (!strcmp(name, "n_state_linear")) return b->nsl;                         // half-space counts as set (per knot for the time-varying set)
+    if (!strcmp(name, "n_input_linear")) return b->nil;
+    if (!strcmp(name, "n_tv_state_linear")) return b->ntsl;
+    if (!strcmp(name, "n_tv_input_linear")) return b->ntil;
+    if (!strcmp(name, "instance_linear")) return (b->inst_lin[0] ? 1 : 0) | (b->inst_lin[1] ? 2 : 0);   // per-instance half-space sets installed: 1 static, 2 time-varying
+    if (!strcmp(name, "last_instance_linear")) return b->last_inst_lin;       // the same mask for what the last solve's kernel read
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;
@@ -1206,7 +1323,7 @@ int tiny_batch_kernel_path(TinyBatch* b) {
     if (!b) return TINY_ERR_NULL;
     if (use_tile(b)) return b->tile_is_jit ? 4 : 1;
     if (use_general(b)) return 2;
-    return (b->kernel && !b->inst_bounds) ? 0 : 3;     // 3: the one-row kernel, instantiated at run time (every form with a per-instance box is)
+    return (b->kernel && !b->inst_bounds && !inst_lin_active(b)) ? 0 : 3;     // 3: the one-row kernel, instantiated at run time (every form with a per-instance box or half-space set is)
 }
 
 long tiny_batch_algorithmic_bytes(TinyBatch* b, int cold) {

@@ -2,6 +2,7 @@
 // tables) and batch_helpers.hip (helper kernels, on-demand buffers) share.
 #pragma once
 #include "batch_impl.hpp"
+#include "lane_tables.hpp"
 
 #define HIP_TRY(b, expr)                                                                          \
     do {                                                                                          \
@@ -32,7 +33,14 @@ int ensure_regroup_buffers(TinyBatch* b, bool second_stream);
 int ensure_adaptive(TinyBatch* b, bool need_tables = true);
 int adaptive_fresh_state(TinyBatch* b);
 int ensure_instance_bounds(TinyBatch* b);   // the per-instance box the kernels read, rebuilt from the caller's arrays when it is out of date (synchronous then)
+// every instance its own half-spaces: is such a set installed AND one of its families enabled (bit 0 static, bit 1 time-varying) / the
+// blocks the kernels read, rebuilt -- or only their offsets rewritten -- when they are out of date (enqueued on the batch's stream)
+int inst_lin_active(const TinyBatch* b);
+int ensure_instance_linear(TinyBatch* b);
+int inst_lin_kmax(const TinyBatch* b);     // the block stride of a per-instance set: the smallest power of two that holds the enabled counts
 // ---- lane tables (batch_tables.hip)
+struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)
+SharedHalfspaces shared_halfspaces(const TinyBatch* b);
 bool box_is_uniform(const TinyBatch* b);     // the box is the same at every knot: the one place that decides it
 int lin_kmax(const TinyBatch* b);       // half-spaces per knot and family the LIN variants are built for (4, 8, 16, 32; 0: coverage kernel)
 void build_tables(TinyBatch* b);

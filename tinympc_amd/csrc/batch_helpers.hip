@@ -163,6 +163,115 @@ int ensure_instance_bounds(TinyBatch* b) {
     return TINY_OK;
 }
 
+// ---- every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): the caller's arrays -> [batch][the
+// enabled sets' blocks: static [3][km][lw], then [N slots][3][km][lw]], one thread per (instance, block, constraint k, lane); what lands
+// there: halfspace_entry (lane_tables.hpp), nothing else.  A set that stayed shared is written from its staged host copies, the same for
+// every instance (ia = ib = 0).  mode 1 rewrites a family's offsets only -- the closed-loop update, which moves b and keeps A: no
+// coefficient is read, no norm summed again
+struct InstLinFamily {
+    HalfspaceRows rows;              // instance 0's, all knots
+    long ia, ib;                     // doubles from one instance's coefficients / offsets to the next one's
+    int mode;                        // 0 leave alone, 1 offsets only, 2 everything
+};
+struct InstLinFill {
+    InstLinFamily f[2][2];           // [static | time-varying][state | input]
+    double* out;
+    int batch, nx, nu, N, lw, km, lv;
+    size_t stride;
+};
+static __global__ __launch_bounds__(256) void fill_instance_linear_kernel(const InstLinFill F) {
+    const int nblk = ((F.lv & 1) ? 1 : 0) + ((F.lv & 2) ? F.N : 0);
+    const size_t total = (size_t)F.batch * nblk * F.km * F.lw;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % F.lw), k = (int)((e / F.lw) % F.km), q = (int)((e / ((size_t)F.lw * F.km)) % nblk);
+        const size_t inst = e / ((size_t)F.lw * F.km * nblk);
+        const int set = ((F.lv & 1) && q == 0) ? 0 : 1, slot = q - (F.lv & 1);
+        const int mode = F.f[set][lane < F.nx ? 0 : 1].mode;
+        if (mode == 0) continue;
+        HalfspaceRows st = F.f[set][0].rows, in = F.f[set][1].rows;
+        st.a += inst * F.f[set][0].ia; st.b += inst * F.f[set][0].ib;
+        in.a += inst * F.f[set][1].ia; in.b += inst * F.f[set][1].ib;
+        if (set == 1) { st = st.knot(slot); in = in.knot(slot - 1); }      // input lanes: slot s = knot s-1
+        double* blk = F.out + inst * F.stride + (size_t)q * 3 * F.km * F.lw;
+        if (mode == 1) { blk[F.km * F.lw + k * F.lw + lane] = halfspace_offset(st, in, F.nx, F.nu, k, lane, F.km); continue; }
+        const HalfspaceEntry v = halfspace_entry(st, in, F.nx, F.nu, k, lane, F.km);
+        blk[k * F.lw + lane] = v.a; blk[F.km * F.lw + k * F.lw + lane] = v.b; blk[2 * F.km * F.lw + k * F.lw + lane] = v.nn;
+    }
+}
+int inst_lin_active(const TinyBatch* b) {
+    return ((b->inst_lin[0] && (b->set.en_state_linear || b->set.en_input_linear)) ? 1 : 0) |
+           ((b->inst_lin[1] && (b->set.en_tv_state_linear || b->set.en_tv_input_linear)) ? 2 : 0);
+}
+// the block stride of a per-instance set: the smallest power of two that holds the enabled counts (1 and 2 included)
+int inst_lin_kmax(const TinyBatch* b) {
+    int m = 0;
+    if (b->set.en_state_linear) m = std::max(m, b->nsl);
+    if (b->set.en_input_linear) m = std::max(m, b->nil);
+    if (b->set.en_tv_state_linear) m = std::max(m, b->ntsl);
+    if (b->set.en_tv_input_linear) m = std::max(m, b->ntil);
+    return halfspace_pow2(m);
+}
+int ensure_instance_linear(TinyBatch* b) {
+    if (!b->inst_lin[0] && !b->inst_lin[1]) return TINY_OK;
+    if (!b->il_full && !b->il_offsets) return TINY_OK;
+    const int N = b->N, nx = b->nx, nu = b->nu;
+    const int lv = ((b->set.en_state_linear || b->set.en_input_linear) ? 1 : 0) | ((b->set.en_tv_state_linear || b->set.en_tv_input_linear) ? 2 : 0);
+    InstLinFill F = {};
+    if (b->il_full) {
+        b->il_lv = lv; b->il_km = inst_lin_kmax(b);
+        b->il_stride = (size_t)3 * b->il_km * box_lanes(nx, nu) * ((lv & 1) + ((lv & 2) ? N : 0));
+    }
+    F.out = nullptr; F.batch = b->batch; F.nx = nx; F.nu = nu; F.N = N; F.lw = box_lanes(nx, nu); F.km = b->il_km; F.lv = b->il_lv; F.stride = b->il_stride;
+    if (b->il_stride == 0 || !inst_lin_active(b)) { b->il_offsets = 0; return TINY_OK; }      // (nothing a kernel would read; il_full stays: built when a switch comes on)
+    const size_t need = (size_t)b->batch * b->il_stride;
+    if (b->il_doubles < need) {
+        if (b->d_inst_lin) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(b->d_inst_lin); }
+        b->d_inst_lin = nullptr; b->il_doubles = 0;
+        HIP_TRY(b, hipMalloc(&b->d_inst_lin, need * sizeof(double)));
+        b->il_doubles = need;
+        b->il_full = true;
+    }
+    F.out = b->d_inst_lin;
+    // the caller's arrays: per instance an (n x cols) column-major matrix, one ROW per half-space -- time-varying: row n * knot + k
+    const int cnt[2][2] = {{b->nsl, b->nil}, {b->ntsl, b->ntil}};
+    const bool on[2][2] = {{b->set.en_state_linear != 0, b->set.en_input_linear != 0}, {b->set.en_tv_state_linear != 0, b->set.en_tv_input_linear != 0}};
+    for (int set = 0; set < 2; ++set)
+        for (int fam = 0; fam < 2; ++fam) {
+            if (!b->inst_lin[set]) continue;
+            const int n = fam ? nu : nx, c = cnt[set][fam];
+            const long knots = set ? (fam ? N - 1 : N) : 1;
+            InstLinFamily& f = F.f[set][fam];
+            f.rows = halfspace_caller_rows(b->d_il_src[set][2 * fam], b->d_il_src[set][2 * fam + 1], c, n, (int)knots, on[set][fam]);
+            f.ia = c * knots * n; f.ib = c * knots;
+            f.mode = b->il_full ? 2 : ((b->il_offsets >> (2 * set + fam)) & 1);
+        }
+    // a set that stayed shared while the other one is per instance: its host copies, staged, for every instance (full builds only)
+    if (b->il_full && (!b->inst_lin[0] || !b->inst_lin[1])) {
+        const int set = b->inst_lin[0] ? 1 : 0;
+        const SharedHalfspaces h = shared_halfspaces(b);
+        const HalfspaceRows hr[2] = {set ? h.tx : h.sx, set ? h.tu : h.su};
+        const std::vector<double>* src[4] = {set ? &b->tvA_x : &b->Alin_x, set ? &b->tvb_x : &b->blin_x, set ? &b->tvA_u : &b->Alin_u, set ? &b->tvb_u : &b->blin_u};
+        std::vector<double> stage;
+        size_t at[4];
+        for (int i = 0; i < 4; ++i) { at[i] = stage.size(); stage.insert(stage.end(), src[i]->begin(), src[i]->end()); }
+        stage.push_back(0.0);
+        if (int rc = upload_growing(b, &b->d_il_stage, &b->il_stage_doubles, stage)) return rc;
+        for (int fam = 0; fam < 2; ++fam) {
+            InstLinFamily& f = F.f[set][fam];
+            f.rows = hr[fam];
+            f.rows.a = b->d_il_stage + at[2 * fam]; f.rows.b = b->d_il_stage + at[2 * fam + 1];
+            f.ia = 0; f.ib = 0; f.mode = 2;
+        }
+    }
+    const int nblk = ((F.lv & 1) ? 1 : 0) + ((F.lv & 2) ? N : 0);
+    const size_t total = (size_t)b->batch * nblk * F.km * F.lw;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
+    hipLaunchKernelGGL(fill_instance_linear_kernel, dim3(grid), dim3(256), 0, b->stream, F);
+    HIP_TRY(b, hipGetLastError());
+    b->il_full = false; b->il_offsets = 0;
+    return TINY_OK;
+}
+
 // histogram of the iteration counts the solve just enqueued leaves in d_status -> pinned host memory, asynchronously (hist_ev)
 int enqueue_iteration_histogram(TinyBatch* b) {
     if (!b->d_hist) {

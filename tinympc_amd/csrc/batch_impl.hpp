@@ -122,6 +122,20 @@ struct TinyBatch {
     double* d_ib_src[4] = {nullptr, nullptr, nullptr, nullptr};
     double* d_inst_bounds = nullptr;
     int* d_ib_flag = nullptr;
+    // every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): set 0 static, set 1 time-varying,
+    // each installed on its own.  d_il_src[set]: the caller's arrays as given -- A_x, b_x, A_u, b_u with a leading batch axis; the counts
+    // are nsl / nil / ntsl / ntil above, whose host copies are empty then.  d_inst_lin: what the kernels read, built from them (and from
+    // the host copies of a set that stayed shared) by batch_helpers.hip with the fill rule of lane_tables.hpp halfspace_entry:
+    // [batch][il_stride] = the enabled sets' blocks, static [3][il_km][lw] first, then [N][3][il_km][lw].  il_full: everything is rebuilt
+    // (a set, a count or an enable switch changed); il_offsets bit 2 * set + family: only that family's offsets are rewritten
+    bool inst_lin[2] = {false, false};
+    bool il_full = false;
+    int il_offsets = 0;
+    int il_km = 1, il_lv = 0;                      // block stride / which sets the array holds (bit 0 static, bit 1 time-varying), as last built
+    size_t il_stride = 0, il_doubles = 0, il_stage_doubles = 0;
+    double* d_il_src[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+    double *d_inst_lin = nullptr, *d_il_stage = nullptr;
+    int last_inst_lin = 0;                         // the mask of per-instance sets the last solve's kernel read
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

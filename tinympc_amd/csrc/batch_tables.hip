@@ -68,11 +68,23 @@ struct HostView {
 };
 }  // namespace
 
+// the four shared half-space families as the fill rule views them: the host copies, row-major [k][n] and [knot][k][n]; a disabled family
+// is off, and so is every family of a set that is installed per instance (its host copies are empty)
+SharedHalfspaces shared_halfspaces(const TinyBatch* b) {
+    const int nx = b->nx, nu = b->nu;
+    const bool s = !b->inst_lin[0], t = !b->inst_lin[1];
+    SharedHalfspaces h;
+    h.sx = {b->Alin_x.data(), b->blin_x.data(), s ? b->nsl : 0, nx, nx, 1, 0, 0, s && b->set.en_state_linear};
+    h.su = {b->Alin_u.data(), b->blin_u.data(), s ? b->nil : 0, nu, nu, 1, 0, 0, s && b->set.en_input_linear};
+    h.tx = {b->tvA_x.data(), b->tvb_x.data(), t ? b->ntsl : 0, nx, nx, 1, (long)b->ntsl * nx, b->ntsl, t && b->set.en_tv_state_linear};
+    h.tu = {b->tvA_u.data(), b->tvb_u.data(), t ? b->ntil : 0, nu, nu, 1, (long)b->ntil * nu, b->ntil, t && b->set.en_tv_input_linear};
+    return h;
+}
+
 // A lane table in the layout T (admm_kernel.hip.h LaneTab) from the batch's cache, bounds, cones and half-spaces.
 static void fill_lane_tables(TinyBatch* b, const LaneTab T, std::vector<double>& t) {
     const int nx = b->nx, nu = b->nu, N = b->N, lw = T.lw;
     const int km = std::max(lin_kmax(b), (int)LIN_KMAX);            // stride of the half-space tables
-    const double inf = std::numeric_limits<double>::infinity();
     t.assign(T.doubles(N, km), 0.0);
     double* vec = &t[T.VEC()];
     const HostView view(b);
@@ -105,32 +117,19 @@ static void fill_lane_tables(TinyBatch* b, const LaneTab T, std::vector<double>&
     }
     // half-space tables of the LIN variants (admm.cpp:137-211): blocks of [3][km][lw] -- coefficient, offset, squared norm; a block is
     // blank (offset +inf, norm 1) where there is no constraint k; constraints beyond km are dropped (lin_kmax = 0: the coverage kernel runs)
-    auto blank = [&](double* blk) {
-        for (int e = 0; e < km * lw; ++e) { blk[km * lw + e] = inf; blk[2 * km * lw + e] = 1.0; }
-    };
-    auto fill = [&](double* blk, int count, const double* Arows, const double* bs, int n, int lane0, bool enabled) {
-        for (int k = 0; k < count && k < km; ++k) {
-            const double* Arow = Arows + (size_t)k * n;
-            double nn = 0.0;
-            for (int c = 0; c < n; ++c) nn += Arow[c] * Arow[c];
-            for (int c = 0; c < n; ++c) {
-                blk[k * lw + lane0 + c] = enabled ? Arow[c] : 0.0;
-                blk[km * lw + k * lw + lane0 + c] = enabled ? bs[k] : inf;
-                blk[2 * km * lw + k * lw + lane0 + c] = enabled ? nn : 1.0;
+    // (which entry holds what: halfspace_entry, lane_tables.hpp -- the rule of a per-instance set, too; a set installed per instance
+    // leaves its blocks here blank: no kernel form reads them)
+    auto fill = [&](double* blk, const HalfspaceRows& st, const HalfspaceRows& in) {
+        for (int k = 0; k < km; ++k)
+            for (int j = 0; j < lw; ++j) {
+                const HalfspaceEntry e = halfspace_entry(st, in, nx, nu, k, j, km);
+                blk[k * lw + j] = e.a; blk[km * lw + k * lw + j] = e.b; blk[2 * km * lw + k * lw + j] = e.nn;
             }
-        }
     };
-    double* ls = &t[T.lin_offset(N)];
-    blank(ls);
-    fill(ls, b->nsl, b->Alin_x.data(), b->blin_x.data(), nx, 0, b->set.en_state_linear);
-    fill(ls, b->nil, b->Alin_u.data(), b->blin_u.data(), nu, nx, b->set.en_input_linear);
-    for (int s = 0; s < N; ++s) {
-        double* blk = &t[T.tlin_offset(N, km)] + (size_t)s * 3 * km * lw;
-        blank(blk);
-        fill(blk, b->ntsl, b->tvA_x.data() + (size_t)s * b->ntsl * nx, b->tvb_x.data() + (size_t)s * b->ntsl, nx, 0, b->set.en_tv_state_linear);   // state lanes: slot s = knot s
-        if (s >= 1)                                                                                                                          // input lanes: slot s = knot s-1
-            fill(blk, b->ntil, b->tvA_u.data() + (size_t)(s - 1) * b->ntil * nu, b->tvb_u.data() + (size_t)(s - 1) * b->ntil, nu, nx, b->set.en_tv_input_linear);
-    }
+    const SharedHalfspaces hs = shared_halfspaces(b);
+    fill(&t[T.lin_offset(N)], hs.sx, hs.su);
+    for (int s = 0; s < N; ++s)                      // state lanes: slot s = knot s; input lanes: slot s = knot s-1
+        fill(&t[T.tlin_offset(N, km)] + (size_t)s * 3 * km * lw, hs.tx.knot(s), hs.tu.knot(s - 1));
     // bounds (admm.cpp:91-98): a disabled or never-set box is (-inf, +inf)
     // (which element lands in which slot and lane: box_entry, lane_tables.hpp -- the rule of the per-instance box, too; with one of
     // those installed this block is not read)

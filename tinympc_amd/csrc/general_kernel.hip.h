@@ -50,6 +50,14 @@ struct GeneralArgs {
     // box_entry: row j of knot i sits in slot i + (j >= nx), lane j).  null: the family's box (o_lo / o_hi)
     const double* inst_bounds;
     int ib_lw;
+    // every instance its own half-spaces: [batch][il_stride] doubles, the blocks of the sets of il_lv (bit 0: the static block
+    // [3][il_km][il_lw] coefficient | offset | squared norm, bit 1: one such block per slot behind it) in the register kernels' lane and
+    // slot convention (lane_tables.hpp halfspace_entry: the state rows of knot i in slot i, the input rows in slot i + 1).  With it set
+    // EVERY enabled half-space family is read from the instance's blocks (a set that stayed shared was written into them for all).
+    // null: the family's tables (o_ax ... o_tbu)
+    const double* inst_lin;
+    size_t il_stride;
+    int il_lw, il_km, il_lv;
 };
 
 // phases of admm_phase_kernel (the batched form of the reference's exported phase functions, admm.hpp:12-17)
@@ -225,8 +233,13 @@ __device__ __forceinline__ void gk_forward(const GeneralArgs& P, const GkLds& L,
 
 // cone and half-space projections of the refreshed slacks (admm.cpp:112-211): one lane per knot point,
 // constraints applied sequentially
-__device__ __forceinline__ void gk_project(const GeneralArgs& P, const size_t rec, const int lane) {
+__device__ __forceinline__ void gk_project(const GeneralArgs& P, const int b, const size_t rec, const int lane) {
     const int nx = P.nx, nu = P.nu, N = P.N, nz = nx + nu;
+    // the instance's own half-spaces: row k of a block holds a family's coefficient row in its lanes (state rows from lane 0, input
+    // rows from lane nx), the offset in the row il_km further on; the squared norm is summed here as for the shared tables
+    const int blk = 3 * P.il_km * P.il_lw;
+    const double* il_s = P.inst_lin ? P.inst_lin + (size_t)b * P.il_stride : nullptr;
+    const double* il_t = il_s ? il_s + ((P.il_lv & 1) ? blk : 0) : nullptr;
     for (int i = lane; i < N; i += 64) {
         double* vcol;
         double zbuf[32];
@@ -246,24 +259,34 @@ __device__ __forceinline__ void gk_project(const GeneralArgs& P, const size_t re
             }
         if (P.lin_s && P.nsl > 0) {
             for (int c = 0; c < nx; ++c) zbuf[c] = P.lslack[o + c];
-            for (int k = 0; k < P.nsl; ++k) halfspace_inplace(zbuf, nx, P.gtab + P.o_ax + k * nx, P.gtab[P.o_bx + k]);
+            for (int k = 0; k < P.nsl; ++k) {
+                if (il_s) halfspace_inplace(zbuf, nx, il_s + k * P.il_lw, il_s[(P.il_km + k) * P.il_lw]);
+                else halfspace_inplace(zbuf, nx, P.gtab + P.o_ax + k * nx, P.gtab[P.o_bx + k]);
+            }
             for (int c = 0; c < nx; ++c) P.lslack[o + c] = zbuf[c];
         }
         if (P.lin_i && P.nil > 0 && i < N - 1) {
             for (int c = 0; c < nu; ++c) zbuf[c] = P.lslack[o + nx + c];
-            for (int k = 0; k < P.nil; ++k) halfspace_inplace(zbuf, nu, P.gtab + P.o_au + k * nu, P.gtab[P.o_bu + k]);
+            for (int k = 0; k < P.nil; ++k) {
+                if (il_s) halfspace_inplace(zbuf, nu, il_s + k * P.il_lw + nx, il_s[(P.il_km + k) * P.il_lw + nx]);
+                else halfspace_inplace(zbuf, nu, P.gtab + P.o_au + k * nu, P.gtab[P.o_bu + k]);
+            }
             for (int c = 0; c < nu; ++c) P.lslack[o + nx + c] = zbuf[c];
         }
         if (P.tlin_s && P.ntsl > 0) {
             for (int c = 0; c < nx; ++c) zbuf[c] = P.tlslack[o + c];
-            for (int k = 0; k < P.ntsl; ++k)
-                halfspace_inplace(zbuf, nx, P.gtab + P.o_tax + (size_t)(i * P.ntsl + k) * nx, P.gtab[P.o_tbx + i * P.ntsl + k]);
+            for (int k = 0; k < P.ntsl; ++k) {
+                if (il_s) halfspace_inplace(zbuf, nx, il_t + (size_t)i * blk + k * P.il_lw, il_t[(size_t)i * blk + (P.il_km + k) * P.il_lw]);
+                else halfspace_inplace(zbuf, nx, P.gtab + P.o_tax + (size_t)(i * P.ntsl + k) * nx, P.gtab[P.o_tbx + i * P.ntsl + k]);
+            }
             for (int c = 0; c < nx; ++c) P.tlslack[o + c] = zbuf[c];
         }
         if (P.tlin_i && P.ntil > 0 && i < N - 1) {
             for (int c = 0; c < nu; ++c) zbuf[c] = P.tlslack[o + nx + c];
-            for (int k = 0; k < P.ntil; ++k)
-                halfspace_inplace(zbuf, nu, P.gtab + P.o_tau + (size_t)(i * P.ntil + k) * nu, P.gtab[P.o_tbu + i * P.ntil + k]);
+            for (int k = 0; k < P.ntil; ++k) {
+                if (il_s) halfspace_inplace(zbuf, nu, il_t + (size_t)(i + 1) * blk + k * P.il_lw + nx, il_t[(size_t)(i + 1) * blk + (P.il_km + k) * P.il_lw + nx]);
+                else halfspace_inplace(zbuf, nu, P.gtab + P.o_tau + (size_t)(i * P.ntil + k) * nu, P.gtab[P.o_tbu + i * P.ntil + k]);
+            }
             for (int c = 0; c < nu; ++c) P.tlslack[o + nx + c] = zbuf[c];
         }
     }
@@ -361,7 +384,7 @@ __global__ __launch_bounds__(64) void admm_general_kernel(const GeneralArgs P) {
             }
             __syncthreads();
             // ---- projections (admm.cpp:112-211)
-            gk_project(P, rec, lane);
+            gk_project(P, b, rec, lane);
             // ---- duals of the cone / linear slacks (admm.cpp:228-255)
             if (P.soc_s | P.soc_i | P.lin_s | P.lin_i | P.tlin_s | P.tlin_i) {
                 for (int e = lane; e < rec_n; e += 64) {
@@ -476,7 +499,7 @@ __global__ __launch_bounds__(64) void admm_phase_kernel(const GeneralArgs P, con
                 if (st ? P.tlin_s : P.tlin_i) P.tlslack[rec + e] = xv + P.tldual[rec + e];        // :176-183
             }
             __syncthreads();
-            gk_project(P, rec, lane);
+            gk_project(P, b, rec, lane);
         } else if (phase == PHASE_DUAL) {
             for (int e = lane; e < rec_n; e += 64) {
                 const int i = e / nz, j = e - i * nz;

@@ -294,6 +294,38 @@ int tiny_group_set_tv_linear_constraints(TinyGroup* g, int ns, const double* Ax,
     if (!g) return TINY_ERR_NULL;
     return for_shards(g, [&](TinyBatch* b) { return tiny_batch_set_tv_linear_constraints(b, ns, Ax, bx, ni, Au, bu); });
 }
+// every instance its own half-spaces: the full batch axis in host memory, the caller's instance order; each shard gets its instances'
+// blocks (set 0 static, 1 time-varying; a NULL coefficient array: the offsets-only update, forwarded as such)
+static int group_set_instance_linear(TinyGroup* g, int set, int ns, const double* Ax, const double* bx, int ni, const double* Au, const double* bu) {
+    if (ns < 0 || ni < 0) return gfail(g, TINY_ERR_DIM, "negative constraint count");
+    const double* src[4] = {Ax, bx, Au, bu};
+    const size_t ks = set ? (size_t)g->N : 1, ki = set ? (size_t)g->N - 1 : 1;
+    const size_t per[4] = {(size_t)ns * ks * g->nx, (size_t)ns * ks, (size_t)ni * ki * g->nu, (size_t)ni * ki};
+    std::vector<double> stage[4];
+    for (int k = 0; k < g->n; ++k) {
+        const double* from[4];
+        for (int a = 0; a < 4; ++a) {
+            from[a] = src[a] ? src[a] + (size_t)first_of(g, k) * per[a] : nullptr;
+            if (g->interleaved && src[a]) {
+                stage[a].resize((size_t)g->count[k] * per[a] + 1);
+                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
+                from[a] = stage[a].data();
+            }
+        }
+        const int rc = set ? tiny_batch_set_instance_tv_linear_constraints(g->shard[k], ns, from[0], from[1], ni, from[2], from[3], TINY_HOST)
+                           : tiny_batch_set_instance_linear_constraints(g->shard[k], ns, from[0], from[1], ni, from[2], from[3], TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
+int tiny_group_set_instance_linear_constraints(TinyGroup* g, int ns, const double* Ax, const double* bx, int ni, const double* Au, const double* bu) {
+    if (!g) return TINY_ERR_NULL;
+    return group_set_instance_linear(g, 0, ns, Ax, bx, ni, Au, bu);
+}
+int tiny_group_set_instance_tv_linear_constraints(TinyGroup* g, int ns, const double* Ax, const double* bx, int ni, const double* Au, const double* bu) {
+    if (!g) return TINY_ERR_NULL;
+    return group_set_instance_linear(g, 1, ns, Ax, bx, ni, Au, bu);
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

@@ -198,7 +198,12 @@ Code compile(const std::string& name_s, const bool tile) {
         R.log_size(prog, &n);
         std::string log(n, '\0');
         if (n) R.log(prog, &log[0]);
-        c.err = "hipRTC compilation of " + std::string(name) + " failed: " + log.substr(0, 400);
+        // the excerpt starts at the line of the first error, not at the "In file included from ..." lines in front of it, whose length
+        // depends on where the compiler keeps its temporary files: a static_assert's message -- what tells the caller WHY a form does
+        // not exist -- reaches him whole wherever the process runs
+        size_t at = log.find("error:");
+        at = at == std::string::npos ? 0 : log.rfind('\n', at) + 1;        // (npos + 1 = 0: the first line)
+        c.err = "hipRTC compilation of " + std::string(name) + " failed: " + log.substr(at, 800);
         R.destroy(&prog);
         return c;
     }
@@ -294,9 +299,10 @@ int jit_used_names(std::string* out) {
 
 hipFunction_t jit_solve_kernel(const JitKey& k, std::string* err) {
     char name[256];
-    // (PB, every instance its own box, is bit 2 of the kernel's MODE argument: the name of every form without it is what it was)
+    // (PB, every instance its own box, is bit 2 of the kernel's MODE argument, PL, every instance its own half-spaces, bit 3: the name of
+    // every form without them is what it was)
     snprintf(name, sizeof(name), "tinympc_amd::admm_solve_kernel<%d, %d, %d, %s, %s, %d, %d, %s, %d, %s%s>", k.nx, k.nu, k.N,
-             k.soc ? "true" : "false", k.dbg ? "true" : "false", k.mode | (k.pb ? 4 : 0), k.lin, k.het ? "true" : "false", k.kmax, k.adapt ? "true" : "false", k.ub ? ", true" : "");
+             k.soc ? "true" : "false", k.dbg ? "true" : "false", k.mode | (k.pb ? 4 : 0) | (k.pl ? 8 : 0), k.lin, k.het ? "true" : "false", k.kmax, k.adapt ? "true" : "false", k.ub ? ", true" : "");
     return get(name, false, err);
 }
 

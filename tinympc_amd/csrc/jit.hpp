@@ -13,9 +13,10 @@ struct JitKey {
     int nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt;
     int ub = 0;               // the knot-invariant-bounds form (round 5: for the per-instance-data variant, which is only compiled in without it)
     int pb = 0;               // every instance its own box (admm_kernel.hip.h PB): run-time instantiated only
+    int pl = 0;               // every instance its own half-spaces (admm_kernel.hip.h PL): run-time instantiated only, kmax from 1
     bool operator<(const JitKey& o) const {
-        const int a[12] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb}, b[12] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb};
-        for (int i = 0; i < 12; ++i)
+        const int a[13] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl}, b[13] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl};
+        for (int i = 0; i < 13; ++i)
             if (a[i] != b[i]) return a[i] < b[i];
         return false;
     }

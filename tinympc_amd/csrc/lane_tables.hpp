@@ -101,4 +101,55 @@ __host__ __device__ inline BoxEntry box_entry(const double* x_min, const double*
 // lanes of a per-instance bounds block: whole DPP rows (16 for the shapes of the one-row kernel, 32 for the wide ones of the coverage kernel)
 __host__ __device__ constexpr int box_lanes(int nx, int nu) { return 16 * ((nx + nu + 15) / 16); }
 
+// ---- half-spaces: what entry (constraint k, lane) of a block [3][km][lw] -- coefficient | offset | squared norm -- holds: the static
+// block and the per-slot blocks of a lane table (LaneTab::lin_offset / tlin_offset) and every instance's blocks of a per-instance set
+// (SolveArgs::inst_lin, GeneralArgs::inst_lin).  State lanes keep the state family's row k, input lanes the input family's; an entry
+// without a constraint -- k beyond the family's count or km, a lane from nx + nu on, a disabled family -- is blank: coefficient 0, offset
+// +inf, norm 1 (cv = 0 > +inf is false: inert).  The squared norm is summed from 0.0 in row order, every product rounded (what
+// tests/halfspace_ref.py models).
+// One family's half-spaces at one knot, wherever they lie: row k has the entries a[k * rs + c * cs], c < n, and the offset b[k]; the
+// next knot's lie ak / bk doubles further on (time-varying sets)
+struct HalfspaceRows {
+    const double *a, *b;
+    int count, n;
+    long rs, cs, ak, bk;
+    bool on;
+    __host__ __device__ HalfspaceRows knot(int i) const {      // (knot -1, an input lane's slot 0: nothing)
+        HalfspaceRows r = *this;
+        if (i < 0) { r.count = 0; return r; }
+        r.a = a + i * ak; r.b = b + i * bk;
+        return r;
+    }
+};
+// one instance's arrays of a family as the setters take them: a (count * knots) x n column-major matrix whose row count * knot + k is
+// half-space k of that knot, and the offsets [knot][k] (a static set: one knot)
+__host__ __device__ inline HalfspaceRows halfspace_caller_rows(const double* a, const double* b, int count, int n, int knots, bool on) {
+    return {a, b, count, n, 1, (long)count * knots, count, count, on};
+}
+struct HalfspaceEntry { double a, b, nn; };
+// the family and the column a lane keeps (nullptr: none)
+__host__ __device__ inline const HalfspaceRows* halfspace_family(const HalfspaceRows& st, const HalfspaceRows& in, int nx, int nu, int k, int lane, int km, int* c) {
+    if (lane >= nx + nu) return nullptr;
+    const HalfspaceRows* f = lane < nx ? &st : &in;
+    *c = lane < nx ? lane : lane - nx;
+    return (f->on && k < f->count && k < km) ? f : nullptr;
+}
+// the offset alone (an offsets-only update rewrites nothing else)
+__host__ __device__ inline double halfspace_offset(const HalfspaceRows& st, const HalfspaceRows& in, int nx, int nu, int k, int lane, int km) {
+    int c = 0;
+    const HalfspaceRows* f = halfspace_family(st, in, nx, nu, k, lane, km, &c);
+    return f ? f->b[k] : __builtin_huge_val();
+}
+__host__ __device__ inline HalfspaceEntry halfspace_entry(const HalfspaceRows& st, const HalfspaceRows& in, int nx, int nu, int k, int lane, int km) {
+#pragma clang fp contract(off)
+    int c = 0;
+    const HalfspaceRows* f = halfspace_family(st, in, nx, nu, k, lane, km, &c);
+    if (!f) return {0.0, __builtin_huge_val(), 1.0};
+    double nn = 0.0;
+    for (int i = 0; i < f->n; ++i) { const double v = f->a[k * f->rs + i * f->cs]; const double pr = v * v; nn = nn + pr; }
+    return {f->a[k * f->rs + c * f->cs], f->b[k], nn};
+}
+// the smallest power of two that holds `count` half-spaces per knot and family (at least 1): the km of a per-instance set's blocks
+__host__ __device__ constexpr int halfspace_pow2(int count) { int km = 1; while (km < count) km *= 2; return km; }
+
 }  // namespace tinympc_amd
