@@ -634,8 +634,8 @@ CASES = {
     "cover_12_4_10": dict(dims=(12, 4, 10), set="plain", fams=ALL, path="cover", options={"force_general": 1}),
     "cover_20_4_10": dict(dims=(20, 4, 10), set="plain", fams=ALL, path="cover", options={"force_general": 1}),
     # the per-knot register form: by solve_kernel_lin_lds the planes of (4,2,30) with time-varying tables need 67 712 B > 65 024 B (the
-    # one-row half-space variants are instantiated without UB; tests/test_halfspace_ref_cpu.py pins the row); use_tile normally takes
-    # the shape, no_tile / debug each rule the tile kernel out
+    # one-row half-space variants are instantiated without UB; tests/test_halfspace_ref_cpu.py pins the row); the kernel choice (csrc/kernel_path.hpp,
+    # tile:planes_do_not_fit_one_row) normally gives the tile kernel the shape, no_tile / debug each rule the tile kernel out
     # ((4,2,30) is a compiled-in shape: kernel_path() says "regs"; its half-space variants are run-time instantiated all the same)
     "perknot_4_2_30_no_tile": dict(dims=(4, 2, 30), set="plain", fams=("tx", "tu"), path="regs", options={"no_tile": 1}, used="tinympc_amd::admm_solve_kernel<4,2,30,"),
     "perknot_4_2_30_sparse": dict(dims=(4, 2, 30), set="sparse_null", fams=("tx", "tu"), path="regs", options={"no_tile": 1}, used="tinympc_amd::admm_solve_kernel<4,2,30,"),

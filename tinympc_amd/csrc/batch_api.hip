@@ -274,8 +274,8 @@ int tiny_batch_setup_hetero(TinyBatch** out, const double* Adyn, const double* B
     TinyBatch* b = *out;
     // the kernel that will read the per-instance tables decides their layout: the one-row kernel where it holds the shape, else the
     // tile kernel's per-instance form (wide and long shapes: round 5); neither: unsupported
-    if (!has_regs(b) && !(b->tile && !b->no_jit)) { tiny_batch_destroy(b); *out = nullptr; return TINY_ERR_UNSUPPORTED; }
-    const bool tile_layout = !has_regs(b);
+    const bool tile_layout = !one_row_form_exists(path_facts(b));
+    if (tile_layout && !(b->tile && !b->no_jit)) { tiny_batch_destroy(b); *out = nullptr; return TINY_ERR_UNSUPPORTED; }
     const int tab_cols = tile_layout ? 32 : 16, tab_lw = tile_layout ? 16 * std::max(1, b->tile->W) : 16;
     auto bail = [&](int code) { tiny_batch_destroy(b); *out = nullptr; return code; };
     const size_t xx = (size_t)nx * nx, xu = (size_t)nx * nu, uu = (size_t)nu * nu, B = batch;
@@ -1321,9 +1321,8 @@ extern "C" {
 
 int tiny_batch_kernel_path(TinyBatch* b) {
     if (!b) return TINY_ERR_NULL;
-    if (use_tile(b)) return b->tile_is_jit ? 4 : 1;
-    if (use_general(b)) return 2;
-    return (b->kernel && !b->inst_bounds && !inst_lin_active(b)) ? 0 : 3;     // 3: the one-row kernel, instantiated at run time (every form with a per-instance box or half-space set is)
+    const PathFacts f = path_facts(b);
+    return kernel_path_code(decide_path(f), f);
 }
 
 long tiny_batch_algorithmic_bytes(TinyBatch* b, int cold) {

@@ -2,6 +2,7 @@
 // tables) and batch_helpers.hip (helper kernels, on-demand buffers) share.
 #pragma once
 #include "batch_impl.hpp"
+#include "kernel_path.hpp"
 #include "lane_tables.hpp"
 
 #define HIP_TRY(b, expr)                                                                          \
@@ -19,13 +20,9 @@ extern const KernelEntry* const* const g_kernel_list;
 extern const int g_nkernels;
 const TileEntry* find_tile(int nx, int nu, int N);
 const KernelEntry* find_kernel(int nx, int nu, int N);
-// ---- which kernel serves the batch as it is configured now
-bool has_regs(const TinyBatch* b);
+// ---- which kernel serves the batch as it is configured now: decide_path(path_facts(b)) (kernel_path.hpp: the facts and the rules)
+PathFacts path_facts(const TinyBatch* b);
 bool soc_active(const TinyBatch* b);
-bool linear_active(const TinyBatch* b);
-int lin_variant(const TinyBatch* b);
-bool use_tile(const TinyBatch* b);
-bool use_general(const TinyBatch* b);
 // ---- buffers and state the API calls create on demand
 int ensure_kpi(TinyBatch* b, double** p);
 int ensure_repack_buffers(TinyBatch* b);
@@ -38,6 +35,7 @@ int ensure_instance_bounds(TinyBatch* b);   // the per-instance box the kernels 
 int inst_lin_active(const TinyBatch* b);
 int ensure_instance_linear(TinyBatch* b);
 int inst_lin_kmax(const TinyBatch* b);     // the block stride of a per-instance set: the smallest power of two that holds the enabled counts
+int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
 // ---- lane tables (batch_tables.hip)
 struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)
 SharedHalfspaces shared_halfspaces(const TinyBatch* b);

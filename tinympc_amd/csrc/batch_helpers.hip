@@ -203,14 +203,7 @@ int inst_lin_active(const TinyBatch* b) {
            ((b->inst_lin[1] && (b->set.en_tv_state_linear || b->set.en_tv_input_linear)) ? 2 : 0);
 }
 // the block stride of a per-instance set: the smallest power of two that holds the enabled counts (1 and 2 included)
-int inst_lin_kmax(const TinyBatch* b) {
-    int m = 0;
-    if (b->set.en_state_linear) m = std::max(m, b->nsl);
-    if (b->set.en_input_linear) m = std::max(m, b->nil);
-    if (b->set.en_tv_state_linear) m = std::max(m, b->ntsl);
-    if (b->set.en_tv_input_linear) m = std::max(m, b->ntil);
-    return halfspace_pow2(m);
-}
+int inst_lin_kmax(const TinyBatch* b) { return halfspace_pow2(max_enabled_halfspaces(b)); }
 int ensure_instance_linear(TinyBatch* b) {
     if (!b->inst_lin[0] && !b->inst_lin[1]) return TINY_OK;
     if (!b->il_full && !b->il_offsets) return TINY_OK;

@@ -13,14 +13,15 @@
 
 namespace tinympc_amd {
 
+// the largest half-space count per knot among the ENABLED families (a disabled family's rows are inert)
+int max_enabled_halfspaces(const TinyBatch* b) {
+    return std::max({0, b->set.en_state_linear ? b->nsl : 0, b->set.en_input_linear ? b->nil : 0, b->set.en_tv_state_linear ? b->ntsl : 0,
+                     b->set.en_tv_input_linear ? b->ntil : 0});
+}
 // Half-spaces per knot and family the register-resident LIN variants are built for: 4 (compiled in), 8 / 16 / 32
 // (instantiated at run time; the tables must still fit the 64 KiB of static LDS), 0 = more than that: coverage kernel.
 int lin_kmax(const TinyBatch* b) {
-    int m = 0;
-    if (b->set.en_state_linear) m = std::max(m, b->nsl);
-    if (b->set.en_input_linear) m = std::max(m, b->nil);
-    if (b->set.en_tv_state_linear) m = std::max(m, b->ntsl);
-    if (b->set.en_tv_input_linear) m = std::max(m, b->ntil);
+    const int m = max_enabled_halfspaces(b);
     if (m <= LIN_KMAX) return LIN_KMAX;
     // more than the compiled-in variants hold: the table stride doubles (run-time instantiated KMAX = 8, 16, 32) while
     // the tables still fit the wave's static LDS
