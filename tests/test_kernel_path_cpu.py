@@ -104,16 +104,31 @@ def test_rule_03_per_instance_halfspaces_one_row_only_where_every_term_holds(ask
 
 
 def test_rule_04_adaptive_rho_stays_on_the_one_row_kernel(ask):
-    """Rule 4: in front of the tile rules and of the half-space rules.  Shared half-spaces reach the launch as `lin` (which refuses them);
-    where the one-row kernel has no variant for them lin is 0 and nothing refuses."""
+    """Rule 4: in front of the tile rules and of the half-space rules.  Shared half-spaces that are ON are refused (2) whether the one-row
+    kernel has a variant for them (lin = lin_families) or not (lin = 0: too many per knot, force_general, a wide set without run-time
+    instantiation) -- without the refusal the second kind ran the adaptive kernel with the half-spaces dropped.  A set that is installed
+    but switched off is no fact at all (lin_families counts enabled sets), and without a register form that text (4) comes first."""
+    wide = dict(LIN, lin_kmax=8, entry_klin=0)
     check(ask, [(dict(FULL, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 0)),
                 (dict(FULL, adaptive=1, has_tile=1, prefer_tile=1), decision("ONE_ROW", "one_row:adaptive", 0)),
                 (dict(FULL, has_tile=1, prefer_tile=1), decision("TILE", "tile:prefer_tile", 1)),
                 (dict(FULL, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:adaptive", 0)),
-                (dict(LIN, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 0, lin=1)),
-                (dict(LIN, adaptive=1, lin_kmax=0, planes_fit=0), decision("ONE_ROW", "one_row:adaptive", 0)),
-                (dict(LIN, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:adaptive", 0)),
-                (dict(TILE_ONLY, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 3, refusal=4))])
+                (dict(LIN, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 0, lin=1, refusal=2)),
+                (dict(LIN, adaptive=1, lin_families=2), decision("ONE_ROW", "one_row:adaptive", 0, lin=2, refusal=2)),
+                (dict(LIN, adaptive=1, lin_families=3), decision("ONE_ROW", "one_row:adaptive", 0, lin=3, refusal=2)),
+                (dict(wide, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 0, lin=1, refusal=2)),
+                (dict(LIN, adaptive=1, lin_kmax=0, planes_fit=0), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, lin_families=3, lin_kmax=0, planes_fit=0), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(wide, adaptive=1, no_jit=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(wide, adaptive=1, variant_jit_failed=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, debug=1, variant_jit_failed=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, entry_klin=0, variant_jit_failed=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, has_tile=1, tile_lin=1, prefer_tile=1), decision("ONE_ROW", "one_row:adaptive", 0, lin=1, refusal=2)),
+                (dict(LIN, adaptive=1, lin_families=0, lin_kmax=0, planes_fit=0, pl_planes_fit=0, entry_klin=0), decision("ONE_ROW", "one_row:adaptive", 0)),
+                (dict(LIN, adaptive=0, lin_kmax=0, planes_fit=0), decision("COVERAGE", "cover:too_many_halfspaces", 2)),
+                (dict(TILE_ONLY, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 3, refusal=4)),
+                (dict(TILE_ONLY, adaptive=1, lin_families=1, lin_kmax=4, tile_lin=1), decision("ONE_ROW", "one_row:adaptive", 3, refusal=4))])
 
 
 def test_rule_05_tile_kernel_for_a_shape_without_a_register_form(ask):
@@ -221,8 +236,9 @@ MESSAGES = ["",
 
 def test_refusals_in_their_order_and_their_messages(driver, ask):
     """What adaptive rho does not combine with: a per-instance box (1), per-instance half-spaces (2), overlapping cones (3), no register form
-    (4), reported in that order; nothing is refused without adaptive rho.  The kernel and the path code are answered all the same: a
-    per-instance box can answer 2 (or 3), per-instance half-spaces answer 3."""
+    (4), shared half-spaces that are on (2 again, LAST: every combination one of the four in front refuses keeps that text), reported in
+    that order; nothing is refused without adaptive rho.  The kernel and the path code are answered all the same: a per-instance box
+    can answer 2 (or 3), per-instance half-spaces answer 3."""
     out = subprocess.run([driver, "messages"], check=True, capture_output=True, text=True, timeout=60).stdout.splitlines()
     assert out == ["%d %s" % (i, m) if m else "%d " % i for i, m in enumerate(MESSAGES)]
     everything = dict(LIN, soc=1, cones_overlap=1, inst_bounds=1, inst_lin=1, adaptive=1)
@@ -238,7 +254,19 @@ def test_refusals_in_their_order_and_their_messages(driver, ask):
                 (dict(JIT, inst_bounds=1, adaptive=1), decision("ONE_ROW", "one_row:pb", 3, pb=1, refusal=1)),
                 (dict(JIT, soc=1, inst_bounds=1, adaptive=1), decision("COVERAGE", "cover:pb", 2, refusal=1)),
                 (dict(LIN, inst_lin=1, adaptive=1), decision("ONE_ROW", "one_row:pl_adaptive", 3, lin=1, pl=1, refusal=2)),
-                (dict(LIN, inst_lin=1, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:pl_adaptive", 3, refusal=2))])
+                (dict(LIN, inst_lin=1, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:pl_adaptive", 3, refusal=2)),
+                # shared half-spaces behind each of the four: the text in front stays
+                (dict(LIN, inst_bounds=1, adaptive=1), decision("COVERAGE", "cover:pb", 2, refusal=1)),
+                (dict(LIN, soc=1, cones_overlap=1, adaptive=1), decision("COVERAGE", "cones_overlap", 2, refusal=3)),
+                (dict(lin_families=1, lin_kmax=4, planes_fit=1, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 3, refusal=4)),
+                (dict(JIT, lin_families=1, lin_kmax=4, planes_fit=1, adaptive=1, no_jit=1), decision("ONE_ROW", "one_row:adaptive", 3, refusal=4)),
+                # ... and alone: with a variant, and in the three cases without one
+                (dict(LIN, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 0, lin=1, refusal=2)),
+                (dict(JIT, lin_families=2, lin_kmax=16, planes_fit=1, adaptive=1), decision("ONE_ROW", "one_row:adaptive", 3, lin=2, refusal=2)),
+                (dict(LIN, adaptive=1, lin_kmax=0, planes_fit=0), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, force_general=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=1, lin_kmax=8, no_jit=1), decision("ONE_ROW", "one_row:adaptive", 0, refusal=2)),
+                (dict(LIN, adaptive=0, lin_kmax=8, no_jit=1), decision("COVERAGE", "cover:wide_halfspaces_without_hiprtc", 2))])
 
 
 def test_the_five_path_codes(ask):
@@ -323,7 +351,7 @@ def restated_rules(f, shape):
     lin = np.where(takes_lin, lf, 0)
     pl = np.array([n.startswith("one_row:pl") for n in name])[which] & (lin != 0)
     pb = np.array([n == "one_row:pb" for n in name])[which]
-    refusal = np.select([np.broadcast_to(c, shape) for c in (~B["adaptive"], B["inst_bounds"], il, B["cones_overlap"], ~regs)], [0, 1, 2, 3, 4], 0)
+    refusal = np.select([np.broadcast_to(c, shape) for c in (~B["adaptive"], B["inst_bounds"], il, B["cones_overlap"], ~regs, lin_on)], [0, 1, 2, 3, 4, 2], 0)
     code = np.where(kernel == 1, np.where(B["tile_is_jit"], 4, 1), np.where(kernel == 2, 2, np.where(B["has_entry"] & ~B["inst_bounds"] & ~il, 0, 3)))
     return which, name, [r[1] for r in rules], lin, pl, pb, refusal, code
 

@@ -57,7 +57,7 @@ constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
     "with a moving cache would need the coverage kernel, which does not take adaptive rho",
-    // (also what the one-row launch answers to shared half-spaces, one_shot and repack_after > 0: build_one_row_launch)
+    // (per-instance or shared half-spaces; also what the one-row launch answers to one_shot and repack_after > 0: build_one_row_launch)
     "adaptive rho does not combine with heterogeneous data / half-spaces / one_shot / repack_after",
     "overlapping cones run on the coverage kernel: no adaptive rho with them",
     "adaptive rho needs the register-resident kernel (nx+nu <= 16, horizon within the register file)",
@@ -84,6 +84,7 @@ inline PathDecision decide_path(const PathFacts& f) {
                                 : f.inst_lin       ? REFUSE_ADAPTIVE_HALFSPACES
                                 : f.cones_overlap  ? REFUSE_ADAPTIVE_OVERLAPPING_CONES
                                 : !regs            ? REFUSE_ADAPTIVE_NO_REGISTER_FORM
+                                : lf               ? REFUSE_ADAPTIVE_HALFSPACES          // shared ones, whether or not a one-row variant exists
                                                    : REFUSE_NONE;
     auto one_row = [&](int lin, int pl, int pb, const char* rule) { return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule}; };
     auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule}; };
@@ -116,7 +117,7 @@ inline PathDecision decide_path(const PathFacts& f) {
         if (f.adaptive) return one_row(pl_form ? lf : 0, pl_form ? 1 : 0, 0, "one_row:pl_adaptive");      // (refused)
         return pl_form ? one_row(lf, 1, 0, "one_row:pl") : cover("cover:pl");
     }
-    // adaptive rho lives on the one-row kernel only (without a register form: refused; with shared half-spaces: the launch refuses)
+    // adaptive rho lives on the one-row kernel only (without a register form, or with shared half-spaces: refused)
     if (f.adaptive) return one_row(no_lin ? 0 : lf, 0, 0, "one_row:adaptive");
     if (tile_can && !regs) return tile("tile:no_register_form");
     if (tile_can && f.prefer_tile) return tile("tile:prefer_tile");
