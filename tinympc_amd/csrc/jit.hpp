@@ -7,20 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <string>
 
-namespace tinympc_amd {
+#include "one_row_variant.hpp"      // JitKey: the key of a one-row instantiation (choose_one_row_variant fills it)
 
-struct JitKey {
-    int nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt;
-    int ub = 0;               // the knot-invariant-bounds form (round 5: for the per-instance-data variant, which is only compiled in without it)
-    int pb = 0;               // every instance its own box (admm_kernel.hip.h PB): run-time instantiated only
-    int pl = 0;               // every instance its own half-spaces (admm_kernel.hip.h PL): run-time instantiated only, kmax from 1
-    bool operator<(const JitKey& o) const {
-        const int a[13] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl}, b[13] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl};
-        for (int i = 0; i < 13; ++i)
-            if (a[i] != b[i]) return a[i] < b[i];
-        return false;
-    }
-};
+namespace tinympc_amd {
 
 // Does the one-row kernel hold this shape at all (one instance per 16-lane row, N-long arrays in <= 512 registers)?
 inline bool jit_shape_fits(int nx, int nu, int N, bool soc) {

@@ -53,7 +53,8 @@ struct TileEntry {
 #define KERNELS_LIN(NX, NU, NN, S)                                                                \
     { nullptr, tinympc_amd::admm_solve_kernel<NX, NU, NN, S, false, 2, 1>,                         \
       tinympc_amd::admm_solve_kernel<NX, NU, NN, S, false, 2, 2>, tinympc_amd::admm_solve_kernel<NX, NU, NN, S, false, 2, 3> }
-#define KERNELS_FOR(NX, NU, NN)                                                                   \
+// which slots the two macros below fill is what the launch reads as EntrySlots (one_row_variant.hpp; batch_dispatch.hip entry_slots)
+#define KERNELS_FOR(NX, NU, NN)                                                                  \
     { NX, NU, NN, { { KERNELS_MODES(NX, NU, NN, false, false), KERNELS_MODES(NX, NU, NN, false, true) },   \
                     { KERNELS_MODES(NX, NU, NN, true, false), KERNELS_MODES(NX, NU, NN, true, true) } },    \
       { KERNELS_LIN(NX, NU, NN, false), KERNELS_LIN(NX, NU, NN, true) },                                    \
