@@ -180,6 +180,29 @@ int tiny_batch_set_instance_tv_linear_constraints(TinyBatch* b, int n_state, con
 /* what instance `instance` is held to by the static (tv = 0) or the time-varying (tv = 1) set, as set (whatever the enable switches say),
  * in the shared setter's layout; on a shared set: the shared one.  any pointer may be NULL */
 int tiny_batch_get_instance_linear_constraints(TinyBatch* b, int instance, int tv, double* A_x, double* b_x, double* A_u, double* b_u);
+/* every instance its own cone coefficients on the cones the last tiny_batch_set_cone_constraints installed: cx [batch][n_state_cones],
+ * cu [batch][n_input_cones], instance i's coefficients in the order of Acx / Acu.  Where the cones sit, how many there are and whether
+ * they share rows stays a property of the batch; with no cone set installed the call is TINY_ERR_ARG.  A NULL array for a family that has
+ * cones keeps that family's shared coefficients for every instance; both NULL is TINY_ERR_ARG.  flags: TINY_HOST or TINY_DEVICE (copied;
+ * the caller may free); TINY_BROADCAST is TINY_ERR_ARG (one coefficient for all: tiny_batch_set_cone_constraints).  The values are stored
+ * as given and truncated to float where admm.cpp:39 does so; nothing is validated that the shared setter does not validate.  The latest
+ * setter wins: a later call replaces both families (one passed as NULL is back on the shared coefficients), a later
+ * tiny_batch_set_cone_constraints drops the per-instance coefficients and frees their arrays.  A failed call leaves what was installed.
+ * The en_state_soc / en_input_soc switches act as on a shared set; tiny_batch_reset leaves the coefficients alone.  Works on
+ * tiny_batch_setup and tiny_batch_setup_hetero batches.
+ * Read-backs (tiny_batch_get_option): "instance_cones" is 1 while per-instance coefficients are installed; "last_instance_cones" is 1 when
+ * the last solve's kernel read them: installed and a cone family on.
+ * Where it runs: the one-row kernel's PC forms (run-time instantiated; tiny_batch_kernel_path 3) for the shapes that kernel holds, with
+ * per-instance problem data and every launch form of the shared cone variant; the coverage kernel -- correct, not fast,
+ * tiny_batch_kernel_path says so -- for tile-kernel shapes, cones that share rows (projected one after the other, each with the
+ * instance's own coefficient), half-spaces (shared or per instance) or a per-instance box at the same time, "debug", "force_general",
+ * "no_jit" or a missing hipRTC.  Adaptive rho fails the solve with TINY_ERR_UNSUPPORTED.  Out of scope: per-instance cone positions or
+ * counts, the tile kernel, per-instance half-spaces together with these on the one-row kernel, adaptive rho, tiny_codegen,
+ * tiny_solve_batch and the drop-in structs (which go on taking one coefficient set for all solvers). */
+int tiny_batch_set_instance_cone_coefficients(TinyBatch* b, const double* cx, const double* cu, int flags);
+/* what instance `instance` is held to, as set (whatever the enable switches say): cx [n_state_cones], cu [n_input_cones]; on a shared
+ * set, and for a family that kept the shared coefficients: the shared values.  either pointer may be NULL */
+int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double* cx, double* cu);
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -454,6 +477,8 @@ int tiny_group_set_instance_linear_constraints(TinyGroup* g, int n_state, const 
                                                int n_input, const double* Alin_u, const double* blin_u);
 int tiny_group_set_instance_tv_linear_constraints(TinyGroup* g, int n_state, const double* tv_Alin_x, const double* tv_blin_x,
                                                   int n_input, const double* tv_Alin_u, const double* tv_blin_u);
+/* every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients): host, full batch axis, caller order; flags: TINY_HOST */
+int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, const double* cu, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

@@ -40,6 +40,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_destroy", "tiny_batch_set_bound_constraints", "tiny_batch_set_instance_bounds", "tiny_batch_get_instance_bounds",
     "tiny_batch_set_cone_constraints", "tiny_batch_set_linear_constraints", "tiny_batch_set_tv_linear_constraints",
     "tiny_batch_set_instance_linear_constraints", "tiny_batch_set_instance_tv_linear_constraints", "tiny_batch_get_instance_linear_constraints",
+    "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -52,7 +53,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -174,6 +175,8 @@ def lib():
         L.tiny_batch_set_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.tiny_batch_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.tiny_batch_get_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+        L.tiny_batch_set_instance_cone_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_instance_cone_coefficients.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -238,6 +241,7 @@ def lib():
         L.tiny_group_set_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
+        L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.tiny_group_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -415,6 +419,29 @@ class TinyBatchSolver:
             self._h, len(ia[0]), ia[0].ctypes.data_as(_ip), ia[1].ctypes.data_as(_ip), da[0].ctypes.data_as(_dp),
             len(ia[2]), ia[2].ctypes.data_as(_ip), ia[3].ctypes.data_as(_ip), da[1].ctypes.data_as(_dp)),
             "set_cone_constraints")
+
+    def _instance_cones(self, cx, cu):
+        """[batch, n_state_cones], [batch, n_input_cones] (None: that family keeps the shared coefficients) -> flat arrays; None stays None"""
+        return [None if v is None else np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(self.batch, -1)).ravel() for v in (cx, cu)]
+
+    def set_instance_cone_coefficients(self, cx, cu):
+        """every instance its own cone coefficients on the cones set_cone_constraints installed: cx [batch, n_state_cones], cu
+        [batch, n_input_cones]; None: that family keeps the shared coefficients for every instance"""
+        a = self._instance_cones(cx, cu)
+        p = [None if v is None else v.ctypes.data_as(C.c_void_p) for v in a]
+        self._check(lib().tiny_batch_set_instance_cone_coefficients(self._h, p[0], p[1], HOST), "set_instance_cone_coefficients")
+
+    def set_instance_cone_coefficients_device(self, cx, cu):
+        """the same from device pointers (ints; 0: none) to [batch][count] doubles resident in HBM (copied)"""
+        p = [C.c_void_p(int(v)) if v else None for v in (cx, cu)]
+        self._check(lib().tiny_batch_set_instance_cone_coefficients(self._h, p[0], p[1], DEVICE), "set_instance_cone_coefficients_device")
+
+    def get_instance_cone_coefficients(self, i):
+        """(cx [n_state_cones], cu [n_input_cones]) instance i is held to, as set; on a shared set: the shared values"""
+        out = [np.zeros(self.get_option("n_state_cones")), np.zeros(self.get_option("n_input_cones"))]
+        self._check(lib().tiny_batch_get_instance_cone_coefficients(self._h, int(i), *[v.ctypes.data_as(_dp) for v in out]),
+                    "get_instance_cone_coefficients")
+        return tuple(out)
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
         """Half-spaces a_k' z <= b_k (tiny_set_linear_constraints): Alin_x (n_s, nx), blin_x (n_s,), Alin_u (n_i, nu)."""
@@ -803,6 +830,25 @@ class TinyGroupSolver:
 
     def set_instance_tv_linear_constraints(self, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u):
         self._set_instance_halfspaces(1, tv_Alin_x, tv_blin_x, tv_Alin_u, tv_blin_u, "set_instance_tv_linear_constraints")
+
+    def set_instance_cone_coefficients(self, cx, cu):
+        """every instance its own cone coefficients, the full batch axis in the caller's order (TinyBatchSolver's shapes)"""
+        a = TinyBatchSolver._instance_cones(self, cx, cu)
+        p = [None if v is None else v.ctypes.data_as(_dp) for v in a]
+        self._check(lib().tiny_group_set_instance_cone_coefficients(self._h, p[0], p[1], HOST), "set_instance_cone_coefficients")
+
+    def get_instance_cone_coefficients(self, i):
+        """(cx, cu) instance i (the caller's order) is held to: asked of the shard that holds it"""
+        for k in range(self.shards):
+            at = np.flatnonzero(self.shard_indices(k) == int(i))
+            if len(at):
+                h = lib().tiny_group_shard(self._h, k)
+                out = [np.zeros(int(lib().tiny_batch_get_option(h, n))) for n in (b"n_state_cones", b"n_input_cones")]
+                rc = lib().tiny_batch_get_instance_cone_coefficients(h, int(at[0]), *[v.ctypes.data_as(_dp) for v in out])
+                if rc != OK:
+                    raise TinyMPCError(f"get_instance_cone_coefficients failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+                return tuple(out)
+        raise TinyMPCError(f"get_instance_cone_coefficients: instance {i} of {self.batch}")
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         ai = lambda v: np.ascontiguousarray(v, dtype=np.int32)

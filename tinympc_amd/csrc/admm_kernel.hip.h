@@ -32,7 +32,7 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces; see
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients; see
 //     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
@@ -197,14 +197,17 @@ struct SolveArgs {
     // pointer takes the place of the PREFETCH form's ticket counters: the argument block of every other form keeps its size and offsets
     // PL forms: every instance its own half-spaces -- [batch][the blocks of the form's LIN sets: static [3][KMAX][16], then [N][3][KMAX][16]]
     // (lane_tables.hpp halfspace_entry; built by batch_helpers.hip).  PL excludes PF and PB alike, so it shares their place
+    // PC forms: every instance its own cone coefficients -- [batch][16 lanes], lane j the coefficient of the cone whose rows include lane j
+    // (lane_tables.hpp cone_entry; built by batch_helpers.hip).  PF and PB are box forms, PL + PC is not built: the same place again
     union {
         unsigned* pf_counter;
         const double* inst_bounds;
         const double* inst_lin;
+        const double* inst_cones;
     };
     unsigned pf_base[8];
 };
-// (the PB / PL pointers share the ticket counters' place: the argument block every compiled-in form was built against stays what it was)
+// (the PB / PL / PC pointers share the ticket counters' place: the argument block every compiled-in form was built against stays what it was)
 static_assert(sizeof(SolveArgs) == 472 && __builtin_offsetof(SolveArgs, het_tabs) == 208 && __builtin_offsetof(SolveArgs, pf_mask) == 416 &&
               __builtin_offsetof(SolveArgs, pf_counter) == 432 && __builtin_offsetof(SolveArgs, pf_base) == 440, "SolveArgs: size and offsets are fixed");
 
@@ -745,6 +748,13 @@ __device__ __forceinline__ void project_halfspace_columns(const int t, const int
 // with the four rows' tables -- which is why these forms are instantiated at KMAX 1 and 2 as well: four [N][3][4][16] tables at N = 10
 // are 61 KB); with SOC, HET and every launch form; not HALF, PF, ADAPT or PB.  Run-time instantiated only; bit 3 of the sixth template
 // argument (MODE | 8), for the reason given at PB.
+// PC: every instance its own cone coefficients (SolveArgs::inst_cones) -- where the cones sit stays the batch's, so the item layout of
+// the transposed cone step (item_at) is the shared form's; the coefficient of a lane's item (item_mu) is a per-ROW quantity, loaded at
+// the top of every tile from the row's instance, next to the HET table loads.  The last component of an outside projection is always
+// the reference's division a / mu: a wave holds four instances' coefficients, and the multiply by 1 / mu that the shared form takes
+// when every coefficient of the launch is a power of two would have to be decided per tile by a ballot in front of the iteration
+// loop -- the division is correct for any mix and costs only where a cone is active.  SOC forms with HET, UB and every launch form;
+// not HALF, PF, PB (box forms), PL or ADAPT.  Run-time instantiated only; bit 4 of the sixth template argument (MODE | 16).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -754,7 +764,10 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr int MODE = MODE_PB & 3;
     constexpr bool PB = (MODE_PB & 4) != 0;
     constexpr bool PL = (MODE_PB & 8) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 16, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces");
+    constexpr bool PC = (MODE_PB & 16) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 32, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients");
+    static_assert(!PC || SOC, "per-instance cone coefficients: a cone variant (SOC)");
+    static_assert(!PC || (!PL && !ADAPT), "per-instance cone coefficients: not with per-instance half-spaces (coverage kernel) or adaptive rho (refused)");
     static_assert(!PL || LIN != 0, "per-instance half-spaces: a half-space variant (LIN != 0)");
     static_assert(!PL || !HALF, "per-instance half-spaces: not the half-row form");
     static_assert(!PL || !PF, "per-instance half-spaces: not the prefetch form");
@@ -876,7 +889,7 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr int SOC_PASSES = SOC ? (soc_item_passes(NX, NU, N) > 0 ? soc_item_passes(NX, NU, N) : 1) : 1;
     int item_at[SOC_PASSES];                                   // LDS index (W plane) of the item's first component; the dummy item for lanes without one
     float item_mu[SOC_PASSES], item_rmu[SOC_PASSES];
-    bool mu_pow2 = true;                                       // every cone coefficient of the launch is 2^k, |k| <= 60 (wave-uniform): soc_project3 multiplies
+    bool mu_pow2 = !PC;                                        // every cone coefficient of the launch is 2^k, |k| <= 60 (wave-uniform): soc_project3 multiplies (PC: never)
     int soc_passes = 0;                                        // passes that hold an item (wave-uniform: a family whose cone is off has none)
     if constexpr (SOC) {
         if (lane < 3) {                                        // the dummy item: W = VC = (0, 0, 1), GC = 0
@@ -895,14 +908,16 @@ void admm_solve_kernel(const SolveArgs P) {
                 const int cnt = hb < NX ? N : N - 1;
                 if (t >= 0 && t < cnt) {
                     item_at[p] = (grp * N + t + (hb < NX ? 0 : 1)) * SLOT_D + hb;
-                    item_mu[p] = (float)P.tab[TAB_VEC + VEC_CONE_MU * 16 + hb];
+                    if constexpr (!PC) item_mu[p] = (float)P.tab[TAB_VEC + VEC_CONE_MU * 16 + hb];      // (PC: the row's instance has its own, loaded for every tile)
                     t = -1;
                 } else if (t >= 0) t -= cnt;
             }
             item_rmu[p] = 1.0f / item_mu[p];
-            const unsigned mb_ = __float_as_uint(item_mu[p]);
-            const bool p2 = (mb_ & 0x807FFFFFu) == 0u && (mb_ >> 23) >= 127u - 60u && (mb_ >> 23) <= 127u + 60u;
-            if (__builtin_amdgcn_ballot_w64(!p2) != 0ull) mu_pow2 = false;
+            if constexpr (!PC) {
+                const unsigned mb_ = __float_as_uint(item_mu[p]);
+                const bool p2 = (mb_ & 0x807FFFFFu) == 0u && (mb_ >> 23) >= 127u - 60u && (mb_ >> 23) <= 127u + 60u;
+                if (__builtin_amdgcn_ballot_w64(!p2) != 0ull) mu_pow2 = false;
+            }
         }
     }
     bool lin_lane = false, tlin_lane = false;
@@ -1134,6 +1149,25 @@ void admm_solve_kernel(const SolveArgs P) {
                 }
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
+            }
+            if constexpr (PC) {
+                // the coefficient of this lane's item in every pass: the item's cone starts at lane hb of the row (item_at holds it: a
+                // slot is SLOT_D > 16 doubles), the row's instance keeps its coefficient there.  A lane without an item keeps the dummy's 1.0
+                // (one load per pass, all from the row's 128-byte block.  One load per lane and a ds_bpermute per pass was built, too: it
+                // costs 4 to 8 B/lane of scratch more in four of the five forms that spill at all, and saves none in any)
+                size_t ic_at = (size_t)b * 16;
+                asm volatile("" : "+v"(ic_at));
+                const double* ic = P.inst_cones + ic_at;
+#pragma unroll
+                for (int p = 0; p < SOC_PASSES; ++p) {
+                    // (through an empty asm: the lane's offset is the same in every tile, and formed once in front of the tile loop it
+                    // would be held -- or spilled -- from the kernel's first instruction to its last, as at PB)
+                    int at = item_at[p];
+                    asm volatile("" : "+v"(at));
+                    const bool has = at != 4 * N * SLOT_D;
+                    const float own = (float)ic[has ? at % SLOT_D : 0];
+                    item_mu[p] = has ? own : 1.0f;
+                }
             }
             if constexpr (ADAPT) {                             // this instance's own rho / Kinf / Pinf (they persist from solve to solve)
                 rho = P.arho[b];

@@ -347,7 +347,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
                     b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_il_src[0][0], b->d_il_src[0][1], b->d_il_src[0][2], b->d_il_src[0][3],
-                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
     if (b->h_wire) hipHostFree(b->h_wire);
@@ -440,6 +440,19 @@ int tiny_batch_get_instance_bounds(TinyBatch* b, int instance, double* x_min, do
     return TINY_OK;
 }
 
+// tiny_batch_set_cone_constraints is about to install one coefficient set for all (and, maybe, other cones): per-instance coefficients
+// go, their arrays freed once the stream has run dry of their readers
+static int drop_instance_cones(TinyBatch* b) {
+    if (!b->inst_cones && !b->d_inst_cones && !b->d_ic_src[0] && !b->d_ic_src[1]) return TINY_OK;
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    void* gone[] = {b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos};
+    for (void* p : gone) if (p) (void)hipFree(p);
+    b->d_ic_src[0] = b->d_ic_src[1] = nullptr; b->d_inst_cones = nullptr; b->d_ic_stage = nullptr; b->d_ic_pos = nullptr; b->ic_stage_doubles = 0;
+    b->inst_cones = false; b->inst_cones_dirty = false;
+    return TINY_OK;
+}
+
 int tiny_batch_set_cone_constraints(TinyBatch* b, int nsc, const int* Acx, const int* qcx, const double* cx,
                                     int nic, const int* Acu, const int* qcu, const double* cu) {
     if (!b) { printf("Error in tiny_set_cone_constraints: solver is nullptr\n"); return 1; }     // tiny_api.cpp:179-182
@@ -462,10 +475,62 @@ int tiny_batch_set_cone_constraints(TinyBatch* b, int nsc, const int* Acx, const
                 if (used[off + A[k] + c3]++) (pass ? overlap_u : overlap_x) = true;
         }
     }
+    if (int rc = drop_instance_cones(b)) return rc;      // (the latest setter wins: one coefficient set for all replaces the per-instance one)
     b->cones_overlap_x = overlap_x; b->cones_overlap_u = overlap_u;
     b->Acx.assign(Acx, Acx + nsc); b->qcx.assign(qcx, qcx + nsc); b->cx.assign(cx, cx + nsc);
     b->Acu.assign(Acu, Acu + nic); b->qcu.assign(qcu, qcu + nic); b->cu.assign(cu, cu + nic);
     b->tab_dirty = true;
+    return TINY_OK;
+}
+
+// every instance its own cone coefficients on the cones tiny_batch_set_cone_constraints installed.  The caller's arrays are kept on the
+// device as given (the coverage kernel reads them so); the block the one-row kernel reads is built from them in front of the next
+// launch (ensure_instance_cones).  Everything that can fail happens before anything installed is touched
+int tiny_batch_set_instance_cone_coefficients(TinyBatch* b, const double* cx, const double* cu, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    if (b->Acx.empty() && b->Acu.empty()) return fail(b, TINY_ERR_ARG, "no cone set installed: tiny_batch_set_cone_constraints first");
+    if (flags & TINY_BROADCAST) return fail(b, TINY_ERR_ARG, "one coefficient for every instance: tiny_batch_set_cone_constraints");
+    const size_t cnt[2] = {b->Acx.size(), b->Acu.size()};
+    const double* src[2] = {cnt[0] ? cx : nullptr, cnt[1] ? cu : nullptr};
+    if (!src[0] && !src[1]) return fail(b, TINY_ERR_ARG, "null coefficient arrays for every cone family that has cones");
+    HIP_TRY(b, hipSetDevice(b->device));
+    double* fresh[2] = {nullptr, nullptr};
+    hipError_t err = hipSuccess;
+    for (int i = 0; i < 2 && err == hipSuccess; ++i) {
+        if (!src[i]) continue;
+        const size_t n = (size_t)b->batch * cnt[i];
+        err = hipMalloc(&fresh[i], n * sizeof(double));
+        if (err == hipSuccess) err = hipMemcpyAsync(fresh[i], src[i], n * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
+    }
+    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);      // (the caller may free its arrays; nothing reads the old ones any more)
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        for (double* p : fresh) if (p) (void)hipFree(p);
+        return fail(b, TINY_ERR_HIP, "per-instance cone coefficients: %s", hipGetErrorString(err));
+    }
+    for (int i = 0; i < 2; ++i) {                                        // (the latest setter wins: a family passed as NULL is back on the shared coefficients)
+        if (b->d_ic_src[i]) (void)hipFree(b->d_ic_src[i]);
+        b->d_ic_src[i] = fresh[i];
+    }
+    b->inst_cones = true; b->inst_cones_dirty = true;
+    b->tab_dirty = true;
+    return TINY_OK;
+}
+// what instance `instance` is held to, as set (whatever the switches say); on a shared set, or for a family that kept it: the shared values
+int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double* cx, double* cu) {
+    if (!b) return TINY_ERR_NULL;
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    double* dst[2] = {cx, cu};
+    const std::vector<double>* shared[2] = {&b->cx, &b->cu};
+    for (int i = 0; i < 2; ++i) {
+        const size_t n = shared[i]->size();
+        if (!dst[i] || !n) continue;
+        if (b->inst_cones && b->d_ic_src[i]) {
+            HIP_TRY(b, hipSetDevice(b->device));
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+            HIP_TRY(b, hipMemcpy(dst[i], b->d_ic_src[i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
+        } else for (size_t k = 0; k < n; ++k) dst[i][k] = (*shared[i])[k];
+    }
     return TINY_OK;
 }
 
@@ -1188,6 +1253,10 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "n_tv_input_linear")) return b->ntil;
     if (!strcmp(name, "instance_linear")) return (b->inst_lin[0] ? 1 : 0) | (b->inst_lin[1] ? 2 : 0);   // per-instance half-space sets installed: 1 static, 2 time-varying
     if (!strcmp(name, "last_instance_linear")) return b->last_inst_lin;       // the same mask for what the last solve's kernel read
+    if (!strcmp(name, "n_state_cones")) return (long)b->Acx.size();              // cone counts as set
+    if (!strcmp(name, "n_input_cones")) return (long)b->Acu.size();
+    if (!strcmp(name, "instance_cones")) return b->inst_cones ? 1 : 0;          // per-instance cone coefficients are installed (tiny_batch_set_instance_cone_coefficients)
+    if (!strcmp(name, "last_instance_cones")) return b->last_inst_cones ? 1 : 0;   // the last solve's kernel read them: installed and a cone family on
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;

@@ -35,6 +35,10 @@ int ensure_instance_bounds(TinyBatch* b);   // the per-instance box the kernels 
 int inst_lin_active(const TinyBatch* b);
 int ensure_instance_linear(TinyBatch* b);
 int inst_lin_kmax(const TinyBatch* b);     // the block stride of a per-instance set: the smallest power of two that holds the enabled counts
+// every instance its own cone coefficients: installed AND a cone family on / the block the one-row kernel reads, rebuilt when a setter
+// has changed it (enqueued on the batch's stream)
+bool inst_cones_active(const TinyBatch* b);
+int ensure_instance_cones(TinyBatch* b);
 int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
 // ---- lane tables (batch_tables.hip)
 struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)

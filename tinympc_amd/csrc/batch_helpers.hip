@@ -265,6 +265,46 @@ int ensure_instance_linear(TinyBatch* b) {
     return TINY_OK;
 }
 
+// ---- every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients): the caller's dense arrays cx [batch][n_state],
+// cu [batch][n_input] -> [batch][lw lanes], one thread per (instance, lane); what lands there: cone_entry (lane_tables.hpp), nothing else.
+// A family whose array is null takes the shared coefficients, the same for every instance (stride 0)
+static __global__ __launch_bounds__(256) void fill_instance_cones_kernel(double* __restrict__ out, const double* __restrict__ cx, const double* __restrict__ cu, long cx_stride,
+                                                                         long cu_stride, const int* __restrict__ Acx, int n_state, const int* __restrict__ Acu, int n_input,
+                                                                         int batch, int nx, int nu, int lw) {
+    const size_t total = (size_t)batch * lw;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % lw);
+        const size_t b = e / lw;
+        out[e] = cone_entry(cx + b * cx_stride, cu + b * cu_stride, Acx, n_state, Acu, n_input, nx, nu, lane);
+    }
+}
+bool inst_cones_active(const TinyBatch* b) { return b->inst_cones && soc_active(b); }
+int ensure_instance_cones(TinyBatch* b) {
+    if (!b->inst_cones || !b->inst_cones_dirty) return TINY_OK;
+    const int lw = box_lanes(b->nx, b->nu), ns = (int)b->Acx.size(), ni = (int)b->Acu.size();
+    const size_t total = (size_t)b->batch * lw;
+    if (!b->d_inst_cones) HIP_TRY(b, hipMalloc(&b->d_inst_cones, total * sizeof(double)));
+    if (!b->d_ic_pos) HIP_TRY(b, hipMalloc(&b->d_ic_pos, (size_t)(ns + ni + 1) * sizeof(int)));
+    // the cone positions and the shared coefficients (of a family that did not get its own), staged; the host vectors are pageable:
+    // the copies are staged synchronously
+    std::vector<int> pos(b->Acx);
+    pos.insert(pos.end(), b->Acu.begin(), b->Acu.end());
+    pos.push_back(0);
+    std::vector<double> shared(b->cx);
+    shared.insert(shared.end(), b->cu.begin(), b->cu.end());
+    shared.push_back(1.0);
+    HIP_TRY(b, hipMemcpyAsync(b->d_ic_pos, pos.data(), pos.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
+    if (int rc = upload_growing(b, &b->d_ic_stage, &b->ic_stage_doubles, shared)) return rc;
+    const double* cx = b->d_ic_src[0] ? b->d_ic_src[0] : b->d_ic_stage;
+    const double* cu = b->d_ic_src[1] ? b->d_ic_src[1] : b->d_ic_stage + ns;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
+    hipLaunchKernelGGL(fill_instance_cones_kernel, dim3(grid), dim3(256), 0, b->stream, b->d_inst_cones, cx, cu, b->d_ic_src[0] ? (long)ns : 0L,
+                       b->d_ic_src[1] ? (long)ni : 0L, b->d_ic_pos, ns, b->d_ic_pos + ns, ni, b->batch, b->nx, b->nu, lw);
+    HIP_TRY(b, hipGetLastError());
+    b->inst_cones_dirty = false;
+    return TINY_OK;
+}
+
 // histogram of the iteration counts the solve just enqueued leaves in d_status -> pinned host memory, asynchronously (hist_ev)
 int enqueue_iteration_histogram(TinyBatch* b) {
     if (!b->d_hist) {

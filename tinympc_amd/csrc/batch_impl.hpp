@@ -136,6 +136,17 @@ struct TinyBatch {
     double* d_il_src[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
     double *d_inst_lin = nullptr, *d_il_stage = nullptr;
     int last_inst_lin = 0;                         // the mask of per-instance sets the last solve's kernel read
+    // every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients).  d_ic_src: the caller's arrays as given --
+    // cx [batch][Acx.size()], cu [batch][Acu.size()]; a null one: that family keeps the shared coefficients (cx / cu above) for every
+    // instance.  The coverage kernel reads them as they are (it walks the cones by index); d_inst_cones [batch][lw] is what the one-row
+    // kernel's PC forms read, built by batch_helpers.hip with the fill rule of lane_tables.hpp cone_entry from the arrays and from
+    // d_ic_stage (the cone positions and the shared coefficients, staged).  The block does not depend on the enable switches
+    bool inst_cones = false, inst_cones_dirty = false;
+    double* d_ic_src[2] = {nullptr, nullptr};
+    double *d_inst_cones = nullptr, *d_ic_stage = nullptr;
+    int* d_ic_pos = nullptr;
+    size_t ic_stage_doubles = 0;
+    bool last_inst_cones = false;                  // the last solve's kernel read them
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

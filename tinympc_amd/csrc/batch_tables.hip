@@ -102,15 +102,19 @@ static void fill_lane_tables(TinyBatch* b, const LaneTab T, std::vector<double>&
     for (int j = 0; j < lw; ++j) vec[VEC_CONE_BASE * lw + j] = -1.0;
     const bool s_on = b->set.en_state_soc && !b->Acx.empty(), i_on = b->set.en_input_soc && !b->Acu.empty();
     for (int j = 0; j < nx + nu; ++j) vec[VEC_SOCFLAG * lw + j] = (j < nx ? s_on : i_on) ? 1.0 : 0.0;
-    auto cones = [&](const std::vector<int>& first, const std::vector<double>& mu, int lane0) {
+    auto cones = [&](const std::vector<int>& first, int lane0) {
         for (size_t k = 0; k < first.size(); ++k)
-            for (int c3 = 0; c3 < 3; ++c3) {
-                vec[VEC_CONE_BASE * lw + lane0 + first[k] + c3] = lane0 + first[k];
-                vec[VEC_CONE_MU * lw + lane0 + first[k] + c3] = mu[k];
-            }
+            for (int c3 = 0; c3 < 3; ++c3) vec[VEC_CONE_BASE * lw + lane0 + first[k] + c3] = lane0 + first[k];
     };
-    if (b->set.en_state_soc) cones(b->Acx, b->cx, 0);
-    if (b->set.en_input_soc) cones(b->Acu, b->cu, nx);
+    if (b->set.en_state_soc) cones(b->Acx, 0);
+    if (b->set.en_input_soc) cones(b->Acu, nx);
+    // (whose coefficient a lane keeps: cone_entry, lane_tables.hpp -- the rule of per-instance coefficients, too; a lane without a
+    // cone, or of a family that is off, stays 0.0 here)
+    const int ncx = (int)b->Acx.size(), ncu = (int)b->Acu.size();
+    const bool sc_on = b->set.en_state_soc != 0, ic_on = b->set.en_input_soc != 0;
+    for (int j = 0; j < nx + nu; ++j)
+        if (cone_source(b->Acx.data(), ncx, b->Acu.data(), ncu, nx, nu, j, sc_on, ic_on).family >= 0)
+            vec[VEC_CONE_MU * lw + j] = cone_entry(b->cx.data(), b->cu.data(), b->Acx.data(), ncx, b->Acu.data(), ncu, nx, nu, j, sc_on, ic_on);
     // linear-constraint slacks exist for a whole family as soon as its switch is on (admm.cpp:138-145, 176-183)
     for (int j = 0; j < nx + nu; ++j) {
         vec[VEC_LINFLAG * lw + j] = (j < nx ? b->set.en_state_linear : b->set.en_input_linear) ? 1.0 : 0.0;

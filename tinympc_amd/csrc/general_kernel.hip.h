@@ -58,6 +58,14 @@ struct GeneralArgs {
     const double* inst_lin;
     size_t il_stride;
     int il_lw, il_km, il_lv;
+    // every instance its own cone coefficients: [batch][ic_lw lanes], lane j the coefficient of the cone whose three rows include row j
+    // (lane_tables.hpp cone_entry) -- what the one-row kernel's PC forms read, and this kernel where no two cones share a row.  Cones
+    // that do share rows are walked by index, each with its own coefficient, which no lane layout can hold (two cones may start at
+    // the same row): then the caller's dense arrays are read, inst_cx [batch][ic_ns], inst_cu [batch][ic_ni] (a null one: that family
+    // kept the shared coefficients, o_sc / o_ic).  inst_cones null: the family's coefficients
+    const double* inst_cones;
+    const double *inst_cx, *inst_cu;
+    int ic_lw, ic_ns, ic_ni, ic_dense;
 };
 
 // phases of admm_phase_kernel (the batched form of the reference's exported phase functions, admm.hpp:12-17)
@@ -231,6 +239,16 @@ __device__ __forceinline__ void gk_forward(const GeneralArgs& P, const GkLds& L,
     __syncthreads();
 }
 
+// the coefficient of cone k of a family (0 state, 1 input; its first row: `first`) for instance b: the instance's own where
+// per-instance coefficients are installed (GeneralArgs::inst_cones), else the family's
+__device__ __forceinline__ double gk_cone_mu(const GeneralArgs& P, const int b, const int family, const int k, const int first) {
+    if (P.inst_cones) {
+        if (!P.ic_dense) return P.inst_cones[(size_t)b * P.ic_lw + (family ? P.nx : 0) + first];
+        const double* own = family ? P.inst_cu : P.inst_cx;
+        if (own) return own[(size_t)b * (family ? P.ic_ni : P.ic_ns) + k];
+    }
+    return P.gtab[(family ? P.o_ic : P.o_sc) + 2 * k + 1];
+}
 // cone and half-space projections of the refreshed slacks (admm.cpp:112-211): one lane per knot point,
 // constraints applied sequentially
 __device__ __forceinline__ void gk_project(const GeneralArgs& P, const int b, const size_t rec, const int lane) {
@@ -245,16 +263,18 @@ __device__ __forceinline__ void gk_project(const GeneralArgs& P, const int b, co
         double zbuf[32];
         const size_t o = rec + (size_t)i * nz;
         for (int k = 0; k < P.n_sc; ++k) {
-            vcol = P.cslack + o + (int)P.gtab[P.o_sc + 2 * k];
+            const int first = (int)P.gtab[P.o_sc + 2 * k];
+            vcol = P.cslack + o + first;
             double s3[3] = {vcol[0], vcol[1], vcol[2]};
-            soc3_inplace(s3, P.gtab[P.o_sc + 2 * k + 1]);
+            soc3_inplace(s3, gk_cone_mu(P, b, 0, k, first));
             vcol[0] = s3[0]; vcol[1] = s3[1]; vcol[2] = s3[2];
         }
         if (i < N - 1)
             for (int k = 0; k < P.n_ic; ++k) {
-                vcol = P.cslack + o + nx + (int)P.gtab[P.o_ic + 2 * k];
+                const int first = (int)P.gtab[P.o_ic + 2 * k];
+                vcol = P.cslack + o + nx + first;
                 double s3[3] = {vcol[0], vcol[1], vcol[2]};
-                soc3_inplace(s3, P.gtab[P.o_ic + 2 * k + 1]);
+                soc3_inplace(s3, gk_cone_mu(P, b, 1, k, first));
                 vcol[0] = s3[0]; vcol[1] = s3[1]; vcol[2] = s3[2];
             }
         if (P.lin_s && P.nsl > 0) {

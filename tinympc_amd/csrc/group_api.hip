@@ -326,6 +326,29 @@ int tiny_group_set_instance_tv_linear_constraints(TinyGroup* g, int ns, const do
     if (!g) return TINY_ERR_NULL;
     return group_set_instance_linear(g, 1, ns, Ax, bx, ni, Au, bu);
 }
+// every instance its own cone coefficients: the full batch axis in host memory, the caller's instance order; each shard gets its
+// instances' rows (the counts are the shards' own: the cone set every shard got from tiny_group_set_cone_constraints)
+int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, const double* cu, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags != TINY_HOST) return gfail(g, TINY_ERR_ARG, "per-instance cone coefficients of a group: host arrays (TINY_HOST)");
+    const double* src[2] = {cx, cu};
+    std::vector<double> stage[2];
+    for (int k = 0; k < g->n; ++k) {
+        const size_t per[2] = {(size_t)tiny_batch_get_option(g->shard[k], "n_state_cones"), (size_t)tiny_batch_get_option(g->shard[k], "n_input_cones")};
+        const double* from[2];
+        for (int a = 0; a < 2; ++a) {
+            from[a] = src[a] ? src[a] + (size_t)first_of(g, k) * per[a] : nullptr;
+            if (g->interleaved && src[a]) {
+                stage[a].resize((size_t)g->count[k] * per[a] + 1);
+                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
+                from[a] = stage[a].data();
+            }
+        }
+        const int rc = tiny_batch_set_instance_cone_coefficients(g->shard[k], from[0], from[1], TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

@@ -30,6 +30,7 @@ struct PathFacts {
     bool debug = false;
     bool inst_bounds = false;      // every instance its own box
     int inst_lin = 0;              // ... its own half-spaces: the sets installed AND on (a subset of lin_families)
+    bool inst_cones = false;       // ... its own cone coefficients: installed AND a cone family on
     // ---- options
     bool force_general = false, no_jit = false, no_tile = false, prefer_tile = false;
     // ---- what failed earlier on this handle
@@ -47,12 +48,14 @@ inline bool facts_consistent(const PathFacts& f) {
            (!f.entry_plain || f.has_entry) && (!f.entry_klin || (f.has_entry && f.lin_families)) &&
            (!f.fits || f.fits_box) && (f.soc || f.fits == f.fits_box) &&             // a cone costs registers
            (!f.tile_is_jit || f.has_tile) && (!f.tile_lin || (f.has_tile && f.lin_kmax != 0)) &&
-           (!f.cones_overlap || f.soc);
+           (!f.cones_overlap || f.soc) && (!f.inst_cones || f.soc);
 }
 
 enum KernelPath { ONE_ROW = 0, TILE = 1, COVERAGE = 2 };
 // what adaptive rho does not combine with; the texts callers read through tiny_batch_last_error
-enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIVE_HALFSPACES, REFUSE_ADAPTIVE_OVERLAPPING_CONES, REFUSE_ADAPTIVE_NO_REGISTER_FORM };
+// (REFUSE_ADAPTIVE_INSTANCE_CONES came last and keeps the values of the others; it is REPORTED in front of the overlapping cones: decide_path)
+enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIVE_HALFSPACES, REFUSE_ADAPTIVE_OVERLAPPING_CONES, REFUSE_ADAPTIVE_NO_REGISTER_FORM,
+                   REFUSE_ADAPTIVE_INSTANCE_CONES };
 constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
@@ -62,6 +65,11 @@ constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "overlapping cones run on the coverage kernel: no adaptive rho with them",
     "adaptive rho needs the register-resident kernel (nx+nu <= 16, horizon within the register file)",
 };
+// (a text of its own next to the table, whose five entries are listed one by one by the callers of tests/dropin/kernel_path_driver.cpp)
+constexpr const char* PATH_REFUSAL_INSTANCE_CONES =
+    "adaptive rho does not combine with per-instance cone coefficients (tiny_batch_set_instance_cone_coefficients): the adaptive cone "
+    "form has no per-instance coefficients, and the coverage kernel does not take adaptive rho";
+inline const char* path_refusal_message(PathRefusal r) { return r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r]; }
 
 struct PathDecision {
     KernelPath kernel;
@@ -69,6 +77,7 @@ struct PathDecision {
     int pl, pb;                    // ONE_ROW: the per-instance half-space / box form
     PathRefusal refusal;           // launch_solve reports it instead of launching; tiny_batch_kernel_path answers all the same
     const char* rule;              // the rule that decided
+    int pc = 0;                    // ONE_ROW: the per-instance cone-coefficient form
 };
 
 // a one-row kernel exists for the shape: compiled in (counted even under no_jit), or one that run-time instantiation can make
@@ -82,13 +91,14 @@ inline PathDecision decide_path(const PathFacts& f) {
     const PathRefusal refusal = !f.adaptive        ? REFUSE_NONE
                                 : f.inst_bounds    ? REFUSE_ADAPTIVE_INSTANCE_BOX
                                 : f.inst_lin       ? REFUSE_ADAPTIVE_HALFSPACES
+                                : f.inst_cones     ? REFUSE_ADAPTIVE_INSTANCE_CONES
                                 : f.cones_overlap  ? REFUSE_ADAPTIVE_OVERLAPPING_CONES
                                 : !regs            ? REFUSE_ADAPTIVE_NO_REGISTER_FORM
                                 : lf               ? REFUSE_ADAPTIVE_HALFSPACES          // shared ones, whether or not a one-row variant exists
                                                    : REFUSE_NONE;
-    auto one_row = [&](int lin, int pl, int pb, const char* rule) { return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule}; };
-    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule}; };
-    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule}; };
+    auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) { return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc}; };
+    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0}; };
+    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0}; };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
                          : !regs                                                              ? "cover:no_register_form"
@@ -112,11 +122,15 @@ inline PathDecision decide_path(const PathFacts& f) {
     // entry is not asked); everything else on the coverage kernel
     if (f.inst_bounds) return (f.fits_box && !f.soc && !lf && !f.debug && !f.force_general && hiprtc) ? one_row(0, 0, 1, "one_row:pb") : cover("cover:pb");
     // every instance its own half-spaces: the PL form, run-time instantiated only, where its planes and the four rows' tables fit
+    if (f.inst_lin && f.inst_cones) return cover("cover:pc_with_halfspaces");      // (PL and PC keep their pointers in one place: no form has both)
     if (f.inst_lin) {
         const bool pl_form = f.fits && !f.debug && !f.force_general && hiprtc && f.pl_planes_fit;
         if (f.adaptive) return one_row(pl_form ? lf : 0, pl_form ? 1 : 0, 0, "one_row:pl_adaptive");      // (refused)
         return pl_form ? one_row(lf, 1, 0, "one_row:pl") : cover("cover:pl");
     }
+    // every instance its own cone coefficients: the PC form of the cone variant, run-time instantiated only, with or without per-instance
+    // problem data; with shared half-spaces, on a tile-kernel shape and everywhere else on the coverage kernel (adaptive rho: refused)
+    if (f.inst_cones) return (f.fits && !lf && !f.debug && !f.force_general && hiprtc) ? one_row(0, 0, 0, "one_row:pc", 1) : cover("cover:pc");
     // adaptive rho lives on the one-row kernel only (without a register form, or with shared half-spaces: refused)
     if (f.adaptive) return one_row(no_lin ? 0 : lf, 0, 0, "one_row:adaptive");
     if (tile_can && !regs) return tile("tile:no_register_form");
@@ -135,11 +149,11 @@ inline PathDecision decide_path(const PathFacts& f) {
 }
 
 // tiny_batch_kernel_path: 0 the one-row kernel, compiled in; 1 the tile kernel; 2 the coverage kernel; 3 the one-row kernel, instantiated at
-// run time (every form with a per-instance box or half-space set is); 4 the tile kernel, instantiated at run time
+// run time (every form with a per-instance box, half-space set or cone coefficients is); 4 the tile kernel, instantiated at run time
 inline int kernel_path_code(const PathDecision& d, const PathFacts& f) {
     if (d.kernel == TILE) return f.tile_is_jit ? 4 : 1;
     if (d.kernel == COVERAGE) return 2;
-    return (f.has_entry && !f.inst_bounds && !f.inst_lin) ? 0 : 3;
+    return (f.has_entry && !f.inst_bounds && !f.inst_lin && !d.pc) ? 0 : 3;
 }
 
 }  // namespace tinympc_amd

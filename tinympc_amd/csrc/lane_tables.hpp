@@ -152,4 +152,29 @@ __host__ __device__ inline HalfspaceEntry halfspace_entry(const HalfspaceRows& s
 // the smallest power of two that holds `count` half-spaces per knot and family (at least 1): the km of a per-instance set's blocks
 __host__ __device__ constexpr int halfspace_pow2(int count) { int km = 1; while (km < count) km *= 2; return km; }
 
+// ---- cones: which cone's coefficient lane j keeps -- VEC_CONE_MU of a lane table and every instance's block [lw] of per-instance
+// cone coefficients (SolveArgs::inst_cones).  The three rows of state cone k are the lanes Acx[k] .. Acx[k] + 2, those of input cone k
+// the lanes nx + Acu[k] .. + 2; where cones share rows the last one in the caller's order holds the lane (the register kernels, which
+// read a cone's coefficient at its first lane, do not run such sets: kernel_path.hpp).  A family that is off keeps nothing.
+// family: 0 cx, 1 cu, -1 no cone; index: the cone
+struct ConeSource { int family, index; };
+__host__ __device__ inline ConeSource cone_source(const int* Acx, int n_state, const int* Acu, int n_input, int nx, int nu, int lane, bool state_on, bool input_on) {
+    const bool st = lane < nx;
+    if (lane >= nx + nu || !(st ? state_on : input_on)) return ConeSource{-1, 0};
+    const int* first = st ? Acx : Acu;
+    const int row = st ? lane : lane - nx;
+    for (int k = (st ? n_state : n_input) - 1; k >= 0; --k)
+        if (row >= first[k] && row < first[k] + 3) return ConeSource{st ? 0 : 1, k};
+    return ConeSource{-1, 0};
+}
+// ... and the coefficient it holds (cx / cu: one instance's, or the family's); 1.0 on a lane without a cone: the coefficient of the
+// register kernels' dummy item
+__host__ __device__ inline double cone_entry(const double* cx, const double* cu, const int* Acx, int n_state, const int* Acu, int n_input, int nx, int nu, int lane,
+                                             bool state_on = true, bool input_on = true) {
+    const ConeSource s = cone_source(Acx, n_state, Acu, n_input, nx, nu, lane, state_on, input_on);
+    if (s.family == 0) return cx[s.index];
+    if (s.family == 1) return cu[s.index];
+    return 1.0;
+}
+
 }  // namespace tinympc_amd

@@ -14,9 +14,11 @@ struct JitKey {
     int ub = 0;               // the knot-invariant-bounds form (round 5: for the per-instance-data variant, which is only compiled in without it)
     int pb = 0;               // every instance its own box (admm_kernel.hip.h PB): run-time instantiated only
     int pl = 0;               // every instance its own half-spaces (admm_kernel.hip.h PL): run-time instantiated only, kmax from 1
+    int pc = 0;               // every instance its own cone coefficients (admm_kernel.hip.h PC): run-time instantiated only, with soc
     bool operator<(const JitKey& o) const {
-        const int a[13] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl}, b[13] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl};
-        for (int i = 0; i < 13; ++i)
+        const int a[14] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc},
+                  b[14] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc};
+        for (int i = 0; i < 14; ++i)
             if (a[i] != b[i]) return a[i] < b[i];
         return false;
     }
@@ -66,6 +68,7 @@ struct VariantFacts {
     // ---- from the path decision
     int lin = 0;                       // the LIN template value (0: no half-space variant)
     bool pl = false, pb = false;       // the per-instance half-space / box form
+    bool pc = false;                   // the per-instance cone-coefficient form
     // ---- from the problem
     bool soc = false, debug = false;
     int dpp_mode = 0;                  // option "dpp_mode" as set (values outside 0..2 count as 0)
@@ -84,7 +87,8 @@ struct VariantFacts {
 
 // what batch_dispatch.hip can produce (a necessary condition, not a tight one): the sweep of tests/dropin/one_row_variant_driver.cpp
 // counts these combinations only.  decide_path gives pl with half-spaces only, pb for the plain box launch only, both only where
-// run-time instantiation may be tried, and refuses adaptive rho with either and with half-spaces.
+// run-time instantiation may be tried, and refuses adaptive rho with either and with half-spaces; pc for a cone launch without
+// half-spaces, a per-instance box or debug outputs only, under the same two conditions.
 inline bool variant_facts_consistent(const VariantFacts& f, const EntrySlots& s) {
     auto stride = [](int km) { return km == 4 || km == 8 || km == 16 || km == 32; };
     const bool rest = s.k[0][0][0];    // every slot but k[0][0][2], kub and the shape-dependent ones: KERNELS_FOR fills them all, KERNELS_LEAN none
@@ -100,7 +104,8 @@ inline bool variant_facts_consistent(const VariantFacts& f, const EntrySlots& s)
     return slots_ok && f.lin >= 0 && f.lin <= 3 && (!f.pl || f.lin) && !(f.pb && (f.pl || f.soc || f.lin || f.debug)) && !(f.pl && f.debug) &&
            !((f.pb || f.pl) && (f.no_jit || f.variant_jit_failed)) && !(f.adaptive && (f.pb || f.pl || f.lin)) &&
            (f.lin ? (f.pl ? f.lin_kmax == 0 || stride(f.lin_kmax) : stride(f.lin_kmax)) : f.lin_kmax == 0) &&
-           (f.pl ? f.il_km >= 1 && f.il_km <= 32 : f.il_km == 0);
+           (f.pl ? f.il_km >= 1 && f.il_km <= 32 : f.il_km == 0) &&
+           !(f.pc && (!f.soc || f.pb || f.pl || f.lin || f.debug || f.adaptive || f.no_jit || f.variant_jit_failed));
 }
 
 struct VariantChoice {
@@ -124,16 +129,18 @@ inline VariantChoice choose_one_row_variant(const VariantFacts& f, const EntrySl
     VariantChoice c;
     JitKey& k = c.key;
     const int soc = f.soc ? 1 : 0, dbg = f.debug ? 1 : 0;
-    // ---- the key: <SOC, DBG, MODE, LIN, HET, KMAX, ADAPT, UB, PB, PL>
+    // ---- the key: <SOC, DBG, MODE, LIN, HET, KMAX, ADAPT, UB, PB, PL, PC>
     k.soc = soc; k.dbg = dbg; k.mode = clamped_dpp_mode(f.dpp_mode);
     k.lin = f.lin; k.het = f.hetero ? 1 : 0; k.adapt = f.adaptive ? 1 : 0;
     k.pl = (f.lin && f.pl) ? 1 : 0;                                      // (the PL form rides on a half-space variant, at the blocks' own stride)
     k.kmax = !f.lin ? VARIANT_LIN_KMAX : k.pl ? f.il_km : f.lin_kmax;
     if (k.lin || k.het || k.adapt) k.mode = 2;                           // those variants exist on the single-chain FMA blocks only
     if (f.pb) { k.pb = 1; k.ub = (f.uniform_ub && (!f.hetero || f.het_ub)) ? 1 : 0; }
-    // ---- the rungs: which compiled-in slot holds that key (PB and PL are run-time instantiated only: the entry is not asked)
+    // (the PC form rides on the cone variant -- full rows, no PREFETCH slot --, on its UB form where the compiled-in rungs below would take one)
+    if (f.pc && f.soc) { k.pc = 1; k.ub = (!dbg && k.mode == 2 && f.uniform_ub && (!f.hetero || f.het_ub)) ? 1 : 0; }
+    // ---- the rungs: which compiled-in slot holds that key (PB, PL and PC are run-time instantiated only: the entry is not asked)
     SlotRef want;
-    if (s.has_entry && !k.pb && !k.pl) {
+    if (s.has_entry && !k.pb && !k.pl && !k.pc) {
         if (k.adapt) { if (!k.soc && !k.het) want = SlotRef{SLOT_KADAPT, dbg}; }      // (with a cone or per-instance data: run-time instantiated, jit_prebuilt.txt)
         else if (!k.lin && !k.het) want = plain_slot(f.soc, f.debug, k.mode, f.uniform_ub);
         else if (k.lin && !k.het && !dbg && k.kmax == VARIANT_LIN_KMAX) want = SlotRef{SLOT_KLIN, soc, k.lin};
