@@ -203,6 +203,32 @@ int tiny_batch_set_instance_cone_coefficients(TinyBatch* b, const double* cx, co
 /* what instance `instance` is held to, as set (whatever the enable switches say): cx [n_state_cones], cu [n_input_cones]; on a shared
  * set, and for a family that kept the shared coefficients: the shared values.  either pointer may be NULL */
 int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double* cx, double* cu);
+/* every instance its own additive disturbance sequence, applied on the device at the plant step of a closed loop (advance_x0,
+ * steps_per_launch > 1): a batch of closed loops under process noise, gusts or unmodelled forces without the host in the loop.
+ * w is [n_steps][batch][nx], step-major (a launch reads one contiguous [batch][nx] block per MPC step).  flags: TINY_HOST or TINY_DEVICE
+ * (copied; the caller may free); with TINY_BROADCAST w is ONE sequence [n_steps][nx] for every instance (expanded on the device).
+ * w == NULL or n_steps <= 0 removes the sequence and frees it.  A failed call leaves what was installed.  Synchronous; works on
+ * tiny_batch_setup and tiny_batch_setup_hetero batches.
+ * Meaning: while a sequence is installed, the plant step of MPC step k stores fl(x1 + w[k][i]) as instance i's next x0, x1 being what
+ * the undisturbed plant step stores (work->x[:,1] of that solve): one IEEE double addition, nothing fused into it.  k is the batch's
+ * disturbance step counter: the setter puts it to 0, every MPC step of a launch that takes a plant step advances it by one (inside
+ * fused launches and their stretches, too), tiny_batch_set_option("disturbance_step", k) moves it, tiny_batch_reset leaves sequence
+ * and counter alone.  Steps with k >= n_steps or k < 0 take the undisturbed plant step bit for bit (no addition, not one of zero);
+ * where no plant step happens (max_iter = 0) nothing is added and the counter still advances.  A launch without a plant step reads
+ * nothing, leaves the counter alone and runs the kernel form it runs without a sequence.  Only x0 moves: work->x and solution->x keep
+ * the solver's prediction.
+ * Read-backs (tiny_batch_get_option): "disturbance" is n_steps as installed (0: none), "disturbance_step" the counter,
+ * "last_disturbance" 1 when the last solve's launches applied the sequence (installed and a plant step taken).
+ * Where it runs: the one-row kernel's PD forms (run-time instantiated; tiny_batch_kernel_path 3) of the box, cone, half-space,
+ * per-instance-data and per-instance box / half-space / cone-coefficient forms, on full rows ("last_half_rows" and "last_prefetch"
+ * read 0); the coverage kernel -- correct, not fast -- for tile-kernel shapes, overlapping cones, "debug", "force_general", "no_jit",
+ * a missing hipRTC and whatever runs there without a sequence.  Adaptive rho on a launch with a plant step fails the solve with
+ * TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with a per-instance disturbance").
+ * Out of scope: the tile kernel (its shapes run on the coverage kernel while a disturbance applies), the half-row and PREFETCH forms,
+ * a state-dependent plant (own A_p, B_p), a per-step log of the realised x0, tiny_codegen, tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_disturbance(TinyBatch* b, const double* w, int n_steps, int flags);
+/* row `step` of instance `instance` as installed: w_out [nx]; TINY_ERR_ARG with none installed or an index outside it */
+int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out);
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -479,6 +505,9 @@ int tiny_group_set_instance_tv_linear_constraints(TinyGroup* g, int n_state, con
                                                   int n_input, const double* tv_Alin_u, const double* tv_blin_u);
 /* every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients): host, full batch axis, caller order; flags: TINY_HOST */
 int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, const double* cu, int flags);
+/* every instance its own disturbance sequence (tiny_batch_set_disturbance): host, [n_steps][batch][nx] over the full batch axis in the
+ * caller's order, or with TINY_BROADCAST one [n_steps][nx]; NULL removes.  tiny_group_set_option forwards "disturbance_step" */
+int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

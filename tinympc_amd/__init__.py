@@ -41,6 +41,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_cone_constraints", "tiny_batch_set_linear_constraints", "tiny_batch_set_tv_linear_constraints",
     "tiny_batch_set_instance_linear_constraints", "tiny_batch_set_instance_tv_linear_constraints", "tiny_batch_get_instance_linear_constraints",
     "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
+    "tiny_batch_set_disturbance", "tiny_batch_get_disturbance",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -53,7 +54,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -177,6 +178,8 @@ def lib():
         L.tiny_batch_get_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
         L.tiny_batch_set_instance_cone_coefficients.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.tiny_batch_get_instance_cone_coefficients.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+        L.tiny_batch_set_disturbance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.tiny_batch_get_disturbance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -242,6 +245,7 @@ def lib():
         L.tiny_group_set_instance_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
+        L.tiny_group_set_disturbance.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.tiny_group_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -442,6 +446,35 @@ class TinyBatchSolver:
         self._check(lib().tiny_batch_get_instance_cone_coefficients(self._h, int(i), *[v.ctypes.data_as(_dp) for v in out]),
                     "get_instance_cone_coefficients")
         return tuple(out)
+
+    def _disturbance(self, w):
+        """(n_steps, batch, nx), or (n_steps, nx) for one sequence for all -> (flat array, n_steps, broadcast flag)"""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.ndim == 2 and w.shape[1] == self.nx and w.shape[0] > 0:
+            return w.ravel(), w.shape[0], BROADCAST
+        if w.ndim != 3 or w.shape[0] == 0 or w.shape[1:] != (self.batch, self.nx):
+            raise ValueError(f"disturbance: (n_steps, {self.batch}, {self.nx}) or (n_steps, {self.nx}), got {w.shape}")
+        return w.ravel(), w.shape[0], 0
+
+    def set_disturbance(self, w):
+        """every instance its own additive disturbance at the plant step of a closed loop (advance_x0, steps_per_launch > 1): the x0
+        MPC step k hands on is x1 + w[k, i].  w: (n_steps, batch, nx), or (n_steps, nx) for one sequence for all; None removes it.
+        The step counter (option "disturbance_step") starts at 0 and advances with every plant step; steps outside w add nothing"""
+        if w is None:
+            return self._check(lib().tiny_batch_set_disturbance(self._h, None, 0, HOST), "set_disturbance")
+        flat, n, bc = self._disturbance(w)
+        self._check(lib().tiny_batch_set_disturbance(self._h, flat.ctypes.data_as(C.c_void_p), n, HOST | bc), "set_disturbance")
+
+    def set_disturbance_device(self, w, n_steps, broadcast=False):
+        """the same from a device pointer (int) to [n_steps][batch][nx] doubles ([n_steps][nx] with broadcast) resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_disturbance(self._h, C.c_void_p(int(w)), int(n_steps), DEVICE | (BROADCAST if broadcast else 0)),
+                    "set_disturbance_device")
+
+    def get_disturbance(self, step, i):
+        """w[step, i] (nx,) as installed"""
+        out = np.zeros(self.nx)
+        self._check(lib().tiny_batch_get_disturbance(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_disturbance")
+        return out
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
         """Half-spaces a_k' z <= b_k (tiny_set_linear_constraints): Alin_x (n_s, nx), blin_x (n_s,), Alin_u (n_i, nu)."""
@@ -849,6 +882,26 @@ class TinyGroupSolver:
                     raise TinyMPCError(f"get_instance_cone_coefficients failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
                 return tuple(out)
         raise TinyMPCError(f"get_instance_cone_coefficients: instance {i} of {self.batch}")
+
+    def set_disturbance(self, w):
+        """every instance its own disturbance sequence, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if w is None:
+            return self._check(lib().tiny_group_set_disturbance(self._h, None, 0, HOST), "set_disturbance")
+        flat, n, bc = TinyBatchSolver._disturbance(self, w)
+        self._check(lib().tiny_group_set_disturbance(self._h, flat.ctypes.data_as(_dp), n, HOST | bc), "set_disturbance")
+
+    def get_disturbance(self, step, i):
+        """w[step, i] of instance i (the caller's order): asked of the shard that holds it"""
+        for k in range(self.shards):
+            at = np.flatnonzero(self.shard_indices(k) == int(i))
+            if len(at):
+                h = lib().tiny_group_shard(self._h, k)
+                out = np.zeros(self.nx)
+                rc = lib().tiny_batch_get_disturbance(h, int(step), int(at[0]), out.ctypes.data_as(_dp))
+                if rc != OK:
+                    raise TinyMPCError(f"get_disturbance failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+                return out
+        raise TinyMPCError(f"get_disturbance: instance {i} of {self.batch}")
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         ai = lambda v: np.ascontiguousarray(v, dtype=np.int32)

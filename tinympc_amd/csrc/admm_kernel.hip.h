@@ -32,7 +32,7 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients; see
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients), PD (per-instance disturbance at the plant step; see
 //     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
@@ -205,7 +205,17 @@ struct SolveArgs {
         const double* inst_lin;
         const double* inst_cones;
     };
-    unsigned pf_base[8];
+    // PD forms: every instance its own additive disturbance at the plant step -- dist [dist_steps][batch][NX], step-major; MPC step
+    // `step` of this launch adds row dist_step0 + step of its INSTANCE (not its grid slot) to the x1 it hands on, where that row
+    // exists.  No PD form is a PREFETCH form, the only reader of pf_base: the pointer and its two ints lie over it, the place of the
+    // PB / PL / PC pointer stays free and PD composes with each of them
+    union {
+        unsigned pf_base[8];
+        struct {
+            const double* dist;
+            int dist_steps, dist_step0;
+        };
+    };
 };
 // (the PB / PL / PC pointers share the ticket counters' place: the argument block every compiled-in form was built against stays what it was)
 static_assert(sizeof(SolveArgs) == 472 && __builtin_offsetof(SolveArgs, het_tabs) == 208 && __builtin_offsetof(SolveArgs, pf_mask) == 416 &&
@@ -727,6 +737,13 @@ __device__ __forceinline__ void project_halfspace_columns(const int t, const int
     }
 }
 
+// the disturbed plant step of the PD forms: ONE IEEE double addition.  x1 passes through an empty asm, so that no multiply that
+// produced it can be contracted with this addition into an FMA (the undisturbed forms hand on x1 as it is)
+__device__ __forceinline__ double plant_add(double x1, const double w) {
+    asm volatile("" : "+v"(x1));
+    return x1 + w;
+}
+
 // LIN: bit 0 = static half-spaces (admm.cpp:137-173), bit 1 = time-varying ones (:176-211); 0 = neither
 // HET: per-instance problem data (riccati_kernel.hip.h): the matrix rows are re-loaded for every instance
 // ADAPT: adaptive rho (admm.cpp:397-423): per-instance rho / Kinf / Pinf, re-estimated every 5th iteration
@@ -755,6 +772,13 @@ __device__ __forceinline__ void project_halfspace_columns(const int t, const int
 // when every coefficient of the launch is a power of two would have to be decided per tile by a ballot in front of the iteration
 // loop -- the division is correct for any mix and costs only where a cone is active.  SOC forms with HET, UB and every launch form;
 // not HALF, PF, PB (box forms), PL or ADAPT.  Run-time instantiated only; bit 4 of the sixth template argument (MODE | 16).
+// PD: every instance its own additive disturbance sequence (SolveArgs::dist) -- the plant step of MPC step k hands on fl(x1 + w[k][b])
+// instead of x1: ONE double addition on the state lanes, at the two places a plant step is taken (the x0 of the next fused step, the
+// x0_next store of the launch's last one).  The value is loaded at the END of a step, behind the iteration loop, so that its latency
+// is paid once per MPC step and no register is held through the loop; a step outside the sequence adds nothing at all (wave-uniform
+// test), and so does a step that ran no iteration (max_iter = 0: no plant step).  Only x0 moves: the x|u records keep the solver's
+// prediction.  With every variant and launch form but HALF, PF and ADAPT; composes with PB, PL and PC.  Run-time instantiated only;
+// bit 5 of the sixth template argument (MODE | 32).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -765,7 +789,11 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PB = (MODE_PB & 4) != 0;
     constexpr bool PL = (MODE_PB & 8) != 0;
     constexpr bool PC = (MODE_PB & 16) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 32, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients");
+    constexpr bool PD = (MODE_PB & 32) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 64, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance");
+    static_assert(!PD || !ADAPT, "per-instance disturbance: not with adaptive rho (refused)");
+    static_assert(!PD || !HALF, "per-instance disturbance: not the half-row form");
+    static_assert(!PD || !PF, "per-instance disturbance: not the prefetch form");
     static_assert(!PC || SOC, "per-instance cone coefficients: a cone variant (SOC)");
     static_assert(!PC || (!PL && !ADAPT), "per-instance cone coefficients: not with per-instance half-spaces (coverage kernel) or adaptive rho (refused)");
     static_assert(!PL || LIN != 0, "per-instance half-spaces: a half-space variant (LIN != 0)");
@@ -1292,6 +1320,21 @@ void admm_solve_kernel(const SolveArgs P) {
             bool vp_touched = false;                           // v|z differ from what was loaded (a solve that converges at its first check leaves them alone)
             double rp = 0.0, rd = 0.0;
             const int nsteps = PF ? 1 : (P.steps > 1 ? P.steps : 1);
+            // PD: what the plant step of MPC step `at_step` hands on for this lane's x1 -- fl(x1 + w[dist_step0 + at_step][b]) on a state
+            // lane where that row exists (the test is wave-uniform: a step outside the sequence loads and adds nothing), else x1 as it
+            // is.  Called at the END of a step and at the x0_next store, and everything it needs is formed there: nothing of it
+            // lives through the iteration loop
+            auto disturbed = [&](const double x1, const int at_step) -> double {
+                const int dk = P.dist_step0 + at_step;
+                if ((unsigned)dk >= (unsigned)P.dist_steps || !is_state) return x1;
+                // (the instance index through an empty asm: what is formed from it is the same in every step of a tile, and formed
+                // once in front of the step loop it would be held -- or spilled -- through the iteration loop, as at PB and PC.  On
+                // the 32-bit index, which is alive anyway, not on the 64-bit offset: that product in front of the asm was hoisted)
+                int d_b = b;
+                asm volatile("" : "+v"(d_b));
+                return plant_add(x1, P.dist[((size_t)dk * P.batch + d_b) * NX + j]);
+            };
+            (void)disturbed;
             const int iter_first = resumed ? P.iter_base : 0;  // (a multiple of check_termination: the countdown restarts in phase)
             for (int step = 0; step < nsteps; ++step) {        // closed-loop MPC steps fused in one launch
                 X[0] = x0v;                                    // work->x.col(0) = x0
@@ -1777,6 +1820,9 @@ void admm_solve_kernel(const SolveArgs P) {
                     // plant step x0 <- A x0 + B u_0 + f (== forward_pass x_1).  Input lanes hold u_0 in slot 1: their
                     // slot 0 is the neutral dummy and must stay 0, or its "slack" would enter the dual residual
                     x0v = is_state ? X[1] : 0.0;
+                    if constexpr (PD) {                        // (a step that ran no iteration -- max_iter = 0 -- took no plant step; the last step's is the x0_next store)
+                        if (step + 1 < nsteps && iter > iter0) x0v = disturbed(x0v, step);
+                    }
                 }
             }
 
@@ -1859,6 +1905,9 @@ void admm_solve_kernel(const SolveArgs P) {
                     for (int k = 0; k < NX; ++k) P.aP[(size_t)b * (NX * NX) + k + NX * j] = sP[grp * NX * NX + k + NX * j];
                 }
             }
+            if constexpr (PD) {                              // (the plant step of the launch's LAST MPC step)
+                if (P.x0_next && acc_iter > 0 && is_state) P.x0_next[(size_t)b * NX + j] = disturbed(X[1], nsteps - 1);
+            } else
             if (P.x0_next && acc_iter > 0 && is_state) P.x0_next[(size_t)b * NX + j] = X[1];     // x1 = A x0 + B u0 + f (needs a forward pass)
             const double ps = grp_maxw<RL>(is_state ? rp : 0.0), pi = grp_maxw<RL>(is_input ? rp : 0.0);
             const double ds = grp_maxw<RL>(is_state ? rd : 0.0), di = grp_maxw<RL>(is_input ? rd : 0.0);

@@ -347,7 +347,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
                     b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_il_src[0][0], b->d_il_src[0][1], b->d_il_src[0][2], b->d_il_src[0][3],
-                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos, b->d_dist, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
     if (b->h_wire) hipHostFree(b->h_wire);
@@ -531,6 +531,55 @@ int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double
             HIP_TRY(b, hipMemcpy(dst[i], b->d_ic_src[i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
         } else for (size_t k = 0; k < n; ++k) dst[i][k] = (*shared[i])[k];
     }
+    return TINY_OK;
+}
+
+// every instance its own additive disturbance at the plant step: w [n_steps][batch][nx] (TINY_BROADCAST: [n_steps][nx], expanded on the
+// device so that the kernels know one layout), copied.  Everything that can fail happens before anything installed is touched
+int tiny_batch_set_disturbance(TinyBatch* b, const double* w, int n_steps, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
+        if (b->d_dist) {
+            HIP_TRY(b, hipStreamSynchronize(b->stream));
+            (void)hipFree(b->d_dist);
+        }
+        b->d_dist = nullptr; b->dist_steps = 0; b->dist_step = 0;
+        return TINY_OK;
+    }
+    const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row, given = (flags & TINY_BROADCAST) ? (size_t)n_steps * b->nx : full;
+    if (full / row != (size_t)n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
+        return fail(b, TINY_ERR_ARG, "disturbance: %d steps of %d instances do not fit an address", n_steps, b->batch);
+    double *fresh = nullptr, *stage = nullptr;
+    const hipMemcpyKind kind = (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    hipError_t err = hipMalloc(&fresh, full * sizeof(double));
+    int rc = TINY_OK;
+    if (err == hipSuccess && (flags & TINY_BROADCAST)) {
+        err = hipMalloc(&stage, given * sizeof(double));
+        if (err == hipSuccess) err = hipMemcpyAsync(stage, w, given * sizeof(double), kind, b->stream);
+        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps);
+    } else if (err == hipSuccess) err = hipMemcpyAsync(fresh, w, full * sizeof(double), kind, b->stream);
+    if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);      // (the caller may free its array; nothing reads the old one any more)
+    if (stage) (void)hipFree(stage);
+    if (err != hipSuccess || rc != TINY_OK) {
+        (void)hipGetLastError();
+        if (fresh) (void)hipFree(fresh);
+        return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "per-instance disturbance: %s", hipGetErrorString(err));
+    }
+    if (b->d_dist) (void)hipFree(b->d_dist);
+    b->d_dist = fresh; b->dist_steps = n_steps; b->dist_step = 0;
+    return TINY_OK;
+}
+// row `step` of instance `instance`, as set: w_out [nx]
+int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out) {
+    if (!b) return TINY_ERR_NULL;
+    if (!w_out) return fail(b, TINY_ERR_ARG, "null output");
+    if (!b->d_dist) return fail(b, TINY_ERR_ARG, "no disturbance sequence installed");
+    if (step < 0 || step >= b->dist_steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, b->dist_steps);
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(w_out, b->d_dist + ((size_t)step * b->batch + instance) * b->nx, b->nx * sizeof(double), hipMemcpyDeviceToHost));
     return TINY_OK;
 }
 
@@ -1112,6 +1161,7 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "repack_sort")) { if (value < -1 || value > 1) return fail(b, TINY_ERR_ARG, "repack_sort: 1, 0 or -1 (automatic)"); b->repack_sort = (int)value; }
     else if (!strcmp(name, "repack_dynamic")) b->repack_dynamic = value != 0;   // follow-up stages: tiles off a counter (1) or a fixed grid stride (0)
     else if (!strcmp(name, "traj_step")) b->traj_step = value;
+    else if (!strcmp(name, "disturbance_step")) b->dist_step = value;       // the row of the disturbance sequence the next plant step takes (outside it: none)
     else if (!strcmp(name, "timing")) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));
         while ((long)b->ev_start.size() < value) {
@@ -1257,6 +1307,9 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "n_input_cones")) return (long)b->Acu.size();
     if (!strcmp(name, "instance_cones")) return b->inst_cones ? 1 : 0;          // per-instance cone coefficients are installed (tiny_batch_set_instance_cone_coefficients)
     if (!strcmp(name, "last_instance_cones")) return b->last_inst_cones ? 1 : 0;   // the last solve's kernel read them: installed and a cone family on
+    if (!strcmp(name, "disturbance")) return b->d_dist ? b->dist_steps : 0;   // steps of the per-instance disturbance sequence installed (tiny_batch_set_disturbance); 0: none
+    if (!strcmp(name, "disturbance_step")) return b->dist_step;               // the row the next plant step takes
+    if (!strcmp(name, "last_disturbance")) return b->last_dist ? 1 : 0;       // the last solve's launches applied the sequence: installed and a plant step taken
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;

@@ -39,6 +39,11 @@ int inst_lin_kmax(const TinyBatch* b);     // the block stride of a per-instance
 // has changed it (enqueued on the batch's stream)
 bool inst_cones_active(const TinyBatch* b);
 int ensure_instance_cones(TinyBatch* b);
+// every instance its own disturbance at the plant step: installed AND the next launch takes a plant step (advance_x0, or fused steps) /
+// the row its first MPC step takes, as the kernels' int / a broadcast sequence [n_steps][nx] expanded to [n_steps][batch][nx]
+bool disturbance_active(const TinyBatch* b);
+int dist_step_base(const TinyBatch* b);
+int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps);
 int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
 // ---- lane tables (batch_tables.hip)
 struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)

@@ -305,6 +305,24 @@ int ensure_instance_cones(TinyBatch* b) {
     return TINY_OK;
 }
 
+// ---- every instance its own disturbance at the plant step (tiny_batch_set_disturbance): one sequence for all, seq [n_steps][nx], written
+// out as the layout the kernels read, out [n_steps][batch][nx]; one thread per element (enqueued on the batch's stream)
+static __global__ __launch_bounds__(256) void expand_disturbance_kernel(double* __restrict__ out, const double* __restrict__ seq, size_t total, int batch, int nx) {
+    const size_t row = (size_t)batch * nx;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
+        out[e] = seq[(e / row) * nx + e % nx];
+}
+int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps) {
+    const size_t total = (size_t)n_steps * b->batch * b->nx;
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
+    hipLaunchKernelGGL(expand_disturbance_kernel, dim3(grid), dim3(256), 0, b->stream, out, seq, total, b->batch, b->nx);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
+bool disturbance_active(const TinyBatch* b) { return b->d_dist && b->dist_steps > 0 && (b->advance_x0 || b->steps_per_launch > 1); }
+// (the kernels count steps in an int; a counter moved beyond +-2^30 is outside every sequence either way)
+int dist_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->dist_step, -(1L << 30), 1L << 30); }
+
 // histogram of the iteration counts the solve just enqueued leaves in d_status -> pinned host memory, asynchronously (hist_ev)
 int enqueue_iteration_histogram(TinyBatch* b) {
     if (!b->d_hist) {

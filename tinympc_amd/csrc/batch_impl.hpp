@@ -147,6 +147,14 @@ struct TinyBatch {
     int* d_ic_pos = nullptr;
     size_t ic_stage_doubles = 0;
     bool last_inst_cones = false;                  // the last solve's kernel read them
+    // every instance its own additive disturbance at the plant step (tiny_batch_set_disturbance): d_dist [dist_steps][batch][nx],
+    // step-major -- a launch reads one contiguous [batch][nx] block per MPC step; a broadcast sequence is expanded to that layout by
+    // batch_helpers.hip.  dist_step: the row the next plant step takes (the setter rewinds it, option "disturbance_step" moves it,
+    // every MPC step of a launch with a plant step advances it, tiny_batch_reset leaves it alone); rows outside [0, dist_steps) add nothing
+    double* d_dist = nullptr;
+    int dist_steps = 0;
+    long dist_step = 0;
+    bool last_dist = false;                        // the last solve's launches applied the sequence: installed and a plant step taken
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -66,6 +66,9 @@ struct GeneralArgs {
     const double* inst_cones;
     const double *inst_cx, *inst_cu;
     int ic_lw, ic_ns, ic_ni, ic_dense;
+    // every instance its own disturbance at the plant step: THIS step's block [batch][nx] of the sequence (the host loop that runs fused
+    // steps as single-step launches passes each step's own).  null: the undisturbed plant step
+    const double* dist;
 };
 
 // phases of admm_phase_kernel (the batched form of the reference's exported phase functions, admm.hpp:12-17)
@@ -446,7 +449,8 @@ __global__ __launch_bounds__(64) void admm_general_kernel(const GeneralArgs P) {
                 P.pd[rec + e] = sPD[e];
             }
         }
-        if (P.x0_next && iter > 0 && is_state) P.x0_next[(size_t)b * nx + lane] = sX[nz + lane];
+        // the plant step hands on x1, or fl(x1 + w) (one addition of two loaded values: nothing to contract); the records keep x1
+        if (P.x0_next && iter > 0 && is_state) P.x0_next[(size_t)b * nx + lane] = P.dist ? sX[nz + lane] + P.dist[(size_t)b * nx + lane] : sX[nz + lane];
         if (lane == 0) {
             P.status[b] = make_int4(iter, solved, solved ? 1 : 11, checked);
             *reinterpret_cast<double4*>(P.resid + (size_t)b * 4) = make_double4(r_ps, r_pi, r_ds, r_di);

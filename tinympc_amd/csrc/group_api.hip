@@ -349,6 +349,26 @@ int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, co
     }
     return TINY_OK;
 }
+// every instance its own disturbance at the plant step: w [n_steps][batch][nx] over the full batch axis in host memory, the caller's
+// instance order; each shard gets [n_steps][its count][nx] (TINY_BROADCAST: the one sequence, as it is); NULL / n_steps <= 0 removes
+int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "per-instance disturbance of a group: host arrays (TINY_HOST)");
+    const bool pass = !w || n_steps <= 0 || (flags & TINY_BROADCAST);
+    const size_t nx = (size_t)g->nx;
+    for (int k = 0; k < g->n; ++k) {
+        if (!pass) {
+            const size_t cnt = (size_t)g->count[k];
+            g->stage.resize((size_t)n_steps * cnt * nx + 1);
+            for (int s = 0; s < n_steps; ++s)
+                for (size_t i = 0; i < cnt; ++i)
+                    memcpy(g->stage.data() + ((size_t)s * cnt + i) * nx, w + ((size_t)s * g->batch + (size_t)global_index(g, k, (long)i)) * nx, nx * sizeof(double));
+        }
+        const int rc = tiny_batch_set_disturbance(g->shard[k], pass ? w : g->stage.data(), n_steps, pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {
