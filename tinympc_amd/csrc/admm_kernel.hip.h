@@ -193,12 +193,12 @@ struct SolveArgs {
     // launch, pf_base[x] is where this launch's begin (the host keeps the sums)
     int pf_mask, pf_shards, pf_static;
     // one-row kernel, PB forms: every instance its own box -- [batch][lo | hi][N slots][16 lanes], the slot convention of the shared table's
-    // bounds block (lane_tables.hpp box_entry; built by batch_helpers.hip from the caller's arrays).  PB and PF exclude each other, so the
+    // bounds block (lane_tables.hpp box_entry; built by batch_instance.hip from the caller's arrays).  PB and PF exclude each other, so the
     // pointer takes the place of the PREFETCH form's ticket counters: the argument block of every other form keeps its size and offsets
     // PL forms: every instance its own half-spaces -- [batch][the blocks of the form's LIN sets: static [3][KMAX][16], then [N][3][KMAX][16]]
-    // (lane_tables.hpp halfspace_entry; built by batch_helpers.hip).  PL excludes PF and PB alike, so it shares their place
+    // (lane_tables.hpp halfspace_entry; built by batch_instance.hip).  PL excludes PF and PB alike, so it shares their place
     // PC forms: every instance its own cone coefficients -- [batch][16 lanes], lane j the coefficient of the cone whose rows include lane j
-    // (lane_tables.hpp cone_entry; built by batch_helpers.hip).  PF and PB are box forms, PL + PC is not built: the same place again
+    // (lane_tables.hpp cone_entry; built by batch_instance.hip).  PF and PB are box forms, PL + PC is not built: the same place again
     union {
         unsigned* pf_counter;
         const double* inst_bounds;

@@ -346,10 +346,10 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_iter_log, b->d_u0_log, b->d_lslack, b->d_ldual, b->d_tlslack, b->d_tldual, b->d_gtab, b->d_traj,
                     b->d_traj_offsets, b->d_hA, b->d_hB, b->d_hf, b->d_hQw, b->d_hRw, b->d_hrho, b->d_hK, b->d_hP, b->d_hQuu,
                     b->d_hAmBKt, b->d_hAPf, b->d_hBPf, b->d_het_tabs, b->d_hiters, b->d_ttab, b->d_repack_index, b->d_repack_count,
-                    b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2], b->d_ib_src[3], b->d_inst_bounds, b->d_ib_flag, b->d_il_src[0][0], b->d_il_src[0][1], b->d_il_src[0][2], b->d_il_src[0][3],
-                    b->d_il_src[1][0], b->d_il_src[1][1], b->d_il_src[1][2], b->d_il_src[1][3], b->d_inst_lin, b->d_il_stage, b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos, b->d_dist, b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
+                    b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
+    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist);   // (each names its own: batch_impl.hpp each_buffer)
     if (b->h_wire) hipHostFree(b->h_wire);
     if (b->d_hist) hipFree(b->d_hist);
     if (b->h_hist) hipHostFree(b->h_hist);
@@ -378,78 +378,8 @@ int tiny_batch_set_bound_constraints(TinyBatch* b, const double* x_min, const do
     b->x_min.assign(x_min, x_min + ns); b->x_max.assign(x_max, x_max + ns);
     b->u_min.assign(u_min, u_min + ni); b->u_max.assign(u_max, u_max + ni);
     b->have_bounds = true;
-    if (b->inst_bounds || b->d_inst_bounds || b->d_ib_src[0]) {
-        // the latest setter wins: the shared box replaces a per-instance one, whose device arrays (at 65 536 quadrotors: 168 MB + the
-        // caller's four) go once the stream has run dry of their readers
-        b->inst_bounds = false; b->inst_bounds_dirty = false;
-        HIP_TRY(b, hipSetDevice(b->device));
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        for (double*& p : b->d_ib_src) { if (p) (void)hipFree(p); p = nullptr; }
-        if (b->d_inst_bounds) (void)hipFree(b->d_inst_bounds);
-        b->d_inst_bounds = nullptr;
-    }
+    if (int rc = drop_instance_bounds(b)) return rc;     // (the latest setter wins: the shared box replaces a per-instance one)
     b->tab_dirty = true;
-    return TINY_OK;
-}
-
-// every instance its own box.  The caller's arrays are kept on the device as given; what the kernels read is built from them at once
-// (ensure_instance_bounds: synchronous, it reads the knot-invariance flag back) and again when an enable switch changes.  The shared box
-// is given up only once that has succeeded: a call that fails leaves the batch on the shared box it had (a per-instance box it had
-// before is gone: its arrays were being overwritten)
-int tiny_batch_set_instance_bounds(TinyBatch* b, const double* x_min, const double* x_max, const double* u_min, const double* u_max, int flags) {
-    if (!b) return TINY_ERR_NULL;
-    if (!x_min || !x_max || !u_min || !u_max) return fail(b, TINY_ERR_NULL, "null bound pointer");
-    if (flags & TINY_BROADCAST) return fail(b, TINY_ERR_ARG, "one box for every instance: tiny_batch_set_bound_constraints");
-    HIP_TRY(b, hipSetDevice(b->device));
-    const size_t n[4] = {(size_t)b->batch * b->N * b->nx, (size_t)b->batch * b->N * b->nx, (size_t)b->batch * (b->N - 1) * b->nu, (size_t)b->batch * (b->N - 1) * b->nu};
-    const double* src[4] = {x_min, x_max, u_min, u_max};
-    b->inst_bounds = false;
-    for (int i = 0; i < 4; ++i) {
-        if (!b->d_ib_src[i]) HIP_TRY(b, hipMalloc(&b->d_ib_src[i], std::max<size_t>(n[i], 1) * sizeof(double)));
-        HIP_TRY(b, hipMemcpyAsync(b->d_ib_src[i], src[i], n[i] * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream));
-    }
-    b->inst_bounds = true; b->inst_bounds_dirty = true;
-    b->tab_dirty = true;
-    if (int rc = ensure_instance_bounds(b)) { b->inst_bounds = false; return rc; }
-    b->have_bounds = false;                          // (the latest setter wins: the shared box is gone)
-    b->x_min.clear(); b->x_max.clear(); b->u_min.clear(); b->u_max.clear();
-    return TINY_OK;
-}
-
-int tiny_batch_get_instance_bounds(TinyBatch* b, int instance, double* x_min, double* x_max, double* u_min, double* u_max) {
-    if (!b) return TINY_ERR_NULL;
-    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    const size_t ns = (size_t)b->N * b->nx, ni = (size_t)(b->N - 1) * b->nu;
-    double* dst[4] = {x_min, x_max, u_min, u_max};
-    if (b->inst_bounds) {
-        HIP_TRY(b, hipSetDevice(b->device));
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        for (int i = 0; i < 4; ++i) {
-            const size_t n = i < 2 ? ns : ni;
-            if (dst[i]) HIP_TRY(b, hipMemcpy(dst[i], b->d_ib_src[i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return TINY_OK;
-    }
-    const std::vector<double>* shared[4] = {&b->x_min, &b->x_max, &b->u_min, &b->u_max};
-    for (int i = 0; i < 4; ++i) {
-        if (!dst[i]) continue;
-        const size_t n = i < 2 ? ns : ni;
-        const double none = (i & 1) ? std::numeric_limits<double>::infinity() : -std::numeric_limits<double>::infinity();
-        for (size_t e = 0; e < n; ++e) dst[i][e] = b->have_bounds ? (*shared[i])[e] : none;      // (never set: (-inf, +inf))
-    }
-    return TINY_OK;
-}
-
-// tiny_batch_set_cone_constraints is about to install one coefficient set for all (and, maybe, other cones): per-instance coefficients
-// go, their arrays freed once the stream has run dry of their readers
-static int drop_instance_cones(TinyBatch* b) {
-    if (!b->inst_cones && !b->d_inst_cones && !b->d_ic_src[0] && !b->d_ic_src[1]) return TINY_OK;
-    HIP_TRY(b, hipSetDevice(b->device));
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    void* gone[] = {b->d_ic_src[0], b->d_ic_src[1], b->d_inst_cones, b->d_ic_stage, b->d_ic_pos};
-    for (void* p : gone) if (p) (void)hipFree(p);
-    b->d_ic_src[0] = b->d_ic_src[1] = nullptr; b->d_inst_cones = nullptr; b->d_ic_stage = nullptr; b->d_ic_pos = nullptr; b->ic_stage_doubles = 0;
-    b->inst_cones = false; b->inst_cones_dirty = false;
     return TINY_OK;
 }
 
@@ -483,106 +413,6 @@ int tiny_batch_set_cone_constraints(TinyBatch* b, int nsc, const int* Acx, const
     return TINY_OK;
 }
 
-// every instance its own cone coefficients on the cones tiny_batch_set_cone_constraints installed.  The caller's arrays are kept on the
-// device as given (the coverage kernel reads them so); the block the one-row kernel reads is built from them in front of the next
-// launch (ensure_instance_cones).  Everything that can fail happens before anything installed is touched
-int tiny_batch_set_instance_cone_coefficients(TinyBatch* b, const double* cx, const double* cu, int flags) {
-    if (!b) return TINY_ERR_NULL;
-    if (b->Acx.empty() && b->Acu.empty()) return fail(b, TINY_ERR_ARG, "no cone set installed: tiny_batch_set_cone_constraints first");
-    if (flags & TINY_BROADCAST) return fail(b, TINY_ERR_ARG, "one coefficient for every instance: tiny_batch_set_cone_constraints");
-    const size_t cnt[2] = {b->Acx.size(), b->Acu.size()};
-    const double* src[2] = {cnt[0] ? cx : nullptr, cnt[1] ? cu : nullptr};
-    if (!src[0] && !src[1]) return fail(b, TINY_ERR_ARG, "null coefficient arrays for every cone family that has cones");
-    HIP_TRY(b, hipSetDevice(b->device));
-    double* fresh[2] = {nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 2 && err == hipSuccess; ++i) {
-        if (!src[i]) continue;
-        const size_t n = (size_t)b->batch * cnt[i];
-        err = hipMalloc(&fresh[i], n * sizeof(double));
-        if (err == hipSuccess) err = hipMemcpyAsync(fresh[i], src[i], n * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);      // (the caller may free its arrays; nothing reads the old ones any more)
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        for (double* p : fresh) if (p) (void)hipFree(p);
-        return fail(b, TINY_ERR_HIP, "per-instance cone coefficients: %s", hipGetErrorString(err));
-    }
-    for (int i = 0; i < 2; ++i) {                                        // (the latest setter wins: a family passed as NULL is back on the shared coefficients)
-        if (b->d_ic_src[i]) (void)hipFree(b->d_ic_src[i]);
-        b->d_ic_src[i] = fresh[i];
-    }
-    b->inst_cones = true; b->inst_cones_dirty = true;
-    b->tab_dirty = true;
-    return TINY_OK;
-}
-// what instance `instance` is held to, as set (whatever the switches say); on a shared set, or for a family that kept it: the shared values
-int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double* cx, double* cu) {
-    if (!b) return TINY_ERR_NULL;
-    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    double* dst[2] = {cx, cu};
-    const std::vector<double>* shared[2] = {&b->cx, &b->cu};
-    for (int i = 0; i < 2; ++i) {
-        const size_t n = shared[i]->size();
-        if (!dst[i] || !n) continue;
-        if (b->inst_cones && b->d_ic_src[i]) {
-            HIP_TRY(b, hipSetDevice(b->device));
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
-            HIP_TRY(b, hipMemcpy(dst[i], b->d_ic_src[i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
-        } else for (size_t k = 0; k < n; ++k) dst[i][k] = (*shared[i])[k];
-    }
-    return TINY_OK;
-}
-
-// every instance its own additive disturbance at the plant step: w [n_steps][batch][nx] (TINY_BROADCAST: [n_steps][nx], expanded on the
-// device so that the kernels know one layout), copied.  Everything that can fail happens before anything installed is touched
-int tiny_batch_set_disturbance(TinyBatch* b, const double* w, int n_steps, int flags) {
-    if (!b) return TINY_ERR_NULL;
-    HIP_TRY(b, hipSetDevice(b->device));
-    if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
-        if (b->d_dist) {
-            HIP_TRY(b, hipStreamSynchronize(b->stream));
-            (void)hipFree(b->d_dist);
-        }
-        b->d_dist = nullptr; b->dist_steps = 0; b->dist_step = 0;
-        return TINY_OK;
-    }
-    const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row, given = (flags & TINY_BROADCAST) ? (size_t)n_steps * b->nx : full;
-    if (full / row != (size_t)n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
-        return fail(b, TINY_ERR_ARG, "disturbance: %d steps of %d instances do not fit an address", n_steps, b->batch);
-    double *fresh = nullptr, *stage = nullptr;
-    const hipMemcpyKind kind = (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    hipError_t err = hipMalloc(&fresh, full * sizeof(double));
-    int rc = TINY_OK;
-    if (err == hipSuccess && (flags & TINY_BROADCAST)) {
-        err = hipMalloc(&stage, given * sizeof(double));
-        if (err == hipSuccess) err = hipMemcpyAsync(stage, w, given * sizeof(double), kind, b->stream);
-        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps);
-    } else if (err == hipSuccess) err = hipMemcpyAsync(fresh, w, full * sizeof(double), kind, b->stream);
-    if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);      // (the caller may free its array; nothing reads the old one any more)
-    if (stage) (void)hipFree(stage);
-    if (err != hipSuccess || rc != TINY_OK) {
-        (void)hipGetLastError();
-        if (fresh) (void)hipFree(fresh);
-        return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "per-instance disturbance: %s", hipGetErrorString(err));
-    }
-    if (b->d_dist) (void)hipFree(b->d_dist);
-    b->d_dist = fresh; b->dist_steps = n_steps; b->dist_step = 0;
-    return TINY_OK;
-}
-// row `step` of instance `instance`, as set: w_out [nx]
-int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out) {
-    if (!b) return TINY_ERR_NULL;
-    if (!w_out) return fail(b, TINY_ERR_ARG, "null output");
-    if (!b->d_dist) return fail(b, TINY_ERR_ARG, "no disturbance sequence installed");
-    if (step < 0 || step >= b->dist_steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, b->dist_steps);
-    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    HIP_TRY(b, hipSetDevice(b->device));
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    HIP_TRY(b, hipMemcpy(w_out, b->d_dist + ((size_t)step * b->batch + instance) * b->nx, b->nx * sizeof(double), hipMemcpyDeviceToHost));
-    return TINY_OK;
-}
-
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear,
@@ -594,8 +424,7 @@ int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_
     b->set.en_state_linear = en_state_linear; b->set.en_input_linear = en_input_linear;
     b->set.en_tv_state_linear = en_tv_state_linear; b->set.en_tv_input_linear = en_tv_input_linear;
     b->tab_dirty = true;
-    if (b->inst_bounds) b->inst_bounds_dirty = true;   // (a disabled family is (-inf, +inf) in the array the kernels read)
-    b->il_full = true;                                 // (... and blank in a per-instance set's blocks, whose stride follows the enabled counts)
+    instance_data_settings_changed(b);
     return TINY_OK;
 }
 
@@ -604,113 +433,6 @@ static void rows_of(const double* colmajor, int n, int cols, std::vector<double>
     out->assign((size_t)n * cols, 0.0);
     for (int k = 0; k < n; ++k)
         for (int c = 0; c < cols; ++c) (*out)[(size_t)k * cols + c] = colmajor[(size_t)c * n + k];
-}
-
-// a shared setter of set `set` (0 static, 1 time-varying) is about to install one set for all: a per-instance set goes, its arrays
-// freed once the stream has run dry of their readers; the other set, if it is per instance, has its blocks rebuilt (they hold both)
-static int drop_instance_linear(TinyBatch* b, int set) {
-    if (b->inst_lin[set]) {
-        HIP_TRY(b, hipSetDevice(b->device));
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        for (double*& p : b->d_il_src[set]) { if (p) (void)hipFree(p); p = nullptr; }
-        b->inst_lin[set] = false;
-        if (!b->inst_lin[1 - set]) {
-            if (b->d_inst_lin) (void)hipFree(b->d_inst_lin);
-            if (b->d_il_stage) (void)hipFree(b->d_il_stage);
-            b->d_inst_lin = nullptr; b->d_il_stage = nullptr; b->il_doubles = 0; b->il_stage_doubles = 0;
-        }
-    }
-    b->il_full = true; b->il_offsets = 0;
-    return TINY_OK;
-}
-
-// every instance its own half-spaces, set 0 (static) or 1 (time-varying).  The caller's arrays are kept on the device as given; what
-// the kernels read is built from them in front of the next launch (ensure_instance_linear).  Everything that can fail -- the checks,
-// the allocations, the copies -- happens before anything installed is touched: a failed call leaves what was installed.
-// A == NULL for every family with a positive count: the offsets-only update (the counts must be the installed ones)
-static int set_instance_linear(TinyBatch* b, int set, int n_state, const double* A_x, const double* b_x, int n_input, const double* A_u, const double* b_u,
-                               int flags) {
-    if (n_state < 0 || n_input < 0) return fail(b, TINY_ERR_DIM, "negative constraint count");
-    if (flags & TINY_BROADCAST)
-        return fail(b, TINY_ERR_ARG, "one set for every instance: %s", set ? "tiny_batch_set_tv_linear_constraints" : "tiny_batch_set_linear_constraints");
-    if ((n_state > 0 && !b_x) || (n_input > 0 && !b_u)) return fail(b, TINY_ERR_NULL, "null offsets with a positive count");
-    const int cnt[2] = {n_state, n_input};
-    const double* src[4] = {A_x, b_x, A_u, b_u};
-    const int have[2] = {set ? b->ntsl : b->nsl, set ? b->ntil : b->nil};
-    bool offsets_only[2];
-    for (int fam = 0; fam < 2; ++fam) {
-        offsets_only[fam] = cnt[fam] > 0 && !src[2 * fam];
-        if (offsets_only[fam] && (!b->inst_lin[set] || have[0] != n_state || have[1] != n_input))
-            return fail(b, TINY_ERR_ARG, "null coefficients: the offsets-only update needs a per-instance set of the same counts installed (%d, %d)", n_state, n_input);
-    }
-    HIP_TRY(b, hipSetDevice(b->device));
-    const size_t knots[2] = {set ? (size_t)b->N : 1, set ? (size_t)b->N - 1 : 1};
-    double* fresh[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipError_t err = hipSuccess;
-    for (int i = 0; i < 4 && err == hipSuccess; ++i) {
-        const int fam = i / 2;
-        if (!src[i] || cnt[fam] == 0) continue;
-        const size_t n = (size_t)b->batch * cnt[fam] * knots[fam] * ((i & 1) ? 1 : (fam ? b->nu : b->nx));
-        err = hipMalloc(&fresh[i], std::max<size_t>(n, 1) * sizeof(double));
-        if (err == hipSuccess) err = hipMemcpyAsync(fresh[i], src[i], n * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
-    }
-    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);      // (the caller may free its arrays; nothing reads the old ones any more)
-    if (err != hipSuccess) {
-        (void)hipGetLastError();
-        for (double* p : fresh) if (p) (void)hipFree(p);
-        return fail(b, TINY_ERR_HIP, "per-instance half-spaces: %s", hipGetErrorString(err));
-    }
-    for (int i = 0; i < 4; ++i) {
-        if (offsets_only[i / 2] && !(i & 1)) continue;                   // (this family keeps its coefficients)
-        if (b->d_il_src[set][i]) (void)hipFree(b->d_il_src[set][i]);
-        b->d_il_src[set][i] = fresh[i];
-    }
-    const bool all_offsets = (offsets_only[0] || cnt[0] == 0) && (offsets_only[1] || cnt[1] == 0) && (cnt[0] > 0 || cnt[1] > 0);
-    if (all_offsets) b->il_offsets |= ((offsets_only[0] ? 1 : 0) | (offsets_only[1] ? 2 : 0)) << (2 * set);
-    else b->il_full = true;
-    b->inst_lin[set] = true;
-    if (set) { b->ntsl = n_state; b->ntil = n_input; b->tvA_x.clear(); b->tvb_x.clear(); b->tvA_u.clear(); b->tvb_u.clear(); }
-    else { b->nsl = n_state; b->nil = n_input; b->Alin_x.clear(); b->blin_x.clear(); b->Alin_u.clear(); b->blin_u.clear(); }
-    b->tab_dirty = true;
-    return TINY_OK;
-}
-int tiny_batch_set_instance_linear_constraints(TinyBatch* b, int n_state, const double* Alin_x, const double* blin_x, int n_input,
-                                               const double* Alin_u, const double* blin_u, int flags) {
-    if (!b) return TINY_ERR_NULL;
-    return set_instance_linear(b, 0, n_state, Alin_x, blin_x, n_input, Alin_u, blin_u, flags);
-}
-int tiny_batch_set_instance_tv_linear_constraints(TinyBatch* b, int n_state, const double* tv_Alin_x, const double* tv_blin_x, int n_input,
-                                                  const double* tv_Alin_u, const double* tv_blin_u, int flags) {
-    if (!b) return TINY_ERR_NULL;
-    return set_instance_linear(b, 1, n_state, tv_Alin_x, tv_blin_x, n_input, tv_Alin_u, tv_blin_u, flags);
-}
-// what instance `instance` is held to by set `tv` (0 static, 1 time-varying), as set -- whatever the switches say -- in the shared
-// setter's layout; on a shared set: the shared one.  any pointer may be NULL
-int tiny_batch_get_instance_linear_constraints(TinyBatch* b, int instance, int tv, double* A_x, double* b_x, double* A_u, double* b_u) {
-    if (!b) return TINY_ERR_NULL;
-    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    if (tv != 0 && tv != 1) return fail(b, TINY_ERR_ARG, "set %d: 0 static, 1 time-varying", tv);
-    const int cnt[2] = {tv ? b->ntsl : b->nsl, tv ? b->ntil : b->nil};
-    const size_t rows[2] = {(size_t)cnt[0] * (tv ? b->N : 1), (size_t)cnt[1] * (tv ? b->N - 1 : 1)};
-    double* dst[4] = {A_x, b_x, A_u, b_u};
-    if (b->inst_lin[tv]) {
-        HIP_TRY(b, hipSetDevice(b->device));
-        HIP_TRY(b, hipStreamSynchronize(b->stream));
-        for (int i = 0; i < 4; ++i) {
-            const size_t n = rows[i / 2] * ((i & 1) ? 1 : (i / 2 ? b->nu : b->nx));
-            if (dst[i] && n) HIP_TRY(b, hipMemcpy(dst[i], b->d_il_src[tv][i] + (size_t)instance * n, n * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return TINY_OK;
-    }
-    const std::vector<double>* shared[4] = {tv ? &b->tvA_x : &b->Alin_x, tv ? &b->tvb_x : &b->blin_x, tv ? &b->tvA_u : &b->Alin_u, tv ? &b->tvb_u : &b->blin_u};
-    for (int i = 0; i < 4; ++i) {
-        if (!dst[i]) continue;
-        const size_t r = rows[i / 2], cols = i / 2 ? b->nu : b->nx;
-        if (i & 1) { for (size_t k = 0; k < r; ++k) dst[i][k] = (*shared[i])[k]; }
-        else for (size_t k = 0; k < r; ++k)                                 // (the host copies are row-major: rows_of)
-            for (size_t c = 0; c < cols; ++c) dst[i][c * r + k] = (*shared[i])[k * cols + c];
-    }
-    return TINY_OK;
 }
 
 int tiny_batch_set_linear_constraints(TinyBatch* b, int n_state, const double* Alin_x, const double* blin_x, int n_input,
@@ -1161,7 +883,7 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "repack_sort")) { if (value < -1 || value > 1) return fail(b, TINY_ERR_ARG, "repack_sort: 1, 0 or -1 (automatic)"); b->repack_sort = (int)value; }
     else if (!strcmp(name, "repack_dynamic")) b->repack_dynamic = value != 0;   // follow-up stages: tiles off a counter (1) or a fixed grid stride (0)
     else if (!strcmp(name, "traj_step")) b->traj_step = value;
-    else if (!strcmp(name, "disturbance_step")) b->dist_step = value;       // the row of the disturbance sequence the next plant step takes (outside it: none)
+    else if (!strcmp(name, "disturbance_step")) b->dist.step = value;       // the row of the disturbance sequence the next plant step takes (outside it: none)
     else if (!strcmp(name, "timing")) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));
         while ((long)b->ev_start.size() < value) {
@@ -1295,21 +1017,21 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_half_rows")) return b->last_half ? 1 : 0;       // the last one-row launch took the HALF form (two instances per DPP row)
     if (!strcmp(name, "last_tile_form")) return b->last_tile_form;          // W * 1e6 + R * 1e3 + LM of the tile_dims.txt entry the last tile launch took (-1: run-time instantiated)
     if (!strcmp(name, "last_tile_dyn")) return b->last_tile_dyn ? 1 : 0;      // the last tile-kernel launch took the dynamic slot form
-    if (!strcmp(name, "instance_bounds")) return b->inst_bounds ? 1 : 0;        // a per-instance box is installed (tiny_batch_set_instance_bounds)
-    if (!strcmp(name, "last_instance_bounds")) return b->last_inst_bounds ? 1 : 0;   // the last solve's kernel read a per-instance box
+    if (!strcmp(name, "instance_bounds")) return b->ibox.on ? 1 : 0;        // a per-instance box is installed (tiny_batch_set_instance_bounds)
+    if (!strcmp(name, "last_instance_bounds")) return b->ibox.last ? 1 : 0;   // the last solve's kernel read a per-instance box
     if (!strcmp(name, "n_state_linear")) return b->nsl;                         // half-space counts as set (per knot for the time-varying set)
     if (!strcmp(name, "n_input_linear")) return b->nil;
     if (!strcmp(name, "n_tv_state_linear")) return b->ntsl;
     if (!strcmp(name, "n_tv_input_linear")) return b->ntil;
-    if (!strcmp(name, "instance_linear")) return (b->inst_lin[0] ? 1 : 0) | (b->inst_lin[1] ? 2 : 0);   // per-instance half-space sets installed: 1 static, 2 time-varying
-    if (!strcmp(name, "last_instance_linear")) return b->last_inst_lin;       // the same mask for what the last solve's kernel read
+    if (!strcmp(name, "instance_linear")) return (b->ilin.on[0] ? 1 : 0) | (b->ilin.on[1] ? 2 : 0);   // per-instance half-space sets installed: 1 static, 2 time-varying
+    if (!strcmp(name, "last_instance_linear")) return b->ilin.last;       // the same mask for what the last solve's kernel read
     if (!strcmp(name, "n_state_cones")) return (long)b->Acx.size();              // cone counts as set
     if (!strcmp(name, "n_input_cones")) return (long)b->Acu.size();
-    if (!strcmp(name, "instance_cones")) return b->inst_cones ? 1 : 0;          // per-instance cone coefficients are installed (tiny_batch_set_instance_cone_coefficients)
-    if (!strcmp(name, "last_instance_cones")) return b->last_inst_cones ? 1 : 0;   // the last solve's kernel read them: installed and a cone family on
-    if (!strcmp(name, "disturbance")) return b->d_dist ? b->dist_steps : 0;   // steps of the per-instance disturbance sequence installed (tiny_batch_set_disturbance); 0: none
-    if (!strcmp(name, "disturbance_step")) return b->dist_step;               // the row the next plant step takes
-    if (!strcmp(name, "last_disturbance")) return b->last_dist ? 1 : 0;       // the last solve's launches applied the sequence: installed and a plant step taken
+    if (!strcmp(name, "instance_cones")) return b->icone.on ? 1 : 0;          // per-instance cone coefficients are installed (tiny_batch_set_instance_cone_coefficients)
+    if (!strcmp(name, "last_instance_cones")) return b->icone.last ? 1 : 0;   // the last solve's kernel read them: installed and a cone family on
+    if (!strcmp(name, "disturbance")) return b->dist.seq ? b->dist.steps : 0;   // steps of the per-instance disturbance sequence installed (tiny_batch_set_disturbance); 0: none
+    if (!strcmp(name, "disturbance_step")) return b->dist.step;               // the row the next plant step takes
+    if (!strcmp(name, "last_disturbance")) return b->dist.last ? 1 : 0;       // the last solve's launches applied the sequence: installed and a plant step taken
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;

@@ -1,5 +1,5 @@
 // batch_dispatch.hpp -- what batch_api.hip (the C ABI), batch_dispatch.hip (kernel selection, launch forms), batch_tables.hip (lane
-// tables) and batch_helpers.hip (helper kernels, on-demand buffers) share.
+// tables), batch_helpers.hip (helper kernels, on-demand buffers) and batch_instance.hip (per-instance problem data) share.
 #pragma once
 #include "batch_impl.hpp"
 #include "kernel_path.hpp"
@@ -29,22 +29,30 @@ int ensure_repack_buffers(TinyBatch* b);
 int ensure_regroup_buffers(TinyBatch* b, bool second_stream);
 int ensure_adaptive(TinyBatch* b, bool need_tables = true);
 int adaptive_fresh_state(TinyBatch* b);
-int ensure_instance_bounds(TinyBatch* b);   // the per-instance box the kernels read, rebuilt from the caller's arrays when it is out of date (synchronous then)
-// every instance its own half-spaces: is such a set installed AND one of its families enabled (bit 0 static, bit 1 time-varying) / the
-// blocks the kernels read, rebuilt -- or only their offsets rewritten -- when they are out of date (enqueued on the batch's stream)
+int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
+// ---- every instance its own problem data (batch_instance.hip; the state: InstanceBox ... Disturbance of batch_impl.hpp)
+// what a launch calls: the blocks the kernels read, rebuilt where a setter or an enable switch left them out of date -- the box first and
+// synchronously (it may change the UB decision), the other two enqueued on the batch's stream; nothing out of date: a few flag tests, no
+// HIP call -- / the `last` flags <- what the kernel about to be launched reads
+int ensure_instance_data(TinyBatch* b);
+void note_instance_data_read(TinyBatch* b);
+void instance_data_settings_changed(TinyBatch* b);   // tiny_batch_update_settings: what an enable switch leaves out of date
+// a shared setter is about to install one box / half-space set (0 static, 1 time-varying) / cone set for all: the per-instance one goes,
+// its buffers freed once the stream has run dry of their readers (nothing installed: no HIP call)
+int drop_instance_bounds(TinyBatch* b);
+int drop_instance_linear(TinyBatch* b, int set);
+int drop_instance_cones(TinyBatch* b);
+// half-spaces: is a per-instance set installed AND one of its families enabled (bit 0 static, bit 1 time-varying) / the block stride of
+// such a set: the smallest power of two that holds the enabled counts.  Cones: installed AND a cone family on.  Disturbance: installed
+// AND the next launch takes a plant step (advance_x0, or fused steps) / the row its first MPC step takes, as the kernels' int
 int inst_lin_active(const TinyBatch* b);
-int ensure_instance_linear(TinyBatch* b);
-int inst_lin_kmax(const TinyBatch* b);     // the block stride of a per-instance set: the smallest power of two that holds the enabled counts
-// every instance its own cone coefficients: installed AND a cone family on / the block the one-row kernel reads, rebuilt when a setter
-// has changed it (enqueued on the batch's stream)
+int inst_lin_kmax(const TinyBatch* b);
 bool inst_cones_active(const TinyBatch* b);
-int ensure_instance_cones(TinyBatch* b);
-// every instance its own disturbance at the plant step: installed AND the next launch takes a plant step (advance_x0, or fused steps) /
-// the row its first MPC step takes, as the kernels' int / a broadcast sequence [n_steps][nx] expanded to [n_steps][batch][nx]
 bool disturbance_active(const TinyBatch* b);
 int dist_step_base(const TinyBatch* b);
-int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps);
-int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
+// frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
+template <class S>
+void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }
 // ---- lane tables (batch_tables.hip)
 struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)
 SharedHalfspaces shared_halfspaces(const TinyBatch* b);

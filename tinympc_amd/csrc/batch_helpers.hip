@@ -1,7 +1,7 @@
 // batch_helpers.hip -- what the clock-checked dispatch needs besides the solve kernels: the iteration histogram of a solve (its cost
 // model is host arithmetic: launch_learner.hpp), the counting sorts behind step_regroup / repack_sort and the lock-step estimate (small
 // device kernels of this unit), the per-instance state of adaptive rho, and the buffers all of them allocate on demand.  Split off
-// batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.
+// batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.  (Per-instance problem data and its fill kernels: batch_instance.hip.)
 #include "batch_impl.hpp"
 #include "batch_dispatch.hpp"
 #include "lane_tables.hpp"
@@ -118,210 +118,6 @@ int ensure_adaptive(TinyBatch* b, bool need_tables) {
     }
     return TINY_OK;
 }
-
-// ---- every instance its own box (tiny_batch_set_instance_bounds): the caller's arrays -> [batch][lo | hi][N slots][lw lanes], one thread
-// per (instance, slot, lane); which element lands there: box_entry (lane_tables.hpp), nothing else.  The same pass reduces ONE flag,
-// box_is_uniform's rule over every instance: an enabled entry that differs from its family's first knot (slot 0 of a state lane, slot 1 of
-// an input lane) -- or is a NaN, which differs from itself -- makes the batch not uniform
-static __global__ __launch_bounds__(256) void fill_instance_bounds_kernel(double* __restrict__ out, const double* __restrict__ x_min, const double* __restrict__ x_max,
-                                                                          const double* __restrict__ u_min, const double* __restrict__ u_max, int batch, int nx, int nu,
-                                                                          int N, int lw, int state_on, int input_on, int* __restrict__ not_uniform) {
-    const size_t total = (size_t)batch * N * lw;
-    bool differs = false;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(e % lw), slot = (int)((e / lw) % N);
-        const size_t b = e / ((size_t)N * lw);
-        const double *xl = x_min + b * N * nx, *xh = x_max + b * N * nx, *ul = u_min + b * (N - 1) * nu, *uh = u_max + b * (N - 1) * nu;
-        const BoxEntry v = box_entry(xl, xh, ul, uh, nx, nu, slot, lane, state_on != 0, input_on != 0);
-        out[(b * 2 * N + slot) * lw + lane] = v.lo;
-        out[(b * 2 * N + N + slot) * lw + lane] = v.hi;
-        const int family = box_source(nx, nu, slot, lane, state_on != 0, input_on != 0).family;
-        if (family >= 0) {
-            const BoxEntry first = box_entry(xl, xh, ul, uh, nx, nu, family == 0 ? 0 : 1, lane, state_on != 0, input_on != 0);
-            differs |= (v.lo != first.lo) | (v.hi != first.hi);
-        }
-    }
-    if (differs) atomicOr(not_uniform, 1);
-}
-int ensure_instance_bounds(TinyBatch* b) {
-    if (!b->inst_bounds || !b->inst_bounds_dirty) return TINY_OK;
-    const int lw = box_lanes(b->nx, b->nu);
-    const size_t total = (size_t)b->batch * b->N * lw;
-    if (!b->d_inst_bounds) HIP_TRY(b, hipMalloc(&b->d_inst_bounds, 2 * total * sizeof(double)));
-    if (!b->d_ib_flag) HIP_TRY(b, hipMalloc(&b->d_ib_flag, sizeof(int)));
-    HIP_TRY(b, hipMemsetAsync(b->d_ib_flag, 0, sizeof(int), b->stream));
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
-    hipLaunchKernelGGL(fill_instance_bounds_kernel, dim3(grid), dim3(256), 0, b->stream, b->d_inst_bounds, b->d_ib_src[0], b->d_ib_src[1], b->d_ib_src[2],
-                       b->d_ib_src[3], b->batch, b->nx, b->nu, b->N, lw, b->set.en_state_bound ? 1 : 0, b->set.en_input_bound ? 1 : 0, b->d_ib_flag);
-    HIP_TRY(b, hipGetLastError());
-    int not_uniform = 1;
-    HIP_TRY(b, hipMemcpyAsync(&not_uniform, b->d_ib_flag, sizeof(int), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(b, hipStreamSynchronize(b->stream));
-    b->inst_bounds_uniform = b->N >= 2 && not_uniform == 0;
-    b->inst_bounds_dirty = false;
-    b->tab_dirty = true;                              // (the UB decision rides on the lane table's flag: box_is_uniform)
-    return TINY_OK;
-}
-
-// ---- every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): the caller's arrays -> [batch][the
-// enabled sets' blocks: static [3][km][lw], then [N slots][3][km][lw]], one thread per (instance, block, constraint k, lane); what lands
-// there: halfspace_entry (lane_tables.hpp), nothing else.  A set that stayed shared is written from its staged host copies, the same for
-// every instance (ia = ib = 0).  mode 1 rewrites a family's offsets only -- the closed-loop update, which moves b and keeps A: no
-// coefficient is read, no norm summed again
-struct InstLinFamily {
-    HalfspaceRows rows;              // instance 0's, all knots
-    long ia, ib;                     // doubles from one instance's coefficients / offsets to the next one's
-    int mode;                        // 0 leave alone, 1 offsets only, 2 everything
-};
-struct InstLinFill {
-    InstLinFamily f[2][2];           // [static | time-varying][state | input]
-    double* out;
-    int batch, nx, nu, N, lw, km, lv;
-    size_t stride;
-};
-static __global__ __launch_bounds__(256) void fill_instance_linear_kernel(const InstLinFill F) {
-    const int nblk = ((F.lv & 1) ? 1 : 0) + ((F.lv & 2) ? F.N : 0);
-    const size_t total = (size_t)F.batch * nblk * F.km * F.lw;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(e % F.lw), k = (int)((e / F.lw) % F.km), q = (int)((e / ((size_t)F.lw * F.km)) % nblk);
-        const size_t inst = e / ((size_t)F.lw * F.km * nblk);
-        const int set = ((F.lv & 1) && q == 0) ? 0 : 1, slot = q - (F.lv & 1);
-        const int mode = F.f[set][lane < F.nx ? 0 : 1].mode;
-        if (mode == 0) continue;
-        HalfspaceRows st = F.f[set][0].rows, in = F.f[set][1].rows;
-        st.a += inst * F.f[set][0].ia; st.b += inst * F.f[set][0].ib;
-        in.a += inst * F.f[set][1].ia; in.b += inst * F.f[set][1].ib;
-        if (set == 1) { st = st.knot(slot); in = in.knot(slot - 1); }      // input lanes: slot s = knot s-1
-        double* blk = F.out + inst * F.stride + (size_t)q * 3 * F.km * F.lw;
-        if (mode == 1) { blk[F.km * F.lw + k * F.lw + lane] = halfspace_offset(st, in, F.nx, F.nu, k, lane, F.km); continue; }
-        const HalfspaceEntry v = halfspace_entry(st, in, F.nx, F.nu, k, lane, F.km);
-        blk[k * F.lw + lane] = v.a; blk[F.km * F.lw + k * F.lw + lane] = v.b; blk[2 * F.km * F.lw + k * F.lw + lane] = v.nn;
-    }
-}
-int inst_lin_active(const TinyBatch* b) {
-    return ((b->inst_lin[0] && (b->set.en_state_linear || b->set.en_input_linear)) ? 1 : 0) |
-           ((b->inst_lin[1] && (b->set.en_tv_state_linear || b->set.en_tv_input_linear)) ? 2 : 0);
-}
-// the block stride of a per-instance set: the smallest power of two that holds the enabled counts (1 and 2 included)
-int inst_lin_kmax(const TinyBatch* b) { return halfspace_pow2(max_enabled_halfspaces(b)); }
-int ensure_instance_linear(TinyBatch* b) {
-    if (!b->inst_lin[0] && !b->inst_lin[1]) return TINY_OK;
-    if (!b->il_full && !b->il_offsets) return TINY_OK;
-    const int N = b->N, nx = b->nx, nu = b->nu;
-    const int lv = ((b->set.en_state_linear || b->set.en_input_linear) ? 1 : 0) | ((b->set.en_tv_state_linear || b->set.en_tv_input_linear) ? 2 : 0);
-    InstLinFill F = {};
-    if (b->il_full) {
-        b->il_lv = lv; b->il_km = inst_lin_kmax(b);
-        b->il_stride = (size_t)3 * b->il_km * box_lanes(nx, nu) * ((lv & 1) + ((lv & 2) ? N : 0));
-    }
-    F.out = nullptr; F.batch = b->batch; F.nx = nx; F.nu = nu; F.N = N; F.lw = box_lanes(nx, nu); F.km = b->il_km; F.lv = b->il_lv; F.stride = b->il_stride;
-    if (b->il_stride == 0 || !inst_lin_active(b)) { b->il_offsets = 0; return TINY_OK; }      // (nothing a kernel would read; il_full stays: built when a switch comes on)
-    const size_t need = (size_t)b->batch * b->il_stride;
-    if (b->il_doubles < need) {
-        if (b->d_inst_lin) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(b->d_inst_lin); }
-        b->d_inst_lin = nullptr; b->il_doubles = 0;
-        HIP_TRY(b, hipMalloc(&b->d_inst_lin, need * sizeof(double)));
-        b->il_doubles = need;
-        b->il_full = true;
-    }
-    F.out = b->d_inst_lin;
-    // the caller's arrays: per instance an (n x cols) column-major matrix, one ROW per half-space -- time-varying: row n * knot + k
-    const int cnt[2][2] = {{b->nsl, b->nil}, {b->ntsl, b->ntil}};
-    const bool on[2][2] = {{b->set.en_state_linear != 0, b->set.en_input_linear != 0}, {b->set.en_tv_state_linear != 0, b->set.en_tv_input_linear != 0}};
-    for (int set = 0; set < 2; ++set)
-        for (int fam = 0; fam < 2; ++fam) {
-            if (!b->inst_lin[set]) continue;
-            const int n = fam ? nu : nx, c = cnt[set][fam];
-            const long knots = set ? (fam ? N - 1 : N) : 1;
-            InstLinFamily& f = F.f[set][fam];
-            f.rows = halfspace_caller_rows(b->d_il_src[set][2 * fam], b->d_il_src[set][2 * fam + 1], c, n, (int)knots, on[set][fam]);
-            f.ia = c * knots * n; f.ib = c * knots;
-            f.mode = b->il_full ? 2 : ((b->il_offsets >> (2 * set + fam)) & 1);
-        }
-    // a set that stayed shared while the other one is per instance: its host copies, staged, for every instance (full builds only)
-    if (b->il_full && (!b->inst_lin[0] || !b->inst_lin[1])) {
-        const int set = b->inst_lin[0] ? 1 : 0;
-        const SharedHalfspaces h = shared_halfspaces(b);
-        const HalfspaceRows hr[2] = {set ? h.tx : h.sx, set ? h.tu : h.su};
-        const std::vector<double>* src[4] = {set ? &b->tvA_x : &b->Alin_x, set ? &b->tvb_x : &b->blin_x, set ? &b->tvA_u : &b->Alin_u, set ? &b->tvb_u : &b->blin_u};
-        std::vector<double> stage;
-        size_t at[4];
-        for (int i = 0; i < 4; ++i) { at[i] = stage.size(); stage.insert(stage.end(), src[i]->begin(), src[i]->end()); }
-        stage.push_back(0.0);
-        if (int rc = upload_growing(b, &b->d_il_stage, &b->il_stage_doubles, stage)) return rc;
-        for (int fam = 0; fam < 2; ++fam) {
-            InstLinFamily& f = F.f[set][fam];
-            f.rows = hr[fam];
-            f.rows.a = b->d_il_stage + at[2 * fam]; f.rows.b = b->d_il_stage + at[2 * fam + 1];
-            f.ia = 0; f.ib = 0; f.mode = 2;
-        }
-    }
-    const int nblk = ((F.lv & 1) ? 1 : 0) + ((F.lv & 2) ? N : 0);
-    const size_t total = (size_t)b->batch * nblk * F.km * F.lw;
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
-    hipLaunchKernelGGL(fill_instance_linear_kernel, dim3(grid), dim3(256), 0, b->stream, F);
-    HIP_TRY(b, hipGetLastError());
-    b->il_full = false; b->il_offsets = 0;
-    return TINY_OK;
-}
-
-// ---- every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients): the caller's dense arrays cx [batch][n_state],
-// cu [batch][n_input] -> [batch][lw lanes], one thread per (instance, lane); what lands there: cone_entry (lane_tables.hpp), nothing else.
-// A family whose array is null takes the shared coefficients, the same for every instance (stride 0)
-static __global__ __launch_bounds__(256) void fill_instance_cones_kernel(double* __restrict__ out, const double* __restrict__ cx, const double* __restrict__ cu, long cx_stride,
-                                                                         long cu_stride, const int* __restrict__ Acx, int n_state, const int* __restrict__ Acu, int n_input,
-                                                                         int batch, int nx, int nu, int lw) {
-    const size_t total = (size_t)batch * lw;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
-        const int lane = (int)(e % lw);
-        const size_t b = e / lw;
-        out[e] = cone_entry(cx + b * cx_stride, cu + b * cu_stride, Acx, n_state, Acu, n_input, nx, nu, lane);
-    }
-}
-bool inst_cones_active(const TinyBatch* b) { return b->inst_cones && soc_active(b); }
-int ensure_instance_cones(TinyBatch* b) {
-    if (!b->inst_cones || !b->inst_cones_dirty) return TINY_OK;
-    const int lw = box_lanes(b->nx, b->nu), ns = (int)b->Acx.size(), ni = (int)b->Acu.size();
-    const size_t total = (size_t)b->batch * lw;
-    if (!b->d_inst_cones) HIP_TRY(b, hipMalloc(&b->d_inst_cones, total * sizeof(double)));
-    if (!b->d_ic_pos) HIP_TRY(b, hipMalloc(&b->d_ic_pos, (size_t)(ns + ni + 1) * sizeof(int)));
-    // the cone positions and the shared coefficients (of a family that did not get its own), staged; the host vectors are pageable:
-    // the copies are staged synchronously
-    std::vector<int> pos(b->Acx);
-    pos.insert(pos.end(), b->Acu.begin(), b->Acu.end());
-    pos.push_back(0);
-    std::vector<double> shared(b->cx);
-    shared.insert(shared.end(), b->cu.begin(), b->cu.end());
-    shared.push_back(1.0);
-    HIP_TRY(b, hipMemcpyAsync(b->d_ic_pos, pos.data(), pos.size() * sizeof(int), hipMemcpyHostToDevice, b->stream));
-    if (int rc = upload_growing(b, &b->d_ic_stage, &b->ic_stage_doubles, shared)) return rc;
-    const double* cx = b->d_ic_src[0] ? b->d_ic_src[0] : b->d_ic_stage;
-    const double* cu = b->d_ic_src[1] ? b->d_ic_src[1] : b->d_ic_stage + ns;
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
-    hipLaunchKernelGGL(fill_instance_cones_kernel, dim3(grid), dim3(256), 0, b->stream, b->d_inst_cones, cx, cu, b->d_ic_src[0] ? (long)ns : 0L,
-                       b->d_ic_src[1] ? (long)ni : 0L, b->d_ic_pos, ns, b->d_ic_pos + ns, ni, b->batch, b->nx, b->nu, lw);
-    HIP_TRY(b, hipGetLastError());
-    b->inst_cones_dirty = false;
-    return TINY_OK;
-}
-
-// ---- every instance its own disturbance at the plant step (tiny_batch_set_disturbance): one sequence for all, seq [n_steps][nx], written
-// out as the layout the kernels read, out [n_steps][batch][nx]; one thread per element (enqueued on the batch's stream)
-static __global__ __launch_bounds__(256) void expand_disturbance_kernel(double* __restrict__ out, const double* __restrict__ seq, size_t total, int batch, int nx) {
-    const size_t row = (size_t)batch * nx;
-    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
-        out[e] = seq[(e / row) * nx + e % nx];
-}
-int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps) {
-    const size_t total = (size_t)n_steps * b->batch * b->nx;
-    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)b->num_cus * 16);
-    hipLaunchKernelGGL(expand_disturbance_kernel, dim3(grid), dim3(256), 0, b->stream, out, seq, total, b->batch, b->nx);
-    HIP_TRY(b, hipGetLastError());
-    return TINY_OK;
-}
-bool disturbance_active(const TinyBatch* b) { return b->d_dist && b->dist_steps > 0 && (b->advance_x0 || b->steps_per_launch > 1); }
-// (the kernels count steps in an int; a counter moved beyond +-2^30 is outside every sequence either way)
-int dist_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->dist_step, -(1L << 30), 1L << 30); }
 
 // histogram of the iteration counts the solve just enqueued leaves in d_status -> pinned host memory, asynchronously (hist_ev)
 int enqueue_iteration_histogram(TinyBatch* b) {

@@ -1,5 +1,5 @@
-// batch_impl.hpp -- the opaque TinyBatch behind include/tinympc_amd.h (shared by batch_api.hip, batch_dispatch.hip, batch_tables.hip, batch_helpers.hip and
-// compat_api.hip).
+// batch_impl.hpp -- the opaque TinyBatch behind include/tinympc_amd.h (shared by batch_api.hip, batch_dispatch.hip, batch_tables.hip, batch_helpers.hip,
+// batch_instance.hip and compat_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -25,6 +25,57 @@ struct Settings {              // TinySettings (types.hpp:63-82) hot-path subset
 };
 
 }  // namespace tinympc_amd
+
+// ---- every instance its own problem data: one plain struct per family (batch_instance.hip sets, builds, reads and drops them).  Each
+// names every device buffer it owns in each_buffer -- the drop paths and tiny_batch_destroy free through it and nothing else: a new
+// buffer is one more line there.  `last`: what the last solve's kernel read (options "last_instance_*", "last_disturbance")
+// every instance its own box (tiny_batch_set_instance_bounds): the caller's four arrays as given (src: x_min, x_max [batch][N][nx],
+// u_min, u_max [batch][N-1][nu]) and what the kernels read, built from them: built [batch][lo | hi][N][box_lanes]
+// (lane_tables.hpp box_entry; rebuilt when the box or an enable switch changes: dirty).  uniform: EVERY instance's box is
+// knot-invariant for the enabled families (box_is_uniform's rule, reduced by the same kernel into flag) -- the UB forms
+struct InstanceBox {
+    bool on = false, dirty = false, uniform = false, last = false;
+    double *src[4] = {nullptr, nullptr, nullptr, nullptr}, *built = nullptr;
+    int* flag = nullptr;
+    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(flag); }
+};
+// every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): set 0 static, set 1 time-varying,
+// each installed on its own.  src[set]: the caller's arrays as given -- A_x, b_x, A_u, b_u with a leading batch axis; the counts
+// are TinyBatch's nsl / nil / ntsl / ntil, whose host copies are empty then.  built: what the kernels read, made from them (and from
+// the host copies of a set that stayed shared, staged in stage) with the fill rule of lane_tables.hpp halfspace_entry:
+// [batch][stride] = the enabled sets' blocks, static [3][km][lw] first, then [N][3][km][lw].  full: everything is rebuilt
+// (a set, a count or an enable switch changed); offsets bit 2 * set + family: only that family's offsets are rewritten
+struct InstanceHalfspaces {
+    bool on[2] = {false, false}, full = false;
+    int offsets = 0, km = 1, lv = 0;               // km, lv: block stride / which sets the array holds (bit 0 static, bit 1 time-varying), as last built
+    size_t stride = 0, doubles = 0, stage_doubles = 0;
+    double *src[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}}, *built = nullptr, *stage = nullptr;
+    int last = 0;                                  // the mask of per-instance sets the last solve's kernel read
+    template <class F> void each_buffer(F f) { for (auto& set : src) for (double*& p : set) f(p); f(built); f(stage); }
+};
+// every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients).  src: the caller's arrays as given --
+// cx [batch][Acx.size()], cu [batch][Acu.size()]; a null one: that family keeps the shared coefficients (TinyBatch's cx / cu) for every
+// instance.  The coverage kernel reads them as they are (it walks the cones by index); built [batch][lw] is what the one-row
+// kernel's PC forms read, made with the fill rule of lane_tables.hpp cone_entry from the arrays and from stage / pos (the shared
+// coefficients and the cone positions, staged).  The block does not depend on the enable switches
+struct InstanceCones {
+    bool on = false, dirty = false, last = false;
+    double *src[2] = {nullptr, nullptr}, *built = nullptr, *stage = nullptr;
+    int* pos = nullptr;
+    size_t stage_doubles = 0;
+    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(stage); f(pos); }
+};
+// every instance its own additive disturbance at the plant step (tiny_batch_set_disturbance): seq [steps][batch][nx],
+// step-major -- a launch reads one contiguous [batch][nx] block per MPC step; a broadcast sequence is expanded to that layout on the
+// device.  step: the row the next plant step takes (the setter rewinds it, option "disturbance_step" moves it,
+// every MPC step of a launch with a plant step advances it, tiny_batch_reset leaves it alone); rows outside [0, steps) add nothing
+struct Disturbance {
+    double* seq = nullptr;
+    int steps = 0;
+    long step = 0;
+    bool last = false;                             // (... applied the sequence: installed and a plant step taken)
+    template <class F> void each_buffer(F f) { f(seq); }
+};
 
 constexpr size_t KPI_SKEW_BYTES = 0;             // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
@@ -113,48 +164,8 @@ struct TinyBatch {
     bool use_ub = true;                            // option "uniform_bounds": take the UB kernel variant when the box allows it
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
-    // every instance its own box (tiny_batch_set_instance_bounds): the caller's four arrays as given (d_ib_src: x_min, x_max [batch][N][nx],
-    // u_min, u_max [batch][N-1][nu]) and what the kernels read, built from them by batch_helpers.hip: d_inst_bounds [batch][lo | hi][N][box_lanes]
-    // (lane_tables.hpp box_entry; rebuilt when the box or an enable switch changes: inst_bounds_dirty).  inst_bounds_uniform: EVERY
-    // instance's box is knot-invariant for the enabled families (box_is_uniform's rule, reduced by the same kernel) -- the UB forms
-    bool inst_bounds = false, inst_bounds_dirty = false, inst_bounds_uniform = false;
-    bool last_inst_bounds = false;                 // the last solve's kernel read a per-instance box
-    double* d_ib_src[4] = {nullptr, nullptr, nullptr, nullptr};
-    double* d_inst_bounds = nullptr;
-    int* d_ib_flag = nullptr;
-    // every instance its own half-spaces (tiny_batch_set_instance_linear_constraints / ..._tv_...): set 0 static, set 1 time-varying,
-    // each installed on its own.  d_il_src[set]: the caller's arrays as given -- A_x, b_x, A_u, b_u with a leading batch axis; the counts
-    // are nsl / nil / ntsl / ntil above, whose host copies are empty then.  d_inst_lin: what the kernels read, built from them (and from
-    // the host copies of a set that stayed shared) by batch_helpers.hip with the fill rule of lane_tables.hpp halfspace_entry:
-    // [batch][il_stride] = the enabled sets' blocks, static [3][il_km][lw] first, then [N][3][il_km][lw].  il_full: everything is rebuilt
-    // (a set, a count or an enable switch changed); il_offsets bit 2 * set + family: only that family's offsets are rewritten
-    bool inst_lin[2] = {false, false};
-    bool il_full = false;
-    int il_offsets = 0;
-    int il_km = 1, il_lv = 0;                      // block stride / which sets the array holds (bit 0 static, bit 1 time-varying), as last built
-    size_t il_stride = 0, il_doubles = 0, il_stage_doubles = 0;
-    double* d_il_src[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
-    double *d_inst_lin = nullptr, *d_il_stage = nullptr;
-    int last_inst_lin = 0;                         // the mask of per-instance sets the last solve's kernel read
-    // every instance its own cone coefficients (tiny_batch_set_instance_cone_coefficients).  d_ic_src: the caller's arrays as given --
-    // cx [batch][Acx.size()], cu [batch][Acu.size()]; a null one: that family keeps the shared coefficients (cx / cu above) for every
-    // instance.  The coverage kernel reads them as they are (it walks the cones by index); d_inst_cones [batch][lw] is what the one-row
-    // kernel's PC forms read, built by batch_helpers.hip with the fill rule of lane_tables.hpp cone_entry from the arrays and from
-    // d_ic_stage (the cone positions and the shared coefficients, staged).  The block does not depend on the enable switches
-    bool inst_cones = false, inst_cones_dirty = false;
-    double* d_ic_src[2] = {nullptr, nullptr};
-    double *d_inst_cones = nullptr, *d_ic_stage = nullptr;
-    int* d_ic_pos = nullptr;
-    size_t ic_stage_doubles = 0;
-    bool last_inst_cones = false;                  // the last solve's kernel read them
-    // every instance its own additive disturbance at the plant step (tiny_batch_set_disturbance): d_dist [dist_steps][batch][nx],
-    // step-major -- a launch reads one contiguous [batch][nx] block per MPC step; a broadcast sequence is expanded to that layout by
-    // batch_helpers.hip.  dist_step: the row the next plant step takes (the setter rewinds it, option "disturbance_step" moves it,
-    // every MPC step of a launch with a plant step advances it, tiny_batch_reset leaves it alone); rows outside [0, dist_steps) add nothing
-    double* d_dist = nullptr;
-    int dist_steps = 0;
-    long dist_step = 0;
-    bool last_dist = false;                        // the last solve's launches applied the sequence: installed and a plant step taken
+    // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

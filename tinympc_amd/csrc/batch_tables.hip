@@ -40,7 +40,7 @@ int lin_kmax(const TinyBatch* b) {
 // (-inf, +inf) everywhere; every knot is compared with knot 0, knot 0 included: a NaN bound equals nothing and is not uniform
 bool box_is_uniform(const TinyBatch* b) {
     if (b->N < 2) return false;
-    if (b->inst_bounds) return b->inst_bounds_uniform;   // (the same rule over every instance's box, reduced on the device: batch_helpers.hip)
+    if (b->ibox.on) return b->ibox.uniform;   // (the same rule over every instance's box, reduced on the device: batch_instance.hip)
     if (!b->have_bounds) return true;
     auto same = [](const std::vector<double>& v, int knots, int n) {
         for (int i = 0; i < knots; ++i)
@@ -73,7 +73,7 @@ struct HostView {
 // is off, and so is every family of a set that is installed per instance (its host copies are empty)
 SharedHalfspaces shared_halfspaces(const TinyBatch* b) {
     const int nx = b->nx, nu = b->nu;
-    const bool s = !b->inst_lin[0], t = !b->inst_lin[1];
+    const bool s = !b->ilin.on[0], t = !b->ilin.on[1];
     SharedHalfspaces h;
     h.sx = {b->Alin_x.data(), b->blin_x.data(), s ? b->nsl : 0, nx, nx, 1, 0, 0, s && b->set.en_state_linear};
     h.su = {b->Alin_u.data(), b->blin_u.data(), s ? b->nil : 0, nu, nu, 1, 0, 0, s && b->set.en_input_linear};

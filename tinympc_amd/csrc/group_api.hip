@@ -157,6 +157,15 @@ inline long first_of(const TinyGroup* g, int k) {
     return lo;
 }
 inline long global_index(const TinyGroup* g, int k, long local) { return g->interleaved ? (long)k + local * g->n : first_of(g, k) + local; }
+// shard k's rows of a caller array over the full batch axis, `per` doubles an instance (a null array stays null): contiguous shards read
+// the caller's array in place, interleaved ones a copy gathered into *stage (never empty: a zero-sized row still gives a pointer)
+const double* shard_slice(const TinyGroup* g, int k, const double* src, size_t per, std::vector<double>* stage) {
+    if (!src) return nullptr;
+    if (!g->interleaved) return src + (size_t)first_of(g, k) * per;
+    stage->resize((size_t)g->count[k] * per + 1);
+    for (long i = 0; i < g->count[k]; ++i) memcpy(stage->data() + (size_t)i * per, src + (size_t)global_index(g, k, i) * per, per * sizeof(double));
+    return stage->data();
+}
 
 template <class F>
 int for_shards(TinyGroup* g, F&& f) {
@@ -268,14 +277,7 @@ int tiny_group_set_instance_bounds(TinyGroup* g, const double* x_min, const doub
     std::vector<double> stage[4];
     for (int k = 0; k < g->n; ++k) {
         const double* from[4];
-        for (int a = 0; a < 4; ++a) {
-            from[a] = src[a] + (size_t)first_of(g, k) * per[a];
-            if (g->interleaved) {
-                stage[a].resize((size_t)g->count[k] * per[a]);
-                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
-                from[a] = stage[a].data();
-            }
-        }
+        for (int a = 0; a < 4; ++a) from[a] = shard_slice(g, k, src[a], per[a], &stage[a]);
         if (int rc = tiny_batch_set_instance_bounds(g->shard[k], from[0], from[1], from[2], from[3], TINY_HOST))
             return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
     }
@@ -304,14 +306,7 @@ static int group_set_instance_linear(TinyGroup* g, int set, int ns, const double
     std::vector<double> stage[4];
     for (int k = 0; k < g->n; ++k) {
         const double* from[4];
-        for (int a = 0; a < 4; ++a) {
-            from[a] = src[a] ? src[a] + (size_t)first_of(g, k) * per[a] : nullptr;
-            if (g->interleaved && src[a]) {
-                stage[a].resize((size_t)g->count[k] * per[a] + 1);
-                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
-                from[a] = stage[a].data();
-            }
-        }
+        for (int a = 0; a < 4; ++a) from[a] = shard_slice(g, k, src[a], per[a], &stage[a]);
         const int rc = set ? tiny_batch_set_instance_tv_linear_constraints(g->shard[k], ns, from[0], from[1], ni, from[2], from[3], TINY_HOST)
                            : tiny_batch_set_instance_linear_constraints(g->shard[k], ns, from[0], from[1], ni, from[2], from[3], TINY_HOST);
         if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
@@ -336,14 +331,7 @@ int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, co
     for (int k = 0; k < g->n; ++k) {
         const size_t per[2] = {(size_t)tiny_batch_get_option(g->shard[k], "n_state_cones"), (size_t)tiny_batch_get_option(g->shard[k], "n_input_cones")};
         const double* from[2];
-        for (int a = 0; a < 2; ++a) {
-            from[a] = src[a] ? src[a] + (size_t)first_of(g, k) * per[a] : nullptr;
-            if (g->interleaved && src[a]) {
-                stage[a].resize((size_t)g->count[k] * per[a] + 1);
-                for (long i = 0; i < g->count[k]; ++i) memcpy(stage[a].data() + (size_t)i * per[a], src[a] + (size_t)global_index(g, k, i) * per[a], per[a] * sizeof(double));
-                from[a] = stage[a].data();
-            }
-        }
+        for (int a = 0; a < 2; ++a) from[a] = shard_slice(g, k, src[a], per[a], &stage[a]);
         const int rc = tiny_batch_set_instance_cone_coefficients(g->shard[k], from[0], from[1], TINY_HOST);
         if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
     }
@@ -392,13 +380,7 @@ int tiny_group_set(TinyGroup* g, TinyField field, const double* src, int flags) 
     if (flags & TINY_BROADCAST) return for_shards(g, [&](TinyBatch* b) { return tiny_batch_set(b, field, src, TINY_HOST | TINY_BROADCAST); });
     const size_t per = field_doubles(g->nx, g->nu, g->N, field);
     for (int k = 0; k < g->n; ++k) {
-        const double* from = src + (size_t)first_of(g, k) * per;
-        if (g->interleaved) {
-            g->stage.resize((size_t)g->count[k] * per);
-            for (long i = 0; i < g->count[k]; ++i) memcpy(g->stage.data() + (size_t)i * per, src + (size_t)global_index(g, k, i) * per, per * sizeof(double));
-            from = g->stage.data();
-        }
-        if (int rc = tiny_batch_set(g->shard[k], field, from, TINY_HOST))
+        if (int rc = tiny_batch_set(g->shard[k], field, shard_slice(g, k, src, per, &g->stage), TINY_HOST))
             return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
     }
     return TINY_OK;

@@ -4,7 +4,7 @@
 // (batch_tables.hip) view Mat / Cache, the Riccati and sensitivity epilogues view the column-major LDS and global arrays they hold,
 // so all of them write the same tables by construction.  The products Quu_inv B' (QBt) and Quu_inv BPf (QBPf) are inputs of the
 // mapping: each side computes them with its own matrix product.
-// Included by batch_tables.hip, batch_helpers.hip, riccati_kernel.hip.h and sensitivity_kernel.hip.h -- never by the two headers that
+// Included by batch_tables.hip, batch_helpers.hip, batch_instance.hip, riccati_kernel.hip.h and sensitivity_kernel.hip.h -- never by the two headers that
 // are instantiated at run time from their source text (admm_kernel.hip.h, tile_kernel.hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
