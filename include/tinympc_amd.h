@@ -225,10 +225,47 @@ int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double
  * a missing hipRTC and whatever runs there without a sequence.  Adaptive rho on a launch with a plant step fails the solve with
  * TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with a per-instance disturbance").
  * Out of scope: the tile kernel (its shapes run on the coverage kernel while a disturbance applies), the half-row and PREFETCH forms,
- * a state-dependent plant (own A_p, B_p), a per-step log of the realised x0, tiny_codegen, tiny_solve_batch and the drop-in structs. */
+ * tiny_codegen, tiny_solve_batch and the drop-in structs.  (A plant of its own and a log of the realised x0: tiny_batch_set_plant.) */
 int tiny_batch_set_disturbance(TinyBatch* b, const double* w, int n_steps, int flags);
 /* row `step` of instance `instance` as installed: w_out [nx]; TINY_ERR_ARG with none installed or an index outside it */
 int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out);
+/* a plant model of its own at the plant step of a closed loop (advance_x0, steps_per_launch > 1): the controller keeps predicting with
+ * its A, B, f while the state is handed on by A_p, B_p, f_p -- model mismatch (mass, inertia, actuator gain, drag per vehicle; a finer
+ * discretisation as "truth") without the host in the loop.
+ * flags TINY_HOST or TINY_DEVICE: every instance its own plant, A_p [batch][nx*nx] column-major, B_p [batch][nx*nu], f_p [batch][nx] or
+ * NULL for zero (the layout of tiny_batch_setup_hetero); copied, the caller may free.  With TINY_BROADCAST: ONE plant for all, [nx*nx],
+ * [nx*nu], [nx], stored once.  A_p == NULL removes the plant and frees it; B_p == NULL with A_p != NULL is TINY_ERR_ARG.  A failed call
+ * leaves what was installed; tiny_batch_reset leaves the plant alone.  Synchronous; works on tiny_batch_setup and
+ * tiny_batch_setup_hetero batches.
+ * Meaning: while a plant is installed, wherever a launch takes a plant step (the next fused step's x0, the x0_next store of
+ * advance_x0), state row j of instance i becomes
+ *     acc = f_p[j];  for k < nx: acc = fma(x0[k], A_p[j][k], acc);  for k < nu: acc = fma(u0[k], B_p[j][k], acc);  x0_next[j] = acc
+ * (then fl(acc + w[k][i]) where a disturbance row applies): x0 the state this MPC step started from, u0 the control it applied (what
+ * the step log records); ONE chain, one rounding per term, in this order, whatever "dpp_mode" says and on every kernel path.  It is the
+ * order of the one-row kernel's forward pass under the default "dpp_mode": a plant equal to the model reproduces the run without a
+ * plant bit for bit.  A step that ran no iteration (max_iter = 0) takes no plant step.  Only x0 moves: work->x, solution->x and the x
+ * record keep the solver's prediction.  A launch without a plant step reads nothing of the plant and runs the kernel form it runs
+ * without one.
+ * Read-backs (tiny_batch_get_option): "plant" 0 none, 1 one for all, 2 every instance its own; "last_plant" 1 when the last solve's
+ * launches took their plant step through it.
+ * Where it runs: the one-row kernel's PP forms (run-time instantiated; tiny_batch_kernel_path 3) of every form the PD forms exist for,
+ * with or without a disturbance, on full rows; everywhere else (tile-kernel shapes, overlapping cones, "debug", "force_general",
+ * "no_jit", a missing hipRTC) a helper kernel behind each single-step launch of the coverage kernel, same bits.  Adaptive rho on a
+ * launch with a plant step fails the solve with TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with a plant of its own ...").
+ * Out of scope: the tile kernel, the half-row and PREFETCH forms, tiny_codegen, tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_plant(TinyBatch* b, const double* A_p, const double* B_p, const double* f_p, int flags);
+/* the plant instance `instance` is stepped by, as installed: A_p [nx*nx], B_p [nx*nu], f_p [nx] (zeros where none was given); any pointer
+ * may be NULL.  TINY_ERR_ARG with none installed or an instance outside the batch */
+int tiny_batch_get_plant(TinyBatch* b, int instance, double* A_p, double* B_p, double* f_p);
+/* option "state_log" = 1: every launch that takes a plant step (fused steps -- cut into stretches or not --, single steps with
+ * advance_x0) records, per MPC step of the solve call and per instance, the state the plant step handed on: the x0 the next step
+ * started from, plant and disturbance included; a step that took no plant step logs the x0 it left in place.  x0_next is
+ * [steps][batch][nx], steps at most what the last solve call ran (a single step: one row).  With neither a plant nor a disturbance
+ * installed the launch takes a PD form with an empty sequence (same bits as the plain form; tiny_batch_kernel_path 3: run-time
+ * instantiated even for a compiled-in shape) and a tile-kernel shape runs on the coverage kernel.  Unlike "step_log", the log does not
+ * combine with adaptive rho: a launch that takes a plant step with the log on is refused (TINY_ERR_UNSUPPORTED, "adaptive rho does not
+ * combine with the state log") */
+int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps);
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -508,6 +545,9 @@ int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, co
 /* every instance its own disturbance sequence (tiny_batch_set_disturbance): host, [n_steps][batch][nx] over the full batch axis in the
  * caller's order, or with TINY_BROADCAST one [n_steps][nx]; NULL removes.  tiny_group_set_option forwards "disturbance_step" */
 int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int flags);
+/* a plant of its own (tiny_batch_set_plant): host arrays over the full batch axis in the caller's order, or with TINY_BROADCAST one
+ * plant; A_p == NULL removes.  tiny_group_set_option forwards "state_log"; the log is read shard by shard (tiny_group_shard) */
+int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, const double* f_p, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

@@ -41,7 +41,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_cone_constraints", "tiny_batch_set_linear_constraints", "tiny_batch_set_tv_linear_constraints",
     "tiny_batch_set_instance_linear_constraints", "tiny_batch_set_instance_tv_linear_constraints", "tiny_batch_get_instance_linear_constraints",
     "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
-    "tiny_batch_set_disturbance", "tiny_batch_get_disturbance",
+    "tiny_batch_set_disturbance", "tiny_batch_get_disturbance", "tiny_batch_set_plant", "tiny_batch_get_plant", "tiny_batch_get_state_log",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -54,7 +54,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -195,6 +195,9 @@ def lib():
         L.tiny_batch_get_timing.argtypes = [C.c_void_p, _fp, C.c_int]
         L.tiny_batch_set_reference_trajectory.argtypes = [C.c_void_p, _dp, C.c_int, _ip, C.c_int]
         L.tiny_batch_get_step_log.argtypes = [C.c_void_p, _ip, _dp, C.c_int]
+        L.tiny_batch_set_plant.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_plant.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+        L.tiny_batch_get_state_log.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_batch_last_error.argtypes = [C.c_void_p]
         L.tiny_batch_last_error.restype = C.c_char_p
         L.tiny_batch_supported_dims.argtypes = [_ip, C.c_int]
@@ -246,6 +249,7 @@ def lib():
         L.tiny_group_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tiny_group_set_disturbance.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
+        L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
         L.tiny_group_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -474,6 +478,49 @@ class TinyBatchSolver:
         """w[step, i] (nx,) as installed"""
         out = np.zeros(self.nx)
         self._check(lib().tiny_batch_get_disturbance(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_disturbance")
+        return out
+
+    def _plant(self, A_p, B_p, f_p):
+        """A_p (batch, nx, nx) | (nx, nx), B_p (batch, nx, nu) | (nx, nu), f_p (batch, nx) | (nx,) | None -> (flat column-major arrays,
+        broadcast flag)"""
+        A, Bm = np.asarray(A_p, dtype=np.float64), np.asarray(B_p, dtype=np.float64)
+        one = A.ndim == 2
+        if one:
+            A, Bm = A[None], Bm[None]
+        n = 1 if one else self.batch
+        if A.shape != (n, self.nx, self.nx) or Bm.shape != (n, self.nx, self.nu):
+            raise ValueError(f"plant: A_p ({n}, {self.nx}, {self.nx}), B_p ({n}, {self.nx}, {self.nu}), got {A.shape}, {Bm.shape}")
+        f = None if f_p is None else _f64(f_p).reshape(n, self.nx).ravel()
+        return np.ascontiguousarray(A.transpose(0, 2, 1)).ravel(), np.ascontiguousarray(Bm.transpose(0, 2, 1)).ravel(), f, (BROADCAST if one else 0)
+
+    def set_plant(self, A_p, B_p=None, f_p=None):
+        """a plant model of its own at the plant step of a closed loop (advance_x0, steps_per_launch > 1): the state handed on is
+        f_p + A_p x0 + B_p u0, one fused multiply-add chain in that order, while the controller keeps its own model.  A_p (batch, nx, nx),
+        B_p (batch, nx, nu), f_p (batch, nx) or None; 2-D A_p, B_p: one plant for all (stored once).  A_p None removes it"""
+        if A_p is None:
+            return self._check(lib().tiny_batch_set_plant(self._h, None, None, None, HOST), "set_plant")
+        if B_p is None:
+            raise ValueError("plant: A_p without B_p")
+        A, Bm, f, bc = self._plant(A_p, B_p, f_p)
+        self._check(lib().tiny_batch_set_plant(self._h, A.ctypes.data_as(C.c_void_p), Bm.ctypes.data_as(C.c_void_p),
+                                               None if f is None else f.ctypes.data_as(C.c_void_p), HOST | bc), "set_plant")
+
+    def set_plant_device(self, A_p, B_p, f_p=None, broadcast=False):
+        """the same from device pointers (ints) to column-major [batch][nx*nx], [batch][nx*nu], [batch][nx] doubles (one of each with
+        broadcast) resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_plant(self._h, C.c_void_p(int(A_p)), C.c_void_p(int(B_p)), None if f_p is None else C.c_void_p(int(f_p)),
+                                               DEVICE | (BROADCAST if broadcast else 0)), "set_plant_device")
+
+    def get_plant(self, i):
+        """(A_p (nx, nx), B_p (nx, nu), f_p (nx,)) instance i is stepped by, as installed"""
+        A, Bm, f = np.zeros(self.nx * self.nx), np.zeros(self.nx * self.nu), np.zeros(self.nx)
+        self._check(lib().tiny_batch_get_plant(self._h, int(i), A.ctypes.data_as(_dp), Bm.ctypes.data_as(_dp), f.ctypes.data_as(_dp)), "get_plant")
+        return A.reshape(self.nx, self.nx).T.copy(), Bm.reshape(self.nu, self.nx).T.copy(), f
+
+    def state_log(self, steps):
+        """x0_next[steps, batch, nx]: the state every MPC step of the last solve call handed on (option "state_log" = 1)"""
+        out = np.zeros((steps, self.batch, self.nx))
+        self._check(lib().tiny_batch_get_state_log(self._h, out.ctypes.data_as(_dp), int(steps)), "get_state_log")
         return out
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
@@ -902,6 +949,45 @@ class TinyGroupSolver:
                     raise TinyMPCError(f"get_disturbance failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
                 return out
         raise TinyMPCError(f"get_disturbance: instance {i} of {self.batch}")
+
+    def set_plant(self, A_p, B_p=None, f_p=None):
+        """a plant of its own for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); A_p None removes"""
+        if A_p is None:
+            return self._check(lib().tiny_group_set_plant(self._h, None, None, None, HOST), "set_plant")
+        if B_p is None:
+            raise ValueError("plant: A_p without B_p")
+        A, Bm, f, bc = TinyBatchSolver._plant(self, A_p, B_p, f_p)
+        self._check(lib().tiny_group_set_plant(self._h, A.ctypes.data_as(_dp), Bm.ctypes.data_as(_dp), None if f is None else f.ctypes.data_as(_dp),
+                                               HOST | bc), "set_plant")
+
+    def _of_shard(self, i):
+        for k in range(self.shards):
+            at = np.flatnonzero(self.shard_indices(k) == int(i))
+            if len(at):
+                return lib().tiny_group_shard(self._h, k), int(at[0])
+        raise TinyMPCError(f"instance {i} of {self.batch}")
+
+    def get_plant(self, i):
+        """the plant of instance i (the caller's order): asked of the shard that holds it"""
+        h, at = self._of_shard(i)
+        A, Bm, f = np.zeros(self.nx * self.nx), np.zeros(self.nx * self.nu), np.zeros(self.nx)
+        rc = lib().tiny_batch_get_plant(h, at, A.ctypes.data_as(_dp), Bm.ctypes.data_as(_dp), f.ctypes.data_as(_dp))
+        if rc != OK:
+            raise TinyMPCError(f"get_plant failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+        return A.reshape(self.nx, self.nx).T.copy(), Bm.reshape(self.nu, self.nx).T.copy(), f
+
+    def state_log(self, steps):
+        """x0_next[steps, batch, nx] of the last solve call (option "state_log" = 1), gathered from the shards into the caller's order"""
+        out = np.zeros((steps, self.batch, self.nx))
+        for k in range(self.shards):
+            idx = self.shard_indices(k)
+            part = np.zeros((steps, len(idx), self.nx))
+            h = lib().tiny_group_shard(self._h, k)
+            rc = lib().tiny_batch_get_state_log(h, part.ctypes.data_as(_dp), int(steps))
+            if rc != OK:
+                raise TinyMPCError(f"get_state_log failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+            out[:, idx] = part
+        return out
 
     def set_cone_constraints(self, Acx, qcx, cx, Acu, qcu, cu):
         ai = lambda v: np.ascontiguousarray(v, dtype=np.int32)

@@ -32,7 +32,7 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients), PD (per-instance disturbance at the plant step; see
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients), PD (per-instance disturbance at the plant step), PP (a plant model of its own there; see
 //     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
@@ -214,6 +214,12 @@ struct SolveArgs {
         struct {
             const double* dist;
             int dist_steps, dist_step0;
+            // PP forms: a plant model of its own at the plant step -- plant [instances][(NX+NU) columns + the f_p vector][16 lanes]
+            // (plant_entry of lane_tables.hpp).  A shared plant is ONE block: bit 0 of the pointer (the blocks are 8-byte aligned)
+            // says so, which spares a field here and a template bit.  Null in a form without PP
+            const double* plant;
+            // PD and PP forms: optional [steps][batch][NX], the x0 every MPC step of this launch handed on (option "state_log")
+            double* state_log;
         };
     };
 };
@@ -743,6 +749,21 @@ __device__ __forceinline__ double plant_add(double x1, const double w) {
     asm volatile("" : "+v"(x1));
     return x1 + w;
 }
+// the plant step of the PP forms, columns COL0 .. COL0 + NCOL - 1 of ONE chain: acc = fma(bcast(src, lane c), m[c], acc), column after
+// column on the one accumulator.  Cut into blocks of at most four columns, each loading its own operands (m: this lane's entry of column
+// COL0, the columns 16 doubles apart): the same instructions in the same order as one ring1 over all columns, hence the same bits, at
+// 8 transient registers instead of 2 * NCOL
+template <int COL0, int NCOL>
+__device__ __forceinline__ void plant_chain(double& acc, const double src, const double* m) {
+    if constexpr (NCOL > 0) {
+        constexpr int K = NCOL < 4 ? NCOL : 4;
+        double r[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) r[k] = m[k * 16];
+        ring1<COL0, K>(acc, src, r);
+        plant_chain<COL0 + K, NCOL - K>(acc, src, m + K * 16);
+    }
+}
 
 // LIN: bit 0 = static half-spaces (admm.cpp:137-173), bit 1 = time-varying ones (:176-211); 0 = neither
 // HET: per-instance problem data (riccati_kernel.hip.h): the matrix rows are re-loaded for every instance
@@ -779,6 +800,13 @@ __device__ __forceinline__ double plant_add(double x1, const double w) {
 // test), and so does a step that ran no iteration (max_iter = 0: no plant step).  Only x0 moves: the x|u records keep the solver's
 // prediction.  With every variant and launch form but HALF, PF and ADAPT; composes with PB, PL and PC.  Run-time instantiated only;
 // bit 5 of the sixth template argument (MODE | 32).
+// PP: a plant model of its own (SolveArgs::plant: A_p, B_p, f_p per instance, or one for all) -- where a plant step is taken, state row
+// j becomes acc = f_p[j]; acc = fma(x0[k], A_p[j][k], acc), k = 0 .. NX-1; acc = fma(u0[k], B_p[j][k], acc), k = 0 .. NU-1 instead of the
+// solver's x1: ONE chain, one rounding per term, on the DPP blocks whatever MODE says (the order of the forward pass under MODE 2: a plant
+// equal to the model hands on the same bits).  x0 is what the state lanes still hold in slot 0, u0 what the input lanes hold in slot
+// 1.  The lane's row is loaded at the END of a step, in blocks of four columns (plant_chain): nothing of it lives through the iteration
+// loop.  A disturbance row (PD) is added to the result.  Only x0 moves.  Composes with PD, PB, PL, PC and HET; not HALF, PF or ADAPT.
+// Run-time instantiated only; bit 6 of the sixth template argument (MODE | 64).  PD and PP forms write SolveArgs::state_log, if given.
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -790,7 +818,11 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PL = (MODE_PB & 8) != 0;
     constexpr bool PC = (MODE_PB & 16) != 0;
     constexpr bool PD = (MODE_PB & 32) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 64, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance");
+    constexpr bool PP = (MODE_PB & 64) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 128, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own");
+    static_assert(!PP || !ADAPT, "a plant of its own: not with adaptive rho (refused)");
+    static_assert(!PP || !HALF, "a plant of its own: not the half-row form");
+    static_assert(!PP || !PF, "a plant of its own: not the prefetch form");
     static_assert(!PD || !ADAPT, "per-instance disturbance: not with adaptive rho (refused)");
     static_assert(!PD || !HALF, "per-instance disturbance: not the half-row form");
     static_assert(!PD || !PF, "per-instance disturbance: not the prefetch form");
@@ -1335,6 +1367,19 @@ void admm_solve_kernel(const SolveArgs P) {
                 return plant_add(x1, P.dist[((size_t)dk * P.batch + d_b) * NX + j]);
             };
             (void)disturbed;
+            // PP: what the plant hands on for this lane -- the chain above over the row's x0 (slot 0 of the state lanes) and u0 (slot 1 of
+            // the input lanes); like `disturbed` called behind the iteration loop only, and everything it needs is formed there
+            auto plant_step = [&](const double x0_row, const double u0_row) -> double {
+                int p_b = b;
+                asm volatile("" : "+v"(p_b));
+                const unsigned long long raw = reinterpret_cast<unsigned long long>(P.plant);
+                const double* pt = reinterpret_cast<const double*>(raw & ~1ull) + ((raw & 1ull) ? (size_t)0 : (size_t)p_b * ((NZ + 1) * 16)) + j;
+                double acc = pt[NZ * 16];
+                plant_chain<0, NX>(acc, x0_row, pt);
+                plant_chain<NX, NU>(acc, u0_row, pt + NX * 16);
+                return acc;
+            };
+            (void)plant_step;
             const int iter_first = resumed ? P.iter_base : 0;  // (a multiple of check_termination: the countdown restarts in phase)
             for (int step = 0; step < nsteps; ++step) {        // closed-loop MPC steps fused in one launch
                 X[0] = x0v;                                    // work->x.col(0) = x0
@@ -1820,8 +1865,14 @@ void admm_solve_kernel(const SolveArgs P) {
                     // plant step x0 <- A x0 + B u_0 + f (== forward_pass x_1).  Input lanes hold u_0 in slot 1: their
                     // slot 0 is the neutral dummy and must stay 0, or its "slack" would enter the dual residual
                     x0v = is_state ? X[1] : 0.0;
+                    if constexpr (PP) {                        // (likewise; the chain runs on every lane of the row, the input lanes' rows are zero)
+                        if (step + 1 < nsteps && iter > iter0) { const double xp = plant_step(X[0], X[1]); x0v = is_state ? xp : 0.0; }
+                    }
                     if constexpr (PD) {                        // (a step that ran no iteration -- max_iter = 0 -- took no plant step; the last step's is the x0_next store)
                         if (step + 1 < nsteps && iter > iter0) x0v = disturbed(x0v, step);
+                    }
+                    if constexpr (PD || PP) {
+                        if (P.state_log && step + 1 < nsteps && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = x0v;
                     }
                 }
             }
@@ -1905,8 +1956,16 @@ void admm_solve_kernel(const SolveArgs P) {
                     for (int k = 0; k < NX; ++k) P.aP[(size_t)b * (NX * NX) + k + NX * j] = sP[grp * NX * NX + k + NX * j];
                 }
             }
-            if constexpr (PD) {                              // (the plant step of the launch's LAST MPC step)
-                if (P.x0_next && acc_iter > 0 && is_state) P.x0_next[(size_t)b * NX + j] = disturbed(X[1], nsteps - 1);
+            if constexpr (PD || PP) {                        // (the plant step of the launch's LAST MPC step)
+                if (P.x0_next && acc_iter > 0) {
+                    double xn = X[1];
+                    if constexpr (PP) xn = plant_step(X[0], X[1]);
+                    if constexpr (PD) xn = disturbed(xn, nsteps - 1);
+                    if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
+                    if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
+                } else if (P.state_log && is_state) {        // (no plant step: the x0 the launch left in place)
+                    P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = P.x0[(size_t)b * NX + j];
+                }
             } else
             if (P.x0_next && acc_iter > 0 && is_state) P.x0_next[(size_t)b * NX + j] = X[1];     // x1 = A x0 + B u0 + f (needs a forward pass)
             const double ps = grp_maxw<RL>(is_state ? rp : 0.0), pi = grp_maxw<RL>(is_input ? rp : 0.0);

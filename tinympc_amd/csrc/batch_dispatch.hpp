@@ -50,6 +50,18 @@ int inst_lin_kmax(const TinyBatch* b);
 bool inst_cones_active(const TinyBatch* b);
 bool disturbance_active(const TinyBatch* b);
 int dist_step_base(const TinyBatch* b);
+// a plant of its own: installed AND the next launch takes a plant step / the state log: switched on AND the next launch takes a plant
+// step / the pointer a PP form reads (SolveArgs::plant: bit 0 says "one block for all") / room for `rows` rows of the log, none written
+// yet / the coverage path's plant step behind one single-step launch: the new states from x0, the u0 of the x|u record and the plant,
+// plus this step's disturbance block (null: none), for the instances whose launch ran an iteration; then x0 <- them / row `row` of the
+// log <- x0 as it is now
+bool plant_active(const TinyBatch* b);
+bool state_log_active(const TinyBatch* b);
+int ensure_plant_blocks(TinyBatch* b);          // (the blocks of the PP forms, built where the setter left them out of date; enqueued on the batch's stream)
+const double* plant_kernel_pointer(const TinyBatch* b);
+int begin_state_log(TinyBatch* b, int rows);
+int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block);
+int enqueue_state_log_row(TinyBatch* b, int row);
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>
 void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }

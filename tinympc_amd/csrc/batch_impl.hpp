@@ -76,6 +76,22 @@ struct Disturbance {
     bool last = false;                             // (... applied the sequence: installed and a plant step taken)
     template <class F> void each_buffer(F f) { f(seq); }
 };
+// a plant model of its own at the plant step (tiny_batch_set_plant) and the log of what the plant step handed on (option "state_log").
+// src: the caller's A_p | B_p | f_p, kept on the device as given ([batch][...] column-major, or ONE set with kind 1; f_p may be null:
+// zero) -- what the getter and the coverage path's helper kernel read; built: the blocks the one-row kernel's PP forms read
+// (plant_entry of lane_tables.hpp: [batch or 1][nx + nu + 1][16]), made in front of the next launch; next: [batch][nx], where the
+// coverage path's helper kernel puts the new states before they replace x0.  log: [log_steps][batch][nx], the x0 every MPC step of the
+// last solve call handed on
+struct PlantStep {
+    int kind = 0;                                  // 0 none, 1 one plant for all, 2 every instance its own
+    bool dirty = false, last = false;              // (... took their plant step through it: installed and a plant step taken)
+    double *src[3] = {nullptr, nullptr, nullptr}, *built = nullptr, *next = nullptr;
+    bool log_on = false;                           // option "state_log"
+    double* log = nullptr;
+    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
+    int log_rows = 0;
+    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(next); f(log); }
+};
 
 constexpr size_t KPI_SKEW_BYTES = 0;             // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
@@ -165,7 +181,7 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -1,5 +1,5 @@
 // batch_instance.hip -- every instance its own problem data: a box, static and time-varying half-spaces, cone coefficients, a
-// disturbance sequence (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance of batch_impl.hpp).  Per family: the C ABI setter and
+// disturbance sequence, a plant model with its state log (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance, PlantStep of batch_impl.hpp).  Per family: the C ABI setter and
 // getter, the drop the shared setters of batch_api.hip call, the fill kernel that turns the caller's arrays into what the solve kernels
 // read (fill rules: lane_tables.hpp) and the ensure_instance_* that runs it when a setter or an enable switch has left the block out of date.
 // The sequences the families share -- upload, drop, read one instance back -- stand once, at the top.  Declarations: batch_dispatch.hpp.
@@ -285,6 +285,83 @@ bool disturbance_active(const TinyBatch* b) { return b->dist.seq && b->dist.step
 // (the kernels count steps in an int; a counter moved beyond +-2^30 is outside every sequence either way)
 int dist_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->dist.step, -(1L << 30), 1L << 30); }
 
+// ---- a plant of its own at the plant step (tiny_batch_set_plant): the caller's A_p | B_p | f_p -> [plants][nx + nu + 1][16 lanes], one
+// thread per (plant, column, lane); what lands there: plant_entry (lane_tables.hpp), nothing else.  One plant for all: one block (stride 0)
+static __global__ __launch_bounds__(256) void fill_plant_kernel(double* __restrict__ out, const double* __restrict__ A_p, const double* __restrict__ B_p,
+                                                                const double* __restrict__ f_p, int plants, int nx, int nu) {
+    const int rows = nx + nu + 1;
+    const size_t total = (size_t)plants * rows * 16;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % 16), k = (int)((e / 16) % rows);
+        const size_t p = e / ((size_t)16 * rows);
+        out[e] = plant_entry(A_p + p * nx * nx, B_p + p * nx * nu, f_p ? f_p + p * nx : nullptr, nx, nu, k, lane);
+    }
+}
+bool plant_active(const TinyBatch* b) { return b->plant.kind != 0 && (b->advance_x0 || b->steps_per_launch > 1); }
+bool state_log_active(const TinyBatch* b) { return b->plant.log_on && (b->advance_x0 || b->steps_per_launch > 1); }
+const double* plant_kernel_pointer(const TinyBatch* b) {
+    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(b->plant.built) | (b->plant.kind == 1 ? (uintptr_t)1 : (uintptr_t)0));
+}
+// (only the one-row kernel's PP forms read the blocks: the launch that binds one asks for them -- a launch without a plant step, and
+// the coverage path, which reads the caller's arrays, build and read nothing)
+int ensure_plant_blocks(TinyBatch* b) {
+    PlantStep& s = b->plant;
+    if (!s.kind || !s.dirty) return TINY_OK;
+    const int plants = s.kind == 1 ? 1 : b->batch;
+    const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
+    if (!s.built) HIP_TRY(b, hipMalloc(&s.built, total * sizeof(double)));
+    hipLaunchKernelGGL(fill_plant_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.built, s.src[0], s.src[1], s.src[2], plants, b->nx, b->nu);
+    HIP_TRY(b, hipGetLastError());
+    s.dirty = false;
+    return TINY_OK;
+}
+int begin_state_log(TinyBatch* b, int rows) {
+    PlantStep& s = b->plant;
+    s.log_rows = 0;
+    if (s.log_steps < rows) {
+        if (s.log) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(s.log); }
+        s.log = nullptr; s.log_steps = 0;
+        HIP_TRY(b, hipMalloc(&s.log, (size_t)rows * b->batch * b->nx * sizeof(double)));
+        s.log_steps = rows;
+    }
+    s.log_rows = rows;
+    return TINY_OK;
+}
+// the coverage path's plant step: one thread per (instance, state row), the chain of tiny_batch_set_plant in explicit fma()s.  Every
+// thread reads x0 and u0 and writes `next`, never x0 itself: the rows of an instance are read by its other threads.  An instance whose
+// launch ran no iteration took no plant step: its x0 passes through
+static __global__ __launch_bounds__(256) void coverage_plant_step_kernel(double* __restrict__ next, const double* __restrict__ x0, const double* __restrict__ prim,
+                                                                         const int4* __restrict__ status, const double* __restrict__ A_p, const double* __restrict__ B_p,
+                                                                         const double* __restrict__ f_p, int per_instance, const double* __restrict__ dist, int batch,
+                                                                         int nx, int nu, int N) {
+    const size_t total = (size_t)batch * nx;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(e % nx);
+        const size_t bb = e / nx, p = per_instance ? bb : 0;
+        if (status[bb].x <= 0) { next[e] = x0[e]; continue; }
+        const double *A = A_p + p * nx * nx, *B = B_p + p * nx * nu, *u0 = prim + bb * N * (nx + nu) + nx;
+        double acc = f_p ? f_p[p * nx + j] : 0.0;
+        for (int k = 0; k < nx; ++k) acc = fma(x0[bb * nx + k], A[j + nx * k], acc);
+        for (int k = 0; k < nu; ++k) acc = fma(u0[k], B[j + nx * k], acc);
+        next[e] = dist ? acc + dist[e] : acc;
+    }
+}
+int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block) {
+    PlantStep& s = b->plant;
+    const size_t total = (size_t)b->batch * b->nx;
+    if (!s.next) HIP_TRY(b, hipMalloc(&s.next, total * sizeof(double)));
+    hipLaunchKernelGGL(coverage_plant_step_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.next, b->d_x0, b->d_prim, b->d_status, s.src[0], s.src[1],
+                       s.src[2], s.kind == 2 ? 1 : 0, dist_block, b->batch, b->nx, b->nu, b->N);
+    HIP_TRY(b, hipGetLastError());
+    HIP_TRY(b, hipMemcpyAsync(b->d_x0, s.next, total * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+    return TINY_OK;
+}
+int enqueue_state_log_row(TinyBatch* b, int row) {
+    const size_t total = (size_t)b->batch * b->nx;
+    HIP_TRY(b, hipMemcpyAsync(b->plant.log + (size_t)row * total, b->d_x0, total * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+    return TINY_OK;
+}
+
 
 // ---- what a launch and tiny_batch_update_settings call (batch_dispatch.hpp)
 int ensure_instance_data(TinyBatch* b) {
@@ -297,6 +374,8 @@ void note_instance_data_read(TinyBatch* b) {
     b->ilin.last = inst_lin_active(b);                // (likewise)
     b->icone.last = inst_cones_active(b);
     b->dist.last = disturbance_active(b);             // (the one-row and the coverage kernel both add it; decide_path keeps such a launch off the tile kernel)
+    b->plant.log_rows = 0;                            // (the state log is the LAST solve call's: a launch that logs sizes it anew)
+    b->plant.last = plant_active(b);                  // (likewise: the one-row kernel's PP forms, or the helper kernel behind the coverage kernel)
 }
 void instance_data_settings_changed(TinyBatch* b) {
     if (b->ibox.on) b->ibox.dirty = true;             // (a disabled family is (-inf, +inf) in the array the kernels read)
@@ -434,6 +513,51 @@ int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_o
     if (step < 0 || step >= b->dist.steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, b->dist.steps);
     if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
     return read_instance(b, w_out, b->dist.seq + (size_t)step * b->batch * b->nx, instance, b->nx);
+}
+
+// a plant of its own at the plant step: A_p [batch][nx*nx], B_p [batch][nx*nu], f_p [batch][nx] or null (TINY_BROADCAST: one of each),
+// kept on the device as given; the blocks the one-row kernel reads are built from them in front of the next launch (ensure_plant).
+// Everything that can fail happens before anything installed is touched
+int tiny_batch_set_plant(TinyBatch* b, const double* A_p, const double* B_p, const double* f_p, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    PlantStep& s = b->plant;
+    if (A_p && !B_p) return fail(b, TINY_ERR_ARG, "plant: A_p without B_p");
+    double* fresh[3] = {nullptr, nullptr, nullptr};
+    if (A_p) {
+        const size_t plants = (flags & TINY_BROADCAST) ? 1 : (size_t)b->batch;
+        const UploadPart parts[3] = {{A_p, plants * b->nx * b->nx}, {B_p, plants * b->nx * b->nu}, {f_p, plants * b->nx}};
+        if (int rc = upload_fresh(b, parts, fresh, 3, flags, "plant")) return rc;
+    } else if (s.kind) HIP_TRY(b, hipStreamSynchronize(b->stream));       // remove: freed once the stream has run dry of its readers
+    for (int i = 0; i < 3; ++i) { if (s.src[i]) (void)hipFree(s.src[i]); s.src[i] = fresh[i]; }
+    if (s.built) (void)hipFree(s.built);                                 // (its size follows the kind; the state log and `next` stay)
+    s.built = nullptr;
+    s.kind = !A_p ? 0 : (flags & TINY_BROADCAST) ? 1 : 2;
+    s.dirty = s.kind != 0;
+    return TINY_OK;
+}
+// the plant instance `instance` is stepped by, as set: A_p [nx*nx], B_p [nx*nu], f_p [nx] (zero where none was given); any pointer may be NULL
+int tiny_batch_get_plant(TinyBatch* b, int instance, double* A_p, double* B_p, double* f_p) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->plant.kind) return fail(b, TINY_ERR_ARG, "no plant installed");
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    double* dst[3] = {A_p, B_p, f_p};
+    const size_t n[3] = {(size_t)b->nx * b->nx, (size_t)b->nx * b->nu, (size_t)b->nx};
+    for (int i = 0; i < 3; ++i) {
+        if (!dst[i]) continue;
+        if (b->plant.src[i]) { if (int rc = read_instance(b, dst[i], b->plant.src[i], b->plant.kind == 2 ? instance : 0, n[i])) return rc; }
+        else std::fill(dst[i], dst[i] + n[i], 0.0);
+    }
+    return TINY_OK;
+}
+// the x0 every MPC step of the last solve call handed on (option "state_log"): x0_next [steps][batch][nx]
+int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps) {
+    if (!b) return TINY_ERR_NULL;
+    if (steps <= 0 || steps > b->plant.log_rows || !b->plant.log) return fail(b, TINY_ERR_ARG, "no state log recorded (set_option state_log; advance_x0 or steps_per_launch)");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (x0_next) HIP_TRY(b, hipMemcpy(x0_next, b->plant.log, (size_t)steps * b->batch * b->nx * sizeof(double), hipMemcpyDeviceToHost));
+    return TINY_OK;
 }
 
 // every instance its own half-spaces, set 0 (static) or 1 (time-varying).  The caller's arrays are kept on the device as given; what

@@ -357,6 +357,24 @@ int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int f
     }
     return TINY_OK;
 }
+// a plant of its own at the plant step: A_p | B_p | f_p over the full batch axis in host memory, the caller's instance order; each shard
+// gets its instances' rows (TINY_BROADCAST: the one plant, as it is); A_p == NULL removes
+int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, const double* f_p, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "plant of a group: host arrays (TINY_HOST)");
+    const bool pass = !A_p || !B_p || (flags & TINY_BROADCAST);          // (nothing to slice; A_p without B_p: every shard refuses it)
+    const size_t nx = (size_t)g->nx, nu = (size_t)g->nu;
+    const double* src[3] = {A_p, B_p, f_p};
+    const size_t per[3] = {nx * nx, nx * nu, nx};
+    std::vector<double> stage[3];
+    for (int k = 0; k < g->n; ++k) {
+        const double* from[3] = {A_p, B_p, f_p};
+        if (!pass) for (int a = 0; a < 3; ++a) from[a] = shard_slice(g, k, src[a], per[a], &stage[a]);
+        const int rc = tiny_batch_set_plant(g->shard[k], from[0], from[1], from[2], pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

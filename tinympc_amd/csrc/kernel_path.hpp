@@ -39,6 +39,8 @@ struct PathFacts {
     bool tile_soc_failed = false;       // a cone / half-space / EXT form of the tile kernel could not
     // ---- the plant (appended: every decision with it off is what it was)
     bool disturbance = false;           // a per-instance disturbance sequence is installed AND the launch takes a plant step
+    bool plant = false;                 // a plant of its own is installed AND the launch takes a plant step
+    bool state_log = false;             // the state log is on AND the launch takes a plant step
 };
 
 // what path_facts can produce: the sweep of tests/dropin/kernel_path_driver.cpp counts these combinations only
@@ -57,7 +59,8 @@ enum KernelPath { ONE_ROW = 0, TILE = 1, COVERAGE = 2 };
 // what adaptive rho does not combine with; the texts callers read through tiny_batch_last_error
 // (REFUSE_ADAPTIVE_INSTANCE_CONES came last and keeps the values of the others; it is REPORTED in front of the overlapping cones: decide_path)
 enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIVE_HALFSPACES, REFUSE_ADAPTIVE_OVERLAPPING_CONES, REFUSE_ADAPTIVE_NO_REGISTER_FORM,
-                   REFUSE_ADAPTIVE_INSTANCE_CONES, REFUSE_ADAPTIVE_DISTURBANCE };      // (the last one is the last one reported, too)
+                   REFUSE_ADAPTIVE_INSTANCE_CONES, REFUSE_ADAPTIVE_DISTURBANCE, REFUSE_ADAPTIVE_PLANT,
+                   REFUSE_ADAPTIVE_STATE_LOG };      // (the last three are the last ones reported, too, in this order)
 constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
@@ -72,8 +75,10 @@ constexpr const char* PATH_REFUSAL_INSTANCE_CONES =
     "adaptive rho does not combine with per-instance cone coefficients (tiny_batch_set_instance_cone_coefficients): the adaptive cone "
     "form has no per-instance coefficients, and the coverage kernel does not take adaptive rho";
 constexpr const char* PATH_REFUSAL_DISTURBANCE = "adaptive rho does not combine with a per-instance disturbance";
+constexpr const char* PATH_REFUSAL_PLANT = "adaptive rho does not combine with a plant of its own at the plant step (tiny_batch_set_plant)";
+constexpr const char* PATH_REFUSAL_STATE_LOG = "adaptive rho does not combine with the state log (option state_log)";
 inline const char* path_refusal_message(PathRefusal r) {
-    return r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
+    return r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
 }
 
 struct PathDecision {
@@ -84,6 +89,7 @@ struct PathDecision {
     const char* rule;              // the rule that decided
     int pc = 0;                    // ONE_ROW: the per-instance cone-coefficient form
     int pd = 0;                    // ONE_ROW: the per-instance disturbance form (of whatever form the fields above name)
+    int pp = 0;                    // ONE_ROW: the form with a plant of its own (likewise; with or without pd)
 };
 
 // a one-row kernel exists for the shape: compiled in (counted even under no_jit), or one that run-time instantiation can make
@@ -102,18 +108,24 @@ inline PathDecision decide_path(const PathFacts& f) {
                                 : !regs            ? REFUSE_ADAPTIVE_NO_REGISTER_FORM
                                 : lf               ? REFUSE_ADAPTIVE_HALFSPACES          // shared ones, whether or not a one-row variant exists
                                 : f.disturbance    ? REFUSE_ADAPTIVE_DISTURBANCE         // (last: every combination refused before keeps its text)
+                                : f.plant          ? REFUSE_ADAPTIVE_PLANT
+                                : f.state_log      ? REFUSE_ADAPTIVE_STATE_LOG
                                                    : REFUSE_NONE;
-    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0}; };
-    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0}; };
+    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0}; };
+    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0}; };
     // every instance its own disturbance at the plant step: ONE rule pair, applied to whatever one-row answer the rules below give --
     // the PD form of that very form (PB, PL and PC forms take the bit as well and keep their rule's name; every other one-row answer
     // is "one_row:pd"), run-time instantiated only, so where hipRTC may not be tried, with debug outputs, under force_general and with
     // adaptive rho (refused) the coverage kernel answers: "cover:pd".  A coverage answer stays what it is, the tile kernel is not asked
+    // A plant of its own at the plant step: the same rule pair under its own names, "one_row:pp" / "cover:pp" -- the PP form of that
+    // very form, with the PD bit as well where a disturbance applies, under the same conditions.  The state log is written by the PD and
+    // PP forms: with neither installed it rides on the PD form with an empty sequence, which adds nothing (rule names: pd's)
     const bool pd_form = f.fits && hiprtc && !f.force_general && !f.debug && !f.adaptive;
+    const bool pp = f.plant, pd = f.disturbance || (f.state_log && !f.plant);
     auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) {
-        if (!f.disturbance) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0};
-        if (!pd_form) return cover("cover:pd");
-        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : "one_row:pd", pc, 1};
+        if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0};
+        if (!pd_form) return cover(pp ? "cover:pp" : "cover:pd");
+        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0};
     };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
@@ -128,7 +140,7 @@ inline PathDecision decide_path(const PathFacts& f) {
     // half-space / EXT forms and every form of a shape outside tile_dims.txt are run-time instantiated; EXT forms are for the shapes
     // the one-row kernel does not hold)
     const bool ext = f.tile_ext || f.hetero;
-    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance &&
+    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log &&
                           !((f.tile_is_jit || f.soc || lf || ext) && (f.no_jit || f.tile_soc_failed)) && !(ext && regs);
 
     // ---- the rules, in order
@@ -165,11 +177,11 @@ inline PathDecision decide_path(const PathFacts& f) {
 }
 
 // tiny_batch_kernel_path: 0 the one-row kernel, compiled in; 1 the tile kernel; 2 the coverage kernel; 3 the one-row kernel, instantiated at
-// run time (every form with a per-instance box, half-space set, cone coefficients or disturbance is); 4 the tile kernel, instantiated at run time
+// run time (every form with a per-instance box, half-space set, cone coefficients, disturbance or plant is); 4 the tile kernel, instantiated at run time
 inline int kernel_path_code(const PathDecision& d, const PathFacts& f) {
     if (d.kernel == TILE) return f.tile_is_jit ? 4 : 1;
     if (d.kernel == COVERAGE) return 2;
-    return (f.has_entry && !f.inst_bounds && !f.inst_lin && !d.pc && !d.pd) ? 0 : 3;
+    return (f.has_entry && !f.inst_bounds && !f.inst_lin && !d.pc && !d.pd && !d.pp) ? 0 : 3;
 }
 
 }  // namespace tinympc_amd

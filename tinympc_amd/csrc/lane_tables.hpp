@@ -177,4 +177,15 @@ __host__ __device__ inline double cone_entry(const double* cx, const double* cu,
     return 1.0;
 }
 
+// ---- a plant of its own (tiny_batch_set_plant): what entry (column k, lane) of a plant block [nx + nu columns | f_p][16 lanes] holds
+// (SolveArgs::plant).  State lane j keeps row j of A_p (columns 0 .. nx-1) and of B_p (columns nx .. nx+nu-1), both column-major as the
+// caller gave them, and f_p[j] in the last row of the block (column nx + nu); every other lane 0.  f_p may be null: zero
+__host__ __device__ constexpr int plant_block_doubles(int nx, int nu) { return (nx + nu + 1) * 16; }
+__host__ __device__ inline double plant_entry(const double* A_p, const double* B_p, const double* f_p, int nx, int nu, int k, int lane) {
+    if (lane >= nx) return 0.0;
+    if (k < nx) return A_p[lane + nx * k];
+    if (k < nx + nu) return B_p[lane + nx * (k - nx)];
+    return f_p ? f_p[lane] : 0.0;
+}
+
 }  // namespace tinympc_amd

@@ -16,10 +16,11 @@ struct JitKey {
     int pl = 0;               // every instance its own half-spaces (admm_kernel.hip.h PL): run-time instantiated only, kmax from 1
     int pc = 0;               // every instance its own cone coefficients (admm_kernel.hip.h PC): run-time instantiated only, with soc
     int pd = 0;               // every instance its own disturbance at the plant step (admm_kernel.hip.h PD): run-time instantiated only
+    int pp = 0;               // a plant of its own at the plant step (admm_kernel.hip.h PP): run-time instantiated only
     bool operator<(const JitKey& o) const {
-        const int a[15] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd},
-                  b[15] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd};
-        for (int i = 0; i < 15; ++i)
+        const int a[16] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd, pp},
+                  b[16] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd, o.pp};
+        for (int i = 0; i < 16; ++i)
             if (a[i] != b[i]) return a[i] < b[i];
         return false;
     }
@@ -71,6 +72,7 @@ struct VariantFacts {
     bool pl = false, pb = false;       // the per-instance half-space / box form
     bool pc = false;                   // the per-instance cone-coefficient form
     bool pd = false;                   // the per-instance disturbance form: any of the above, or none, with bit 5
+    bool pp = false;                   // the form with a plant of its own: likewise, with bit 6 (with or without bit 5)
     // ---- from the problem
     bool soc = false, debug = false;
     int dpp_mode = 0;                  // option "dpp_mode" as set (values outside 0..2 count as 0)
@@ -108,7 +110,7 @@ inline bool variant_facts_consistent(const VariantFacts& f, const EntrySlots& s)
            (f.lin ? (f.pl ? f.lin_kmax == 0 || stride(f.lin_kmax) : stride(f.lin_kmax)) : f.lin_kmax == 0) &&
            (f.pl ? f.il_km >= 1 && f.il_km <= 32 : f.il_km == 0) &&
            !(f.pc && (!f.soc || f.pb || f.pl || f.lin || f.debug || f.adaptive || f.no_jit || f.variant_jit_failed)) &&
-           !(f.pd && (f.debug || f.adaptive || f.no_jit || f.variant_jit_failed));      // (decide_path: a PD form only where hipRTC may be tried)
+           !((f.pd || f.pp) && (f.debug || f.adaptive || f.no_jit || f.variant_jit_failed));      // (decide_path: a PD / PP form only where hipRTC may be tried)
 }
 
 struct VariantChoice {
@@ -144,12 +146,12 @@ inline VariantChoice choose_one_row_variant(const VariantFacts& f, const EntrySl
     // ---- the rungs: which compiled-in slot holds that key (PB, PL and PC are run-time instantiated only: the entry is not asked)
     // (the PD form of whatever the key is by now -- full rows, no PREFETCH slot --, on the UB form where the compiled-in rungs below would
     // take one: their conditions, asked of the key, since no rung is)
-    if (f.pd) {
-        k.pd = 1;
+    if (f.pd || f.pp) {                                                  // (PP: PD's rule, bit for bit)
+        k.pd = f.pd ? 1 : 0; k.pp = f.pp ? 1 : 0;
         if (!k.pb && !k.pc && !k.lin && !k.adapt && !dbg && k.mode == 2) k.ub = (f.uniform_ub && (!f.hetero || f.het_ub)) ? 1 : 0;
     }
     SlotRef want;
-    if (s.has_entry && !k.pb && !k.pl && !k.pc && !k.pd) {
+    if (s.has_entry && !k.pb && !k.pl && !k.pc && !k.pd && !k.pp) {
         if (k.adapt) { if (!k.soc && !k.het) want = SlotRef{SLOT_KADAPT, dbg}; }      // (with a cone or per-instance data: run-time instantiated, jit_prebuilt.txt)
         else if (!k.lin && !k.het) want = plain_slot(f.soc, f.debug, k.mode, f.uniform_ub);
         else if (k.lin && !k.het && !dbg && k.kmax == VARIANT_LIN_KMAX) want = SlotRef{SLOT_KLIN, soc, k.lin};

@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""GPU: what a plant model of its own at the plant step (tiny_batch_set_plant) costs when it changes nothing -- with the MODEL installed as
+the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
+by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
+(device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--package DIR] [--launches L] [--batch 65536]
+--workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
+                    reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
+--workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
+--plant none        nothing installed (the only form a tree without the feature has: --package DIR imports tinympc_amd from DIR)
+--plant shared      the model installed as ONE plant for all (TINY_BROADCAST)
+--plant own         the model installed per instance ([batch] copies)
+--plant host        nothing installed: per MPC step one single-step solve, x and u read back, x0 <- A x0 + B u0 + f in numpy, set_x0;
+                    --steps MPC steps per episode, wall clock per episode
+--state-log 1       with option "state_log" on
+Prints one JSON line: the median, minimum and maximum time in ms over the timed launches (episodes), the iterations accumulated and
+the read-backs that say which form ran.  profiles/plant.md is where the numbers go."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", choices=("rocket", "hover"), default="rocket")
+    ap.add_argument("--plant", choices=("none", "shared", "own", "host"), default="none")
+    ap.add_argument("--steps", type=int, default=90)
+    ap.add_argument("--package", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--launches", type=int, default=0, help="timed launches (default: 5 episodes / 50 warm steps)")
+    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--state-log", type=int, default=0)
+    a = ap.parse_args()
+    sys.path.insert(0, a.package)
+    import tinympc_amd as tm
+    B = a.batch
+    if a.workload == "rocket":
+        prob, extra = tm.load_problem("rocket_landing_20hz")
+        m = extra["mpc"]
+        nx, nu, N = prob["nx"], prob["nu"], prob["N"]
+        rng = np.random.default_rng(20260923)
+        x0 = 1.1 * np.array(m["xinit"]) * (1 + 0.05 * rng.uniform(-1, 1, (B, nx)))
+        xinit, xg = np.array(m["xinit"], dtype=float), np.array(m["xg"], dtype=float)
+        traj = np.stack([xinit + (xg - xinit) * float(i) / (m["NTOTAL"] - 1) for i in range(m["NTOTAL"])])
+        s = tm.TinyBatchSolver.from_problem(prob, B)
+        s.set_bound_constraints(np.array(m["x_min"]), np.array(m["x_max"]), np.full((nu, 1), m["u_min"]), np.full((nu, 1), m["u_max"]))
+        cx, cu = np.array(m["state_cone"]["c"], dtype=float).ravel(), np.array(m["input_cone"]["c"], dtype=float).ravel()
+        s.set_cone_constraints(m["state_cone"]["A"], m["state_cone"]["q"], cx, m["input_cone"]["A"], m["input_cone"]["q"], cu)
+        s.update_settings(abs_pri_tol=m["abs_pri_tol"], max_iter=m["max_iter"], en_state_soc=0, en_input_soc=1)
+        uref = np.zeros((nu, N - 1))
+        uref[2, :] = m["uref_z"]
+
+        def start():
+            s.reset()
+            s.set_u_ref(uref, broadcast=True)
+            s.set_reference_trajectory(traj)
+            s.set_x0(x0)
+    else:
+        prob, extra = tm.load_problem("quadrotor_20hz")
+        h = extra["hover"]
+        nx, nu, N = prob["nx"], prob["nu"], prob["N"]
+        s = tm.TinyBatchSolver.from_problem(prob, B)
+        s.set_bound_constraints(np.full((nx, 1), h["x_min"]), np.full((nx, 1), h["x_max"]), np.full((nu, 1), h["u_min"]), np.full((nu, 1), h["u_max"]))
+        s.update_settings(max_iter=h["max_iter"])
+        xref = np.tile(np.array(h["xref"], dtype=np.float64).reshape(nx, 1), (1, N))
+        hx0 = np.array(h["x0"], dtype=np.float64)
+
+        def start():
+            s.reset()
+            s.set_x_ref(xref, broadcast=True)
+            s.set_x0(hx0, broadcast=True)
+    A, Bm = np.asarray(prob["A"], dtype=float).reshape(nx, nx), np.asarray(prob["B"], dtype=float).reshape(nx, nu)
+    f = np.zeros(nx) if prob.get("f") is None else np.asarray(prob["f"], dtype=float).reshape(nx)
+    launches = a.launches or (5 if a.steps > 1 or a.plant == "host" else 50)
+    ms = []
+    if a.plant == "host":
+        for e in range(1 + launches):
+            start()
+            s.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                x0h = s.get("x0")
+                s.solve()
+                u0 = s.get("u")[:, :, 0]
+                s.get("x")                                # (the read-back a host-side plant that also looks at the prediction pays)
+                s.set_x0(x0h @ A.T + u0 @ Bm.T + f)
+            s.synchronize()
+            if e >= 1:
+                ms.append(1e3 * (time.perf_counter() - t0))
+    else:
+        s.set_option("advance_x0", 1)
+        if a.steps > 1:
+            s.set_option("steps_per_launch", a.steps)
+        if a.state_log:
+            s.set_option("state_log", 1)
+        if a.plant == "shared":
+            s.set_plant(A, Bm, f)
+        elif a.plant == "own":
+            s.set_plant(np.broadcast_to(A, (B, nx, nx)), np.broadcast_to(Bm, (B, nx, nu)), np.broadcast_to(f, (B, nx)))
+        if a.steps > 1:
+            for e in range(2 + launches):                 # every episode is the same work; the first two settle the dispatch
+                start()
+                s.set_option("timing", 1)
+                s.solve_async()
+                t = float(np.sum(s.timing_ms()))
+                if e >= 2:
+                    ms.append(t)
+        else:
+            start()
+            for _ in range(a.warmup):
+                s.solve_async()
+            s.synchronize()
+            s.set_option("timing", launches)
+            for _ in range(launches):
+                s.solve_async()
+            s.synchronize()
+            ms = list(s.timing_ms())
+    ms = np.array(ms)
+    it = s.status()["iter"]
+    total = s.reduce_stats()[7]                           # iterations accumulated since the last reset
+    out = dict(workload=a.workload, plant=a.plant, steps=a.steps, state_log=a.state_log, batch=B, launches=launches, median_ms=float(np.median(ms)), min_ms=float(ms.min()),
+               max_ms=float(ms.max()), accumulated_iters=float(total), last_iter_mean=float(it.mean()), last_iter_max=int(it.max()), kernel_path=s.kernel_path(),
+               uniform_bounds=int(s.get_option("last_uniform_bounds")))
+    if "tiny_batch_set_plant" in tm.BATCH_SYMBOLS:
+        out.update(plant_kind=int(s.get_option("plant")), last_plant=int(s.get_option("last_plant")))
+    print(json.dumps(out), flush=True)
+    s.close()
+
+
+if __name__ == "__main__":
+    main()
