@@ -36,6 +36,9 @@ CASES = {
     "6_3_10_pl": dict(shape=(6, 3, 10), B=11, hetero=False, on=("lin",), own=("lin",), option=None, path="jit"),
     "6_3_10_pc": dict(shape=(6, 3, 10), B=11, hetero=False, on=("cones",), own=("cones",), option=None, path="jit"),
     "6_3_10_pl_pc": dict(shape=(6, 3, 10), B=11, hetero=False, on=("cones", "lin"), own=("cones", "lin"), option=None, path="cover"),
+    # the extreme splits of a full row (instance_bounds_cases.EDGE_SHAPES): the row w[k][i] ends at lane 14 / is lane 0 alone, N - 1 = 2
+    "15_1_3": dict(shape=ibc.EDGE_SHAPES[0], B=11, hetero=False, on=("box",), own=(), option=None, path="jit"),
+    "1_15_3": dict(shape=ibc.EDGE_SHAPES[1], B=11, hetero=False, on=("box",), own=(), option=None, path="jit"),
 }
 COMPOSITION = ("6_3_10_pb", "6_3_10_pl", "6_3_10_pc", "6_3_10_pl_pc")
 # cases whose first draw fails check_case (6_3_10_cones: an instance whose loop diverges): name -> seed offset.  The draw kept

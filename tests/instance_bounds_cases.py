@@ -12,6 +12,9 @@ from cpu_solvers import OracleSolver
 
 KEYS = ("x", "u", "vnew", "znew", "g", "y", "v", "z")
 MAX_ITER = 60
+# nx + nu = 16 split as one input / one state: the lane tables are [batch][16] blocks, and here the field boundary sits at lane 15 / lane 1
+# (the per-instance box, disturbance and plant cases all take these two shapes)
+EDGE_SHAPES = [(15, 1, 3), (1, 15, 3)]
 
 
 def random_family(nx, nu, N, seed):

@@ -36,10 +36,12 @@ CASES = {
     "6_3_10_with_pl": dict(shape=(6, 3, 10), B=11, hetero=False, Acx=[1], Acu=[0], on=(1, 1), extra="pl", coef="random", path="cover"),
     "6_3_10_with_box": dict(shape=(6, 3, 10), B=11, hetero=False, Acx=[1], Acu=[0], on=(1, 1), extra="box", coef="random", path="cover"),
     "6_3_10_force_general": dict(shape=(6, 3, 10), B=13, hetero=False, Acx=[1], Acu=[0], on=(1, 1), extra="force_general", coef="random", path="cover"),
+    # the cones on the last rows of a full DPP row: state rows 10..12, inputs 0..2 = lanes 13..15
+    "13_3_4": dict(shape=(13, 3, 4), B=11, hetero=False, Acx=[10], Acu=[0], on=(1, 1), extra=None, coef="random", path="jit"),
 }
 # cases whose first draw fails check_case (6_3_10_input: an instance whose input cone never projects) or solves every instance in two or
 # three iterations: name -> seed offset.  The draws kept spread the cold iteration counts between a handful and the cap
-RESEED = {"6_3_10_both": 7, "6_3_10_input": 8, "6_3_10_state": 11}
+RESEED = {"6_3_10_both": 7, "6_3_10_input": 8, "6_3_10_state": 11, "13_3_4": 1}      # (13_3_4: an input cone that never projects)
 
 
 def keys(c):

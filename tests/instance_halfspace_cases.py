@@ -33,7 +33,7 @@ def keys(lin, cone=False):
 
 
 RHO_SCALE = 0.1
-RESEED = {(5, 3, 7, False, 11, 3, False, False): 1}      # cases whose first draw left an instance with a family that never projects (check_case)
+RESEED = {(5, 3, 7, False, 11, 3, False, False): 1, (13, 3, 4, False, 11, 3, False, False): 2}      # cases whose first draw left an instance with a family that never projects (check_case)
 
 
 def family(nx, nu, N, seed):
@@ -175,7 +175,8 @@ def check_case(nx, nu, N, hetero, B, lin=3, cone=False, box=False):
 # every case the GPU tests use: (nx, nu, N, hetero, B, lin, cone, box)
 GPU_CASES = [(12, 4, 10, False, 13, 1, False, False), (12, 4, 10, False, 13, 2, False, False), (12, 4, 10, False, 13, 3, False, False),
              (12, 4, 10, True, 11, 3, False, False), (6, 3, 10, False, 13, 3, True, False), (5, 3, 7, False, 11, 3, False, False),
-             (4, 2, 30, False, 11, 2, False, False), (20, 4, 10, False, 11, 3, False, False), (12, 4, 10, False, 11, 2, False, True)]
+             (4, 2, 30, False, 11, 2, False, False), (20, 4, 10, False, 11, 3, False, False), (12, 4, 10, False, 11, 2, False, True),
+             (13, 3, 4, False, 11, 3, False, False)]                # all 16 lanes in use, the inputs in lanes 13..15, N - 1 = 3
 
 
 @functools.lru_cache(maxsize=None)

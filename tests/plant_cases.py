@@ -36,8 +36,12 @@ CASES = {
     "12_4_10_hetero": dict(shape=(12, 4, 10), B=11, hetero=True),      # per-instance problem data (composition; plant equal to the model)
     "6_3_10": dict(shape=(6, 3, 10), B=11, hetero=False),              # composition with PB / PD; the sharded group
     "20_8_10": dict(shape=(20, 8, 10), B=11, hetero=False),            # a tile-kernel shape: the coverage path
+    # the extreme splits of a full row (instance_bounds_cases.EDGE_SHAPES): a chain of 15 A_p terms and one B_p term, and the reverse
+    "15_1_3": dict(shape=ibc.EDGE_SHAPES[0], B=11, hetero=False),
+    "1_15_3": dict(shape=ibc.EDGE_SHAPES[1], B=11, hetero=False),
 }
 ORACLE_CASES = ("4_2_10", "5_3_7", "12_4_10")
+EDGE_CASES = ("15_1_3", "1_15_3")                 # every instance against its own oracle loop, as ORACLE_CASES (test a. of tests/test_gpu_plant.py)
 
 
 def fma(a, b, c):

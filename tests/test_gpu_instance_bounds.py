@@ -30,6 +30,9 @@ FORMS = {
     "hetero_noub": (12, 4, 10, True, 11, {"het_ub": 0}, "jit"),
     "3_2_2_no_jit": (3, 2, 2, False, 11, {"no_jit": 1}, "cover"),
     "20_8_10": (20, 8, 10, False, 11, {}, "cover"),
+    # the extreme splits of a full row (instance_bounds_cases.EDGE_SHAPES): the field boundary of the [batch][16] lane blocks at lane 15 / lane 1
+    "15_1_3": ibc.EDGE_SHAPES[0] + (False, 11, {}, "jit"),
+    "1_15_3": ibc.EDGE_SHAPES[1] + (False, 11, {}, "jit"),
 }
 
 

@@ -103,6 +103,7 @@ FORMS = {
     "20_4_10": ((20, 4, 10, False, 11, 3, False, False), {}, "cover"),           # a tile-kernel shape
     "12_4_10_box": ((12, 4, 10, False, 11, 2, False, True), {}, "cover"),        # a per-instance box at the same time
     "12_4_10_force_general": ((12, 4, 10, False, 13, 3, False, False), {"force_general": 1}, "cover"),
+    "13_3_4": ((13, 3, 4, False, 11, 3, False, False), {}, "jit"),              # all 16 lanes in use, the inputs in lanes 13..15
 }
 assert sorted({f[0] for f in FORMS.values()}) == sorted(ihc.GPU_CASES)
 

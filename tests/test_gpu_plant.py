@@ -130,7 +130,7 @@ def assert_log_follows_the_reference_plant(c, plant, run, w=None):
 
 
 # ---- a. ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", pc.ORACLE_CASES)
+@pytest.mark.parametrize("name", pc.ORACLE_CASES + pc.EDGE_CASES)
 def test_every_instance_follows_its_own_oracle_loop_under_its_own_plant(name):
     pc.check_case(name)                                              # (the oracle alone: before anything runs on the GPU)
     c, want = pc.case(name), pc.oracle_case(name)

@@ -63,7 +63,7 @@ def test_the_reference_plant_step_is_the_chain_rounded_once_per_term():
     assert np.array_equal(pc.plant_step(A, B, None, x0, u0), pc.plant_step(A, B, np.zeros(nx), x0, u0))
 
 
-@pytest.mark.parametrize("name", pc.ORACLE_CASES)
+@pytest.mark.parametrize("name", pc.ORACLE_CASES + pc.EDGE_CASES)
 def test_the_cases_of_the_gpu_tests_meet_their_conditions(name):
     pc.check_case(name)
     c = pc.case(name)
