@@ -266,6 +266,34 @@ int tiny_batch_get_plant(TinyBatch* b, int instance, double* A_p, double* B_p, d
  * combine with adaptive rho: a launch that takes a plant step with the log on is refused (TINY_ERR_UNSUPPORTED, "adaptive rho does not
  * combine with the state log") */
 int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps);
+/* measurement noise in a closed loop (advance_x0, steps_per_launch > 1): the controller solves from a noisy reading of the state while
+ * the plant evolves from the true one -- sensor noise without the host in the loop.  v [n_steps][batch][nx], step-major; flags TINY_HOST
+ * or TINY_DEVICE, with TINY_BROADCAST one [n_steps][nx] for all (as tiny_batch_set_disturbance); copied, the caller may free.  v == NULL or
+ * n_steps <= 0 removes the sequence.  A failed call leaves what was installed; tiny_batch_reset leaves the sequence and its counter alone.
+ * Meaning: while a sequence is installed, the x0 record is the plant's TRUE state.
+ *   Measurement: MPC step k of a launch that takes a plant step hands the solver xm = fl(x0 + v[k][i]) -- ONE IEEE double addition,
+ *     nothing fused into it; work->x[:,0] of that solve is xm and the whole solve runs from xm.
+ *   Plant step: it then starts from the true x0 and the applied u0, through the one fma chain tiny_batch_set_plant documents: by the
+ *     installed plant, or with none by the batch's own model A, B, f (instance i's own on a tiny_batch_setup_hetero batch; the library
+ *     forms the block itself, "plant" keeps reading 0); then fl(. + w[k][i]) where a disturbance row applies.  The result is the next
+ *     true x0, and what the state log records.
+ *   Step counter: k is a counter of its own with the disturbance counter's rules -- the setter rewinds it, every MPC step of a launch
+ *     with a plant step advances it (inside stretches too), option "measurement_step" moves it; steps with k outside [0, n_steps) hand
+ *     on x0 itself: no addition, not one of zero.
+ *   A step that ran no iteration (max_iter = 0) still sees its measurement in x[:,0]; it takes no plant step.
+ *   A launch without a plant step reads nothing, leaves the counter alone and runs the form it runs without a sequence.
+ * Read-backs (tiny_batch_get_option): "measurement_noise" n_steps as installed (0: none), "measurement_step" the counter,
+ * "last_measurement_noise" 1 when the last solve's launches applied the sequence.
+ * Where it runs: the one-row kernel's PM forms (run-time instantiated; always on a plant block: every form the PP forms exist for);
+ * everywhere else (tile-kernel shapes, overlapping cones, "debug", "force_general", "no_jit", a missing hipRTC) a helper kernel in front
+ * of each single-step launch of the coverage kernel forms the measurements and the one behind it takes the plant step, same bits.
+ * Adaptive rho on such a launch fails the solve with TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with measurement noise
+ * (tiny_batch_set_measurement_noise)").
+ * Out of scope: any estimator or filter (the solver is handed the reading as it is); the tile kernel (its shapes go to the coverage
+ * kernel, as with a plant); the half-row and PREFETCH forms; tiny_codegen; tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_measurement_noise(TinyBatch* b, const double* v, int n_steps, int flags);
+/* row `step` of instance `instance` as installed: v_out [nx]; TINY_ERR_ARG with none installed or an index outside it */
+int tiny_batch_get_measurement_noise(TinyBatch* b, int step, int instance, double* v_out);
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -548,6 +576,9 @@ int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int f
 /* a plant of its own (tiny_batch_set_plant): host arrays over the full batch axis in the caller's order, or with TINY_BROADCAST one
  * plant; A_p == NULL removes.  tiny_group_set_option forwards "state_log"; the log is read shard by shard (tiny_group_shard) */
 int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, const double* f_p, int flags);
+/* measurement noise (tiny_batch_set_measurement_noise): host, [n_steps][batch][nx] over the full batch axis in the caller's order, or
+ * with TINY_BROADCAST one [n_steps][nx]; NULL removes.  tiny_group_set_option forwards "measurement_step" */
+int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

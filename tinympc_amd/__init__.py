@@ -42,6 +42,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_instance_linear_constraints", "tiny_batch_set_instance_tv_linear_constraints", "tiny_batch_get_instance_linear_constraints",
     "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
     "tiny_batch_set_disturbance", "tiny_batch_get_disturbance", "tiny_batch_set_plant", "tiny_batch_get_plant", "tiny_batch_get_state_log",
+    "tiny_batch_set_measurement_noise", "tiny_batch_get_measurement_noise",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -54,7 +55,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -180,6 +181,8 @@ def lib():
         L.tiny_batch_get_instance_cone_coefficients.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
         L.tiny_batch_set_disturbance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.tiny_batch_get_disturbance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.tiny_batch_set_measurement_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.tiny_batch_get_measurement_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -249,6 +252,7 @@ def lib():
         L.tiny_group_set_instance_tv_linear_constraints.argtypes = [C.c_void_p, C.c_int, _dp, _dp, C.c_int, _dp, _dp]
         L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tiny_group_set_disturbance.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
+        L.tiny_group_set_measurement_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -478,6 +482,27 @@ class TinyBatchSolver:
         """w[step, i] (nx,) as installed"""
         out = np.zeros(self.nx)
         self._check(lib().tiny_batch_get_disturbance(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_disturbance")
+        return out
+
+    def set_measurement_noise(self, v):
+        """measurement noise in a closed loop (advance_x0, steps_per_launch > 1): x0 is the plant's true state, MPC step k solves from
+        x0 + v[k, i] and the plant step starts from x0.  v: (n_steps, batch, nx), or (n_steps, nx) for one sequence for all; None
+        removes it.  The step counter (option "measurement_step") starts at 0 and advances with every MPC step of such a launch; steps
+        outside v measure x0 itself"""
+        if v is None:
+            return self._check(lib().tiny_batch_set_measurement_noise(self._h, None, 0, HOST), "set_measurement_noise")
+        flat, n, bc = self._disturbance(v)
+        self._check(lib().tiny_batch_set_measurement_noise(self._h, flat.ctypes.data_as(C.c_void_p), n, HOST | bc), "set_measurement_noise")
+
+    def set_measurement_noise_device(self, v, n_steps, broadcast=False):
+        """the same from a device pointer (int) to [n_steps][batch][nx] doubles ([n_steps][nx] with broadcast) resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_measurement_noise(self._h, C.c_void_p(int(v)), int(n_steps), DEVICE | (BROADCAST if broadcast else 0)),
+                    "set_measurement_noise_device")
+
+    def get_measurement_noise(self, step, i):
+        """v[step, i] (nx,) as installed"""
+        out = np.zeros(self.nx)
+        self._check(lib().tiny_batch_get_measurement_noise(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_measurement_noise")
         return out
 
     def _plant(self, A_p, B_p, f_p):
@@ -936,6 +961,13 @@ class TinyGroupSolver:
             return self._check(lib().tiny_group_set_disturbance(self._h, None, 0, HOST), "set_disturbance")
         flat, n, bc = TinyBatchSolver._disturbance(self, w)
         self._check(lib().tiny_group_set_disturbance(self._h, flat.ctypes.data_as(_dp), n, HOST | bc), "set_disturbance")
+
+    def set_measurement_noise(self, v):
+        """measurement noise for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if v is None:
+            return self._check(lib().tiny_group_set_measurement_noise(self._h, None, 0, HOST), "set_measurement_noise")
+        flat, n, bc = TinyBatchSolver._disturbance(self, v)
+        self._check(lib().tiny_group_set_measurement_noise(self._h, flat.ctypes.data_as(_dp), n, HOST | bc), "set_measurement_noise")
 
     def get_disturbance(self, step, i):
         """w[step, i] of instance i (the caller's order): asked of the shard that holds it"""

@@ -32,7 +32,7 @@
 //     stride instead).  Rows that converge early are masked off by EXEC (per-row exit), the wave leaves the iteration loop
 //     when its last row has converged.
 //   * Template variants: SOC (second-order-cone slacks), DBG (keep q, r, p, d), MODE (how the row broadcast is issued),
-//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients), PD (per-instance disturbance at the plant step), PP (a plant model of its own there; see
+//     LIN / KMAX (static / time-varying half-spaces), HET (per-instance problem data), ADAPT, UB, HALF, PF, PB (per-instance box), PL (per-instance half-spaces), PC (per-instance cone coefficients), PD (per-instance disturbance at the plant step), PP (a plant model of its own there), PM (the solve from a measured state; see
 //     the kernel).  kernel_dims.txt lists the shapes
 //     compiled into the library; every other shape / variant is instantiated at run time from this very header (jit.hip).
 #pragma once
@@ -191,7 +191,16 @@ struct SolveArgs {
     // shard blockIdx % pf_shards (one counter for the whole device saturates at ~90 returning atomics per microsecond: 65 536 tiles
     // would take 0.7 ms).  The counters are never reset: a shard's waves draw exactly (its ticketed tiles) + (its waves) tickets per
     // launch, pf_base[x] is where this launch's begin (the host keeps the sums)
-    int pf_mask, pf_shards, pf_static;
+    // PM forms: the solve of MPC step `step` runs from the MEASURED state fl(x0 + v[meas_step0 + step][instance]) -- meas
+    // [meas_steps][batch][NX], step-major, indexed by INSTANCE like dist -- while the plant step starts from the true x0.  Only the PREFETCH
+    // form reads pf_mask, pf_shards and pf_static, and no PM form is one: the pointer and its two ints lie over them and the padding behind
+    union {
+        struct { int pf_mask, pf_shards, pf_static; };
+        struct {
+            const double* meas;
+            int meas_steps, meas_step0;
+        };
+    };
     // one-row kernel, PB forms: every instance its own box -- [batch][lo | hi][N slots][16 lanes], the slot convention of the shared table's
     // bounds block (lane_tables.hpp box_entry; built by batch_instance.hip from the caller's arrays).  PB and PF exclude each other, so the
     // pointer takes the place of the PREFETCH form's ticket counters: the argument block of every other form keeps its size and offsets
@@ -807,6 +816,14 @@ __device__ __forceinline__ void plant_chain(double& acc, const double src, const
 // 1.  The lane's row is loaded at the END of a step, in blocks of four columns (plant_chain): nothing of it lives through the iteration
 // loop.  A disturbance row (PD) is added to the result.  Only x0 moves.  Composes with PD, PB, PL, PC and HET; not HALF, PF or ADAPT.
 // Run-time instantiated only; bit 6 of the sixth template argument (MODE | 64).  PD and PP forms write SolveArgs::state_log, if given.
+// PM: measurement noise (SolveArgs::meas) -- the x0 record is the plant's TRUE state; MPC step k solves from xm = fl(x0 + v[k][b]) (ONE
+// double addition, plant_add; a step outside the sequence: x0 itself, no addition), so X[0], the cone / half-space slack of slot 0 and
+// the whole solve see xm, and the plant step behind the iteration loop starts from the true x0 again: plant_step(true x0, u0), then the
+// disturbance (PD).  PM implies PP: the launch always supplies a plant block (the model's own where none is installed).  The true state
+// is NOT carried through the iteration loop: a state lane stores what every plant step hands on to its own cell of x0_next and reads
+// that cell back behind the next step's loop (step 0 reads x0), the index formed behind an empty asm as in `disturbed`; the measurement
+// of the NEXT step is formed right there from the value in hand.  A step that ran no iteration takes no plant step: its true state
+// stays.  Composes with everything PP composes with.  Run-time instantiated only; bit 7 of the sixth template argument (MODE | 128).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -819,7 +836,12 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PC = (MODE_PB & 16) != 0;
     constexpr bool PD = (MODE_PB & 32) != 0;
     constexpr bool PP = (MODE_PB & 64) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 128, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own");
+    constexpr bool PM = (MODE_PB & 128) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 256, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise");
+    static_assert(!PM || PP, "measurement noise: a form with a plant block (PP, bit 6): the true state is stepped through it");
+    static_assert(!PM || !ADAPT, "measurement noise: not with adaptive rho (refused)");
+    static_assert(!PM || !HALF, "measurement noise: not the half-row form");
+    static_assert(!PM || !PF, "measurement noise: not the prefetch form");
     static_assert(!PP || !ADAPT, "a plant of its own: not with adaptive rho (refused)");
     static_assert(!PP || !HALF, "a plant of its own: not the half-row form");
     static_assert(!PP || !PF, "a plant of its own: not the prefetch form");
@@ -1253,7 +1275,18 @@ void admm_solve_kernel(const SolveArgs P) {
             double X[N], G[N], VN[N], VP[N], QX[N], Dn[N - 1];
             // cone slack cells of this lane (W plane of slot 0): sC[cw + s * SLOT_D (+ PL_GC | PL_VC)]
             const int cw = grp * N * SLOT_D + (j < NZ ? j : NZ);
-            const double x0v_in = is_state ? (PF ? pf_x0 : P.x0[(size_t)b * NX + j]) : 0.0;      // tiny_set_x0
+            // PM: what the solver is handed for the true state xt at MPC step `at_step` -- fl(xt + v[meas_step0 + at_step][b]) on a state
+            // lane where that row exists (wave-uniform test), else xt as it is
+            auto measured = [&](const double xt, const int at_step) -> double {
+                const int mk = P.meas_step0 + at_step;
+                if ((unsigned)mk >= (unsigned)P.meas_steps || !is_state) return xt;
+                int m_b = b;
+                asm volatile("" : "+v"(m_b));
+                return plant_add(xt, P.meas[((size_t)mk * P.batch + m_b) * NX + j]);
+            };
+            (void)measured;
+            double x0v_in = is_state ? (PF ? pf_x0 : P.x0[(size_t)b * NX + j]) : 0.0;      // tiny_set_x0
+            if constexpr (PM) x0v_in = measured(x0v_in, 0);
             const int cl = grp * N * CSL + (j < NZ ? j : NZ);  // LIN: this lane's cell of slot 0 (slot s: + s * CSL)
             double VL[LSR ? N : 1], GL[LSR ? N : 1], VT[LTR ? N : 1], GT[LTR ? N : 1];
             double Qd[DBG ? N : 1], Pd[DBG ? N : 1], Dd[DBG ? N : 1];
@@ -1380,6 +1413,21 @@ void admm_solve_kernel(const SolveArgs P) {
                 return acc;
             };
             (void)plant_step;
+            // PM: the true state MPC step `at_step` of this launch started from, re-read behind its iteration loop from where the plant
+            // step before put it (this lane's own cell of x0_next; step 0: x0) -- no register carries it through the loop.  x0_next need
+            // not be x0 (it is, in every launch the library makes): step 0 reads x0, every later step what the step before it stored to
+            // x0_next.  A launch of more than one step always has x0_next (bind_common_args: fused steps imply the plant step); the
+            // store in the step loop tests it all the same, as the last step's does, and without it every step reads x0
+            auto true_cell = [&]() -> size_t {                 // (this lane's cell of x0 / x0_next, formed where it is used)
+                int t_b = b;
+                asm volatile("" : "+v"(t_b));
+                return (size_t)t_b * NX + j;
+            };
+            auto true_x0 = [&](const int at_step, const size_t cell) -> double {
+                const double* from = (at_step == 0 || !P.x0_next) ? P.x0 : P.x0_next;
+                return is_state ? from[cell] : 0.0;
+            };
+            (void)true_cell; (void)true_x0;
             const int iter_first = resumed ? P.iter_base : 0;  // (a multiple of check_termination: the countdown restarts in phase)
             for (int step = 0; step < nsteps; ++step) {        // closed-loop MPC steps fused in one launch
                 X[0] = x0v;                                    // work->x.col(0) = x0
@@ -1865,6 +1913,20 @@ void admm_solve_kernel(const SolveArgs P) {
                     // plant step x0 <- A x0 + B u_0 + f (== forward_pass x_1).  Input lanes hold u_0 in slot 1: their
                     // slot 0 is the neutral dummy and must stay 0, or its "slack" would enter the dual residual
                     x0v = is_state ? X[1] : 0.0;
+                    if constexpr (PM) {                        // (X[0] is the measurement: the plant starts from the true state, and the next step is handed ITS measurement)
+                        if (step + 1 < nsteps) {
+                            const size_t cell = true_cell();
+                            double xt = true_x0(step, cell);
+                            if (iter > iter0) {
+                                const double xp = plant_step(xt, X[1]);
+                                xt = is_state ? xp : 0.0;
+                                if constexpr (PD) xt = disturbed(xt, step);
+                            }
+                            if (P.x0_next && is_state) P.x0_next[cell] = xt;      // (where true_x0 finds it; a step without a plant step: unchanged)
+                            if (P.state_log && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = xt;
+                            x0v = measured(xt, step + 1);
+                        }
+                    } else {
                     if constexpr (PP) {                        // (likewise; the chain runs on every lane of the row, the input lanes' rows are zero)
                         if (step + 1 < nsteps && iter > iter0) { const double xp = plant_step(X[0], X[1]); x0v = is_state ? xp : 0.0; }
                     }
@@ -1873,6 +1935,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     }
                     if constexpr (PD || PP) {
                         if (P.state_log && step + 1 < nsteps && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = x0v;
+                    }
                     }
                 }
             }
@@ -1956,6 +2019,17 @@ void admm_solve_kernel(const SolveArgs P) {
                     for (int k = 0; k < NX; ++k) P.aP[(size_t)b * (NX * NX) + k + NX * j] = sP[grp * NX * NX + k + NX * j];
                 }
             }
+            if constexpr (PM) {                              // (the plant step of the launch's LAST MPC step, from the true state)
+                const double xt = true_x0(nsteps - 1, true_cell());
+                if (P.x0_next && acc_iter > 0) {
+                    double xn = plant_step(xt, X[1]);
+                    if constexpr (PD) xn = disturbed(xn, nsteps - 1);
+                    if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
+                    if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
+                } else if (P.state_log && is_state) {
+                    P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xt;
+                }
+            } else
             if constexpr (PD || PP) {                        // (the plant step of the launch's LAST MPC step)
                 if (P.x0_next && acc_iter > 0) {
                     double xn = X[1];

@@ -349,7 +349,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
-    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant);   // (each names its own: batch_impl.hpp each_buffer)
+    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant); free_buffers(b->meas);   // (each names its own: batch_impl.hpp each_buffer)
     if (b->h_wire) hipHostFree(b->h_wire);
     if (b->d_hist) hipFree(b->d_hist);
     if (b->h_hist) hipHostFree(b->h_hist);
@@ -884,6 +884,7 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "repack_sort")) { if (value < -1 || value > 1) return fail(b, TINY_ERR_ARG, "repack_sort: 1, 0 or -1 (automatic)"); b->repack_sort = (int)value; }
     else if (!strcmp(name, "repack_dynamic")) b->repack_dynamic = value != 0;   // follow-up stages: tiles off a counter (1) or a fixed grid stride (0)
     else if (!strcmp(name, "traj_step")) b->traj_step = value;
+    else if (!strcmp(name, "measurement_step")) b->meas.step = value;       // the row of the measurement-noise sequence the next MPC step's measurement takes (outside it: none)
     else if (!strcmp(name, "disturbance_step")) b->dist.step = value;       // the row of the disturbance sequence the next plant step takes (outside it: none)
     else if (!strcmp(name, "timing")) {
         HIP_TRY(b, hipStreamSynchronize(b->stream));
@@ -1033,6 +1034,9 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "disturbance")) return b->dist.seq ? b->dist.steps : 0;   // steps of the per-instance disturbance sequence installed (tiny_batch_set_disturbance); 0: none
     if (!strcmp(name, "disturbance_step")) return b->dist.step;               // the row the next plant step takes
     if (!strcmp(name, "last_disturbance")) return b->dist.last ? 1 : 0;       // the last solve's launches applied the sequence: installed and a plant step taken
+    if (!strcmp(name, "measurement_noise")) return b->meas.seq ? b->meas.steps : 0;   // steps of the measurement-noise sequence installed (tiny_batch_set_measurement_noise); 0: none
+    if (!strcmp(name, "measurement_step")) return b->meas.step;               // the row the next MPC step's measurement takes
+    if (!strcmp(name, "last_measurement_noise")) return b->meas.last ? 1 : 0; // the last solve's launches applied the sequence: installed and a plant step taken
     if (!strcmp(name, "plant")) return b->plant.kind;                         // a plant of its own (tiny_batch_set_plant): 0 none, 1 one for all, 2 every instance its own
     if (!strcmp(name, "last_plant")) return b->plant.last ? 1 : 0;            // the last solve's launches took their plant step through it
     if (!strcmp(name, "state_log")) return b->plant.log_on ? 1 : 0;

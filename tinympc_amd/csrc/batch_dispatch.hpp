@@ -61,6 +61,12 @@ int ensure_plant_blocks(TinyBatch* b);          // (the blocks of the PP forms, 
 const double* plant_kernel_pointer(const TinyBatch* b);
 int begin_state_log(TinyBatch* b, int rows);
 int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block);
+// measurement noise: installed AND the next launch takes a plant step / the counter as the kernels take it / the coverage path's
+// measurements of one MPC step, xm <- fl(x0 + row `step` of the sequence): the array the launch takes as its x0 (x0 itself where the
+// row lies outside the sequence: nothing is enqueued)
+bool measurement_active(const TinyBatch* b);
+int meas_step_base(const TinyBatch* b);
+int enqueue_coverage_measurement(TinyBatch* b, long step, const double** x0_of_launch);
 int enqueue_state_log_row(TinyBatch* b, int row);
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>

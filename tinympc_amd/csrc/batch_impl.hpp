@@ -92,6 +92,20 @@ struct PlantStep {
     int log_rows = 0;
     template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(next); f(log); }
 };
+// measurement noise at the plant step of a closed loop (tiny_batch_set_measurement_noise): seq [steps][batch][nx], step-major like the
+// disturbance's, a broadcast sequence expanded on the device; step: the row the next MPC step's measurement takes (the disturbance
+// counter's rules).  While it applies the x0 record is the TRUE state and the plant step goes through a plant block: the installed
+// plant's, or the model's own -- model: A | B | f of a shared family as the coverage path's helper kernel reads them (a per-instance
+// family: the arrays tiny_batch_setup_hetero keeps), model_built: the block(s) the one-row kernel's PM forms read (plant_entry), both
+// made once: A, B and f are fixed at setup (no setter moves them; adaptive rho moves the cache only).  xm [batch][nx]: where the coverage path forms the measurements its launch takes as x0
+struct MeasurementNoise {
+    double* seq = nullptr;
+    int steps = 0;
+    long step = 0;
+    bool last = false;                             // (... applied the sequence: installed and a plant step taken)
+    double *model[3] = {nullptr, nullptr, nullptr}, *model_built = nullptr, *xm = nullptr;
+    template <class F> void each_buffer(F f) { f(seq); for (double*& p : model) f(p); f(model_built); f(xm); }
+};
 
 constexpr size_t KPI_SKEW_BYTES = 0;             // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
@@ -181,7 +195,7 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -1,5 +1,5 @@
 // batch_instance.hip -- every instance its own problem data: a box, static and time-varying half-spaces, cone coefficients, a
-// disturbance sequence, a plant model with its state log (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance, PlantStep of batch_impl.hpp).  Per family: the C ABI setter and
+// disturbance sequence, a plant model with its state log, a measurement-noise sequence (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance, PlantStep, MeasurementNoise of batch_impl.hpp).  Per family: the C ABI setter and
 // getter, the drop the shared setters of batch_api.hip call, the fill kernel that turns the caller's arrays into what the solve kernels
 // read (fill rules: lane_tables.hpp) and the ensure_instance_* that runs it when a setter or an enable switch has left the block out of date.
 // The sequences the families share -- upload, drop, read one instance back -- stand once, at the top.  Declarations: batch_dispatch.hpp.
@@ -281,6 +281,55 @@ static int expand_disturbance(TinyBatch* b, double* out, const double* seq, int 
     HIP_TRY(b, hipGetLastError());
     return TINY_OK;
 }
+// a step-major sequence [n_steps][batch][nx] (TINY_BROADCAST: [n_steps][nx], expanded on the device so that the kernels know one
+// layout), copied into S::seq with its counter rewound -- the disturbance and the measurement noise.  Everything that can fail happens
+// before anything installed is touched
+template <class S>
+static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, int flags, const char* what, const char* what_short) {
+    HIP_TRY(b, hipSetDevice(b->device));
+    if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
+        if (s.seq) { if (int rc = drop_buffers(b, s)) return rc; }
+        s.steps = 0; s.step = 0;
+        return TINY_OK;
+    }
+    const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row;
+    if (full / row != (size_t)n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
+        return fail(b, TINY_ERR_ARG, "%s: %d steps of %d instances do not fit an address", what_short, n_steps, b->batch);
+    double* fresh = nullptr;
+    if (!(flags & TINY_BROADCAST)) {
+        const UploadPart given = {w, full};
+        if (int rc = upload_fresh(b, &given, &fresh, 1, flags, what)) return rc;
+    } else {
+        // one sequence for all, staged and expanded.  The expanded buffer is allocated FIRST: a step count no device memory holds fails
+        // there, before the stage is sized by it and a byte of the caller's (then far shorter) array is read
+        const size_t given = (size_t)n_steps * b->nx;
+        double* stage = nullptr;
+        hipError_t err = hipMalloc(&fresh, full * sizeof(double));
+        int rc = TINY_OK;
+        if (err == hipSuccess) err = hipMalloc(&stage, given * sizeof(double));
+        if (err == hipSuccess) err = hipMemcpyAsync(stage, w, given * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
+        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps);
+        if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);      // (the caller may free its array; nothing reads the old one any more)
+        if (stage) (void)hipFree(stage);
+        if (err != hipSuccess || rc != TINY_OK) {
+            (void)hipGetLastError();
+            if (fresh) (void)hipFree(fresh);
+            return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
+        }
+    }
+    if (s.seq) (void)hipFree(s.seq);
+    s.seq = fresh; s.steps = n_steps; s.step = 0;
+    return TINY_OK;
+}
+// row `step` of instance `instance` of such a sequence, as set: out [nx]
+template <class S>
+static int read_sequence_row(TinyBatch* b, const S& s, int step, int instance, double* out, const char* none) {
+    if (!out) return fail(b, TINY_ERR_ARG, "null output");
+    if (!s.seq) return fail(b, TINY_ERR_ARG, "%s", none);
+    if (step < 0 || step >= s.steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, s.steps);
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    return read_instance(b, out, s.seq + (size_t)step * b->batch * b->nx, instance, b->nx);
+}
 bool disturbance_active(const TinyBatch* b) { return b->dist.seq && b->dist.steps > 0 && (b->advance_x0 || b->steps_per_launch > 1); }
 // (the kernels count steps in an int; a counter moved beyond +-2^30 is outside every sequence either way)
 int dist_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->dist.step, -(1L << 30), 1L << 30); }
@@ -299,14 +348,42 @@ static __global__ __launch_bounds__(256) void fill_plant_kernel(double* __restri
 }
 bool plant_active(const TinyBatch* b) { return b->plant.kind != 0 && (b->advance_x0 || b->steps_per_launch > 1); }
 bool state_log_active(const TinyBatch* b) { return b->plant.log_on && (b->advance_x0 || b->steps_per_launch > 1); }
+bool measurement_active(const TinyBatch* b) { return b->meas.seq && b->meas.steps > 0 && (b->advance_x0 || b->steps_per_launch > 1); }
+int meas_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->meas.step, -(1L << 30), 1L << 30); }
+// what a launch steps the state by: the plant installed, else -- a launch under measurement noise, which always goes through a plant
+// block -- the batch's own model: every instance's own A | B | f of a tiny_batch_setup_hetero batch, or the shared family's (uploaded once)
+struct PlantSource { const double* src[3]; bool per_instance; double* const* built; };
+static PlantSource plant_source(const TinyBatch* b) {
+    if (b->plant.kind) return {{b->plant.src[0], b->plant.src[1], b->plant.src[2]}, b->plant.kind == 2, &b->plant.built};
+    if (b->hetero) return {{b->d_hA, b->d_hB, b->d_hf}, true, &b->meas.model_built};
+    return {{b->meas.model[0], b->meas.model[1], b->meas.model[2]}, false, &b->meas.model_built};
+}
+static int ensure_model_source(TinyBatch* b) {
+    if (b->plant.kind || b->hetero || b->meas.model[0]) return TINY_OK;
+    const UploadPart parts[3] = {{b->A.a.data(), b->A.a.size()}, {b->B.a.data(), b->B.a.size()}, {b->f.a.data(), b->f.a.size()}};
+    return upload_fresh(b, parts, b->meas.model, 3, TINY_HOST, "model as plant");
+}
 const double* plant_kernel_pointer(const TinyBatch* b) {
-    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(b->plant.built) | (b->plant.kind == 1 ? (uintptr_t)1 : (uintptr_t)0));
+    const PlantSource p = plant_source(b);
+    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(*p.built) | (p.per_instance ? (uintptr_t)0 : (uintptr_t)1));
 }
 // (only the one-row kernel's PP forms read the blocks: the launch that binds one asks for them -- a launch without a plant step, and
-// the coverage path, which reads the caller's arrays, build and read nothing)
+// the coverage path, which reads the caller's arrays, build and read no block.  Under measurement noise with no plant installed the
+// arrays are the model's: a shared family's A | B | f are uploaded once, by whichever path asks first: ensure_model_source)
 int ensure_plant_blocks(TinyBatch* b) {
     PlantStep& s = b->plant;
-    if (!s.kind || !s.dirty) return TINY_OK;
+    if (!s.kind) {                                    // (no plant installed: the model's own block, made once)
+        if (b->meas.model_built) return TINY_OK;
+        if (int rc = ensure_model_source(b)) return rc;
+        const PlantSource p = plant_source(b);
+        const int plants = p.per_instance ? b->batch : 1;
+        const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
+        HIP_TRY(b, hipMalloc(&b->meas.model_built, total * sizeof(double)));
+        hipLaunchKernelGGL(fill_plant_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, b->meas.model_built, p.src[0], p.src[1], p.src[2], plants, b->nx, b->nu);
+        HIP_TRY(b, hipGetLastError());
+        return TINY_OK;
+    }
+    if (!s.dirty) return TINY_OK;
     const int plants = s.kind == 1 ? 1 : b->batch;
     const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
     if (!s.built) HIP_TRY(b, hipMalloc(&s.built, total * sizeof(double)));
@@ -348,12 +425,30 @@ static __global__ __launch_bounds__(256) void coverage_plant_step_kernel(double*
 }
 int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block) {
     PlantStep& s = b->plant;
+    if (int rc = ensure_model_source(b)) return rc;
+    const PlantSource p = plant_source(b);
     const size_t total = (size_t)b->batch * b->nx;
     if (!s.next) HIP_TRY(b, hipMalloc(&s.next, total * sizeof(double)));
-    hipLaunchKernelGGL(coverage_plant_step_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.next, b->d_x0, b->d_prim, b->d_status, s.src[0], s.src[1],
-                       s.src[2], s.kind == 2 ? 1 : 0, dist_block, b->batch, b->nx, b->nu, b->N);
+    hipLaunchKernelGGL(coverage_plant_step_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.next, b->d_x0, b->d_prim, b->d_status, p.src[0], p.src[1],
+                       p.src[2], p.per_instance ? 1 : 0, dist_block, b->batch, b->nx, b->nu, b->N);
     HIP_TRY(b, hipGetLastError());
     HIP_TRY(b, hipMemcpyAsync(b->d_x0, s.next, total * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
+    return TINY_OK;
+}
+// the coverage path's measurements of one MPC step: xm[e] = fl(x0[e] + v[e]) over the [batch][nx] block of that step's row -- one
+// IEEE addition per element, what plant_add does on the one-row kernel
+static __global__ __launch_bounds__(256) void coverage_measurement_kernel(double* __restrict__ xm, const double* __restrict__ x0, const double* __restrict__ v, size_t total) {
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) xm[e] = x0[e] + v[e];
+}
+int enqueue_coverage_measurement(TinyBatch* b, long step, const double** x0_of_launch) {
+    MeasurementNoise& s = b->meas;
+    *x0_of_launch = b->d_x0;
+    if (step < 0 || step >= s.steps) return TINY_OK;
+    const size_t total = (size_t)b->batch * b->nx;
+    if (!s.xm) HIP_TRY(b, hipMalloc(&s.xm, total * sizeof(double)));
+    hipLaunchKernelGGL(coverage_measurement_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.xm, b->d_x0, s.seq + (size_t)step * total, total);
+    HIP_TRY(b, hipGetLastError());
+    *x0_of_launch = s.xm;
     return TINY_OK;
 }
 int enqueue_state_log_row(TinyBatch* b, int row) {
@@ -375,6 +470,7 @@ void note_instance_data_read(TinyBatch* b) {
     b->icone.last = inst_cones_active(b);
     b->dist.last = disturbance_active(b);             // (the one-row and the coverage kernel both add it; decide_path keeps such a launch off the tile kernel)
     b->plant.log_rows = 0;                            // (the state log is the LAST solve call's: a launch that logs sizes it anew)
+    b->meas.last = measurement_active(b);             // (the one-row kernel's PM forms, or the helper kernel in front of the coverage kernel)
     b->plant.last = plant_active(b);                  // (likewise: the one-row kernel's PP forms, or the helper kernel behind the coverage kernel)
 }
 void instance_data_settings_changed(TinyBatch* b) {
@@ -465,54 +561,25 @@ int tiny_batch_get_instance_cone_coefficients(TinyBatch* b, int instance, double
     return TINY_OK;
 }
 
-// every instance its own additive disturbance at the plant step: w [n_steps][batch][nx] (TINY_BROADCAST: [n_steps][nx], expanded on the
-// device so that the kernels know one layout), copied.  Everything that can fail happens before anything installed is touched
+// every instance its own additive disturbance at the plant step
 int tiny_batch_set_disturbance(TinyBatch* b, const double* w, int n_steps, int flags) {
     if (!b) return TINY_ERR_NULL;
-    HIP_TRY(b, hipSetDevice(b->device));
-    Disturbance& s = b->dist;
-    if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
-        if (s.seq) { if (int rc = drop_buffers(b, s)) return rc; }
-        s.steps = 0; s.step = 0;
-        return TINY_OK;
-    }
-    const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row;
-    if (full / row != (size_t)n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
-        return fail(b, TINY_ERR_ARG, "disturbance: %d steps of %d instances do not fit an address", n_steps, b->batch);
-    double* fresh = nullptr;
-    if (!(flags & TINY_BROADCAST)) {
-        const UploadPart given = {w, full};
-        if (int rc = upload_fresh(b, &given, &fresh, 1, flags, "per-instance disturbance")) return rc;
-    } else {
-        // one sequence for all, staged and expanded.  The expanded buffer is allocated FIRST: a step count no device memory holds fails
-        // there, before the stage is sized by it and a byte of the caller's (then far shorter) array is read
-        const size_t given = (size_t)n_steps * b->nx;
-        double* stage = nullptr;
-        hipError_t err = hipMalloc(&fresh, full * sizeof(double));
-        int rc = TINY_OK;
-        if (err == hipSuccess) err = hipMalloc(&stage, given * sizeof(double));
-        if (err == hipSuccess) err = hipMemcpyAsync(stage, w, given * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
-        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps);
-        if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);      // (the caller may free its array; nothing reads the old one any more)
-        if (stage) (void)hipFree(stage);
-        if (err != hipSuccess || rc != TINY_OK) {
-            (void)hipGetLastError();
-            if (fresh) (void)hipFree(fresh);
-            return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "per-instance disturbance: %s", hipGetErrorString(err));
-        }
-    }
-    if (s.seq) (void)hipFree(s.seq);
-    s.seq = fresh; s.steps = n_steps; s.step = 0;
-    return TINY_OK;
+    return install_sequence(b, b->dist, w, n_steps, flags, "per-instance disturbance", "disturbance");
+}
+// measurement noise: what the solver sees of the state at MPC step k is fl(x0 + v[k][i]).  Removing it drops the model's plant block
+// and the coverage path's scratch array with it (both are made again by the launch that needs them)
+int tiny_batch_set_measurement_noise(TinyBatch* b, const double* v, int n_steps, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    return install_sequence(b, b->meas, v, n_steps, flags, "measurement noise", "measurement noise");
+}
+int tiny_batch_get_measurement_noise(TinyBatch* b, int step, int instance, double* v_out) {
+    if (!b) return TINY_ERR_NULL;
+    return read_sequence_row(b, b->meas, step, instance, v_out, "no measurement-noise sequence installed");
 }
 // row `step` of instance `instance`, as set: w_out [nx]
 int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out) {
     if (!b) return TINY_ERR_NULL;
-    if (!w_out) return fail(b, TINY_ERR_ARG, "null output");
-    if (!b->dist.seq) return fail(b, TINY_ERR_ARG, "no disturbance sequence installed");
-    if (step < 0 || step >= b->dist.steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, b->dist.steps);
-    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    return read_instance(b, w_out, b->dist.seq + (size_t)step * b->batch * b->nx, instance, b->nx);
+    return read_sequence_row(b, b->dist, step, instance, w_out, "no disturbance sequence installed");
 }
 
 // a plant of its own at the plant step: A_p [batch][nx*nx], B_p [batch][nx*nu], f_p [batch][nx] or null (TINY_BROADCAST: one of each),

@@ -339,9 +339,9 @@ int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, co
 }
 // every instance its own disturbance at the plant step: w [n_steps][batch][nx] over the full batch axis in host memory, the caller's
 // instance order; each shard gets [n_steps][its count][nx] (TINY_BROADCAST: the one sequence, as it is); NULL / n_steps <= 0 removes
-int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int flags) {
+static int group_set_sequence(TinyGroup* g, const double* w, int n_steps, int flags, int (*set)(TinyBatch*, const double*, int, int), const char* what) {
     if (!g) return TINY_ERR_NULL;
-    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "per-instance disturbance of a group: host arrays (TINY_HOST)");
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "%s of a group: host arrays (TINY_HOST)", what);
     const bool pass = !w || n_steps <= 0 || (flags & TINY_BROADCAST);
     const size_t nx = (size_t)g->nx;
     for (int k = 0; k < g->n; ++k) {
@@ -352,10 +352,17 @@ int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int f
                 for (size_t i = 0; i < cnt; ++i)
                     memcpy(g->stage.data() + ((size_t)s * cnt + i) * nx, w + ((size_t)s * g->batch + (size_t)global_index(g, k, (long)i)) * nx, nx * sizeof(double));
         }
-        const int rc = tiny_batch_set_disturbance(g->shard[k], pass ? w : g->stage.data(), n_steps, pass ? flags : TINY_HOST);
+        const int rc = set(g->shard[k], pass ? w : g->stage.data(), n_steps, pass ? flags : TINY_HOST);
         if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
     }
     return TINY_OK;
+}
+int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int flags) {
+    return group_set_sequence(g, w, n_steps, flags, tiny_batch_set_disturbance, "per-instance disturbance");
+}
+// measurement noise (tiny_batch_set_measurement_noise): the same layout, gathered the same way
+int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps, int flags) {
+    return group_set_sequence(g, v, n_steps, flags, tiny_batch_set_measurement_noise, "measurement noise");
 }
 // a plant of its own at the plant step: A_p | B_p | f_p over the full batch axis in host memory, the caller's instance order; each shard
 // gets its instances' rows (TINY_BROADCAST: the one plant, as it is); A_p == NULL removes

@@ -3,7 +3,7 @@
 the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
 by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
 (device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
-    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--package DIR] [--launches L] [--batch 65536]
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--package DIR] [--launches L] [--batch 65536]
 --workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
                     reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
 --workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
@@ -13,6 +13,10 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
 --plant host        nothing installed: per MPC step one single-step solve, x and u read back, x0 <- A x0 + B u0 + f in numpy, set_x0;
                     --steps MPC steps per episode, wall clock per episode
 --state-log 1       with option "state_log" on
+--noise A           measurement noise installed (tiny_batch_set_measurement_noise): every entry A * U(-1, 1), one row per MPC step of the
+                    run, the counter rewound per episode.  A = 0: an all-zero sequence -- fl(x + 0) = x, so a PM form solves exactly the
+                    problems the PP form with the model as plant solves, and the times differ by what the PM form costs
+                    (profiles/measurement_noise.md).  With --plant none the PM form steps by the model's own block
 Prints one JSON line: the median, minimum and maximum time in ms over the timed launches (episodes), the iterations accumulated and
 the read-backs that say which form ran.  profiles/plant.md is where the numbers go."""
 import argparse
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--state-log", type=int, default=0)
+    ap.add_argument("--noise", type=float, default=None, help="measurement noise of this amplitude (0: an all-zero sequence)")
     a = ap.parse_args()
     sys.path.insert(0, a.package)
     import tinympc_amd as tm
@@ -101,9 +106,14 @@ def main():
             s.set_plant(A, Bm, f)
         elif a.plant == "own":
             s.set_plant(np.broadcast_to(A, (B, nx, nx)), np.broadcast_to(Bm, (B, nx, nu)), np.broadcast_to(f, (B, nx)))
+        if a.noise is not None:
+            rows = a.steps if a.steps > 1 else a.warmup + launches
+            s.set_measurement_noise(a.noise * np.random.default_rng(7).uniform(-1.0, 1.0, (rows, B, nx)))
         if a.steps > 1:
             for e in range(2 + launches):                 # every episode is the same work; the first two settle the dispatch
                 start()
+                if a.noise is not None:
+                    s.set_option("measurement_step", 0)
                 s.set_option("timing", 1)
                 s.solve_async()
                 t = float(np.sum(s.timing_ms()))
@@ -127,6 +137,8 @@ def main():
                uniform_bounds=int(s.get_option("last_uniform_bounds")))
     if "tiny_batch_set_plant" in tm.BATCH_SYMBOLS:
         out.update(plant_kind=int(s.get_option("plant")), last_plant=int(s.get_option("last_plant")))
+    if a.noise is not None:
+        out.update(noise=a.noise, measurement_noise=int(s.get_option("measurement_noise")), last_measurement_noise=int(s.get_option("last_measurement_noise")))
     print(json.dumps(out), flush=True)
     s.close()
 
