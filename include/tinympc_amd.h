@@ -294,6 +294,42 @@ int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps);
 int tiny_batch_set_measurement_noise(TinyBatch* b, const double* v, int n_steps, int flags);
 /* row `step` of instance `instance` as installed: v_out [nx]; TINY_ERR_ARG with none installed or an index outside it */
 int tiny_batch_get_measurement_noise(TinyBatch* b, int step, int instance, double* v_out);
+/* a state estimator in a closed loop (advance_x0, steps_per_launch > 1): between the sensor and the MPC sits a fixed-gain observer --
+ * output-feedback MPC without the host in the loop.  One nx x nx innovation gain M per instance, or with TINY_BROADCAST one for all:
+ * M = L*C covers a Luenberger observer or a steady-state Kalman filter with any output matrix C.  Unmeasured states are zero columns
+ * of M (the noise entries on those columns are multiplied by zero); output-space noise v_y is installed as any v with C v = v_y
+ * (tiny_batch_set_measurement_noise takes state-space rows).
+ * Meaning: while an estimator is installed, the x0 record is the plant's TRUE state, as under measurement noise, and the batch carries
+ * an estimate record xp [batch][nx], the predicted estimate.  MPC step k of a launch that takes a plant step does, for instance i:
+ *   Measurement: xm = fl(x0 + v[k][i]) where a row of an installed measurement-noise sequence applies, by that feature's rules and
+ *     counter; else xm = x0, no addition: an estimator without noise is a perfect sensor behind a filter.
+ *   Correction: e[c] = fl(xm[c] - xp[c]), one IEEE subtraction per state; state row j: acc = xp[j]; acc = fma(e[c], M[j][c], acc),
+ *     c = 0 .. nx-1; xhat[j] = acc -- ONE chain, ascending c, one rounding per term, whatever dpp_mode says and on every kernel path.
+ *   Solve: from xhat -- work->x[:,0] of that solve is xhat, the slot-0 cone and half-space slack see it.
+ *   Prediction: by the controller's own model: acc = f[j]; acc = fma(xhat[c], A[j][c], acc), c < nx; acc = fma(u0[c], B[j][c], acc),
+ *     c < nu; xp[j] = acc -- the chain of tiny_batch_set_plant over the batch's model (instance i's own on a tiny_batch_setup_hetero batch).
+ *   Plant step: exactly as under measurement noise -- from the TRUE x0 and the applied u0, by the installed plant or with none by the
+ *     model, plus the disturbance row where one applies; the state log records the true states.
+ *   A step that ran no iteration (max_iter = 0) shows xhat in x[:,0]; it takes no plant step and no prediction, the estimate record keeps xp.
+ *   A launch without a plant step reads nothing, leaves the estimate record alone and runs the form it runs without an estimator.
+ * Two consequences: M = 0 with xp = x0 (no plant of its own, no disturbance) is bit-identical to a handle with nothing installed,
+ * whatever noise is installed; and with xp = x0, no noise and no plant of its own, e = 0 at every step and the same holds for any finite M.
+ * M [batch][nx*nx] column-major, or with TINY_BROADCAST one [nx*nx]; TINY_HOST | TINY_DEVICE; copied.  M == NULL removes the
+ * estimator (the estimate record is freed).  Installing one where none is installed sets xp = the x0 record as it stands;
+ * replacing the gain keeps xp.  A failed call leaves what was installed; tiny_batch_reset leaves gain and estimate alone.
+ * Read-backs (tiny_batch_get_option): "estimator" 0 none, 1 one gain for all, 2 per instance; "last_estimator" 1 when the last solve's
+ * launches went through it; "estimate_log".
+ * Where it runs: the one-row kernel's PE forms (run-time instantiated; every form the PM forms exist for); everywhere else (tile-kernel
+ * shapes, overlapping cones, "debug", "force_general", "no_jit", a missing hipRTC) helper kernels around each single-step launch of
+ * the coverage kernel correct and predict, same bits.  Adaptive rho on such a launch fails the solve with TINY_ERR_UNSUPPORTED
+ * ("adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)").
+ * Out of scope: time-varying or covariance-propagating filters; an output vector of its own dimension; gains computed on the device;
+ * the tile kernel; the half-row and PREFETCH forms; tiny_codegen; tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_estimator(TinyBatch* b, const double* M, int flags);
+int tiny_batch_get_estimator(TinyBatch* b, int instance, double* M_out);           /* as installed; TINY_ERR_ARG with none */
+int tiny_batch_set_estimate(TinyBatch* b, const double* xp, int flags);            /* [batch][nx]; HOST | DEVICE | BROADCAST ([nx]); TINY_ERR_ARG with no estimator */
+int tiny_batch_get_estimate(TinyBatch* b, double* xp_out);                         /* [batch][nx], host */
+int tiny_batch_get_estimate_log(TinyBatch* b, double* xhat, int steps);            /* option "estimate_log" = 1: [steps][batch][nx], the xhat every MPC step solved from */
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -579,6 +615,11 @@ int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, con
 /* measurement noise (tiny_batch_set_measurement_noise): host, [n_steps][batch][nx] over the full batch axis in the caller's order, or
  * with TINY_BROADCAST one [n_steps][nx]; NULL removes.  tiny_group_set_option forwards "measurement_step" */
 int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps, int flags);
+/* a state estimator (tiny_batch_set_estimator, tiny_batch_set_estimate): host, M [batch][nx*nx] / xp [batch][nx] over the full batch
+ * axis in the caller's order, or with TINY_BROADCAST one; M == NULL removes.  tiny_group_set_option forwards "estimate_log"; the log
+ * and the estimate are read shard by shard (tiny_group_shard) */
+int tiny_group_set_estimator(TinyGroup* g, const double* M, int flags);
+int tiny_group_set_estimate(TinyGroup* g, const double* xp, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

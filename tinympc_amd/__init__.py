@@ -43,6 +43,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
     "tiny_batch_set_disturbance", "tiny_batch_get_disturbance", "tiny_batch_set_plant", "tiny_batch_get_plant", "tiny_batch_get_state_log",
     "tiny_batch_set_measurement_noise", "tiny_batch_get_measurement_noise",
+    "tiny_batch_set_estimator", "tiny_batch_get_estimator", "tiny_batch_set_estimate", "tiny_batch_get_estimate", "tiny_batch_get_estimate_log",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -55,7 +56,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -183,6 +184,11 @@ def lib():
         L.tiny_batch_get_disturbance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         L.tiny_batch_set_measurement_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.tiny_batch_get_measurement_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.tiny_batch_set_estimator.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_estimator.argtypes = [C.c_void_p, C.c_int, _dp]
+        L.tiny_batch_set_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_estimate.argtypes = [C.c_void_p, _dp]
+        L.tiny_batch_get_estimate_log.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -253,6 +259,8 @@ def lib():
         L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tiny_group_set_disturbance.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_set_measurement_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
+        L.tiny_group_set_estimator.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.tiny_group_set_estimate.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -546,6 +554,61 @@ class TinyBatchSolver:
         """x0_next[steps, batch, nx]: the state every MPC step of the last solve call handed on (option "state_log" = 1)"""
         out = np.zeros((steps, self.batch, self.nx))
         self._check(lib().tiny_batch_get_state_log(self._h, out.ctypes.data_as(_dp), int(steps)), "get_state_log")
+        return out
+
+    def _gain(self, M):
+        """M (batch, nx, nx) | (nx, nx) -> (flat column-major array, broadcast flag)"""
+        G = np.asarray(M, dtype=np.float64)
+        one = G.ndim == 2
+        if one:
+            G = G[None]
+        n = 1 if one else self.batch
+        if G.shape != (n, self.nx, self.nx):
+            raise ValueError(f"estimator: M ({n}, {self.nx}, {self.nx}), got {G.shape}")
+        return np.ascontiguousarray(G.transpose(0, 2, 1)).ravel(), (BROADCAST if one else 0)
+
+    def _estimate(self, xp):
+        """xp (batch, nx) | (nx,) -> (flat array, broadcast flag)"""
+        x = _f64(xp)
+        if x.shape not in ((self.batch, self.nx), (self.nx,)):
+            raise ValueError(f"estimate: ({self.batch}, {self.nx}) or ({self.nx},), got {x.shape}")
+        return x.ravel(), (BROADCAST if x.ndim == 1 else 0)
+
+    def set_estimator(self, M):
+        """a fixed-gain state estimator in a closed loop (advance_x0, steps_per_launch > 1): x0 is the plant's true state, MPC step k
+        solves from xhat = xp + M (xm - xp), xm the (noisy) measurement, and the model predicts the next xp from xhat and u0.  M (batch,
+        nx, nx), or (nx, nx) for one gain for all (M = L C: a Luenberger observer, a steady-state Kalman filter); None removes it.
+        Installing one where none is installed starts the estimate at x0; replacing the gain keeps it"""
+        if M is None:
+            return self._check(lib().tiny_batch_set_estimator(self._h, None, HOST), "set_estimator")
+        flat, bc = self._gain(M)
+        self._check(lib().tiny_batch_set_estimator(self._h, flat.ctypes.data_as(C.c_void_p), HOST | bc), "set_estimator")
+
+    def set_estimator_device(self, M, broadcast=False):
+        """the same from a device pointer (int) to column-major [batch][nx*nx] doubles (one with broadcast) resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_estimator(self._h, C.c_void_p(int(M)), DEVICE | (BROADCAST if broadcast else 0)), "set_estimator_device")
+
+    def get_estimator(self, i):
+        """M (nx, nx) instance i is corrected by, as installed"""
+        out = np.zeros(self.nx * self.nx)
+        self._check(lib().tiny_batch_get_estimator(self._h, int(i), out.ctypes.data_as(_dp)), "get_estimator")
+        return out.reshape(self.nx, self.nx).T.copy()
+
+    def set_estimate(self, xp):
+        """the predicted estimate: xp (batch, nx), or (nx,) for all"""
+        flat, bc = self._estimate(xp)
+        self._check(lib().tiny_batch_set_estimate(self._h, flat.ctypes.data_as(C.c_void_p), HOST | bc), "set_estimate")
+
+    def get_estimate(self):
+        """xp (batch, nx): the predicted estimate the next MPC step corrects"""
+        out = np.zeros((self.batch, self.nx))
+        self._check(lib().tiny_batch_get_estimate(self._h, out.ctypes.data_as(_dp)), "get_estimate")
+        return out
+
+    def estimate_log(self, steps):
+        """xhat[steps, batch, nx]: the estimate every MPC step of the last solve call solved from (option "estimate_log" = 1)"""
+        out = np.zeros((steps, self.batch, self.nx))
+        self._check(lib().tiny_batch_get_estimate_log(self._h, out.ctypes.data_as(_dp), int(steps)), "get_estimate_log")
         return out
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
@@ -991,6 +1054,50 @@ class TinyGroupSolver:
         A, Bm, f, bc = TinyBatchSolver._plant(self, A_p, B_p, f_p)
         self._check(lib().tiny_group_set_plant(self._h, A.ctypes.data_as(_dp), Bm.ctypes.data_as(_dp), None if f is None else f.ctypes.data_as(_dp),
                                                HOST | bc), "set_plant")
+
+    def set_estimator(self, M):
+        """a state estimator for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if M is None:
+            return self._check(lib().tiny_group_set_estimator(self._h, None, HOST), "set_estimator")
+        flat, bc = TinyBatchSolver._gain(self, M)
+        self._check(lib().tiny_group_set_estimator(self._h, flat.ctypes.data_as(_dp), HOST | bc), "set_estimator")
+
+    def set_estimator_device(self, M, broadcast=False):
+        raise TinyMPCError("estimator of a group: host arrays (a device pointer belongs to one shard)")
+
+    def set_estimate(self, xp):
+        """the predicted estimate of every instance (the caller's order), or (nx,) for all"""
+        flat, bc = TinyBatchSolver._estimate(self, xp)
+        self._check(lib().tiny_group_set_estimate(self._h, flat.ctypes.data_as(_dp), HOST | bc), "set_estimate")
+
+    def get_estimator(self, i):
+        """the gain of instance i (the caller's order): asked of the shard that holds it"""
+        h, at = self._of_shard(i)
+        out = np.zeros(self.nx * self.nx)
+        rc = lib().tiny_batch_get_estimator(h, at, out.ctypes.data_as(_dp))
+        if rc != OK:
+            raise TinyMPCError(f"get_estimator failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+        return out.reshape(self.nx, self.nx).T.copy()
+
+    def _from_shards(self, steps, read, what):
+        out = np.zeros((steps, self.batch, self.nx))
+        for k in range(self.shards):
+            idx = self.shard_indices(k)
+            part = np.zeros((steps, len(idx), self.nx))
+            h = lib().tiny_group_shard(self._h, k)
+            rc = read(h, part)
+            if rc != OK:
+                raise TinyMPCError(f"{what} failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+            out[:, idx] = part
+        return out
+
+    def get_estimate(self):
+        """xp (batch, nx), gathered from the shards into the caller's order"""
+        return self._from_shards(1, lambda h, part: lib().tiny_batch_get_estimate(h, part.ctypes.data_as(_dp)), "get_estimate")[0]
+
+    def estimate_log(self, steps):
+        """xhat[steps, batch, nx] of the last solve call (option "estimate_log" = 1), gathered from the shards into the caller's order"""
+        return self._from_shards(steps, lambda h, part: lib().tiny_batch_get_estimate_log(h, part.ctypes.data_as(_dp), int(steps)), "get_estimate_log")
 
     def _of_shard(self, i):
         for k in range(self.shards):

@@ -153,7 +153,21 @@ struct SolveArgs {
     // (and the dead copies C1, C2) move every 5th iteration and persist from solve to solve.  arho [batch]; aK [batch][nu*nx],
     // aP [batch][nx*nx], aC1 [batch][nu*nu], aC2 [batch][nx*nx] column-major (aC1 / aC2 may be null); atab: ATAB_* lane tables --
     // one set for the family, or (HET && ADAPT) [batch][ATAB_DOUBLES], every instance's own (sensitivity_kernel.hip.h).
-    double *arho, *aK, *aP, *aC1, *aC2;
+    // PE forms: a fixed-gain state estimator between the measurement and the solve -- est_gain [instances][NX columns][16 lanes]
+    // (gain_entry of lane_tables.hpp; bit 0 of the pointer: one block for all, as at `plant`), est_xp [batch][NX] the predicted
+    // estimate, read at the top of a launch and stored behind its last step, est_log optional [steps][batch][NX], the xhat every MPC step
+    // solved from, est_model the MODEL's plant block (the layout and the bit 0 of `plant`), which predicts.  All indexed by INSTANCE.
+    // Only ADAPT forms read the adaptive-rho pointers, and no PE form is one: the four lie over the first four of them
+    union {
+        struct { double *arho, *aK, *aP, *aC1; };
+        struct {
+            const double* est_gain;
+            double* est_xp;
+            double* est_log;
+            const double* est_model;
+        };
+    };
+    double* aC2;
     const double* atab;
     double arho_min, arho_max;
     int aclip;
@@ -235,6 +249,10 @@ struct SolveArgs {
 // (the PB / PL / PC pointers share the ticket counters' place: the argument block every compiled-in form was built against stays what it was)
 static_assert(sizeof(SolveArgs) == 472 && __builtin_offsetof(SolveArgs, het_tabs) == 208 && __builtin_offsetof(SolveArgs, pf_mask) == 416 &&
               __builtin_offsetof(SolveArgs, pf_counter) == 432 && __builtin_offsetof(SolveArgs, pf_base) == 440, "SolveArgs: size and offsets are fixed");
+// (the PE pointers lie over arho, aK, aP and aC1, which stay where they were, and so does everything behind them)
+static_assert(__builtin_offsetof(SolveArgs, arho) == 304 && __builtin_offsetof(SolveArgs, est_gain) == 304 && __builtin_offsetof(SolveArgs, est_xp) == 312 &&
+              __builtin_offsetof(SolveArgs, est_log) == 320 && __builtin_offsetof(SolveArgs, est_model) == 328 && __builtin_offsetof(SolveArgs, aC1) == 328 &&
+              __builtin_offsetof(SolveArgs, aC2) == 336 && __builtin_offsetof(SolveArgs, atab) == 344, "SolveArgs: the estimator's pointers share the adaptive-rho ones' place");
 
 // ---- DPP row-broadcast FMA blocks ------------------------------------------------------------
 // One asm statement per block so that the two wait states a DPP read needs after a VALU write of
@@ -758,10 +776,26 @@ __device__ __forceinline__ double plant_add(double x1, const double w) {
     asm volatile("" : "+v"(x1));
     return x1 + w;
 }
+// the innovation of the PE forms: ONE IEEE double subtraction, kept apart from what produced its operands in the same way
+__device__ __forceinline__ double plant_sub(double xm, double xp) {
+    asm volatile("" : "+v"(xm), "+v"(xp));
+    return xm - xp;
+}
 // the plant step of the PP forms, columns COL0 .. COL0 + NCOL - 1 of ONE chain: acc = fma(bcast(src, lane c), m[c], acc), column after
 // column on the one accumulator.  Cut into blocks of at most four columns, each loading its own operands (m: this lane's entry of column
 // COL0, the columns 16 doubles apart): the same instructions in the same order as one ring1 over all columns, hence the same bits, at
 // 8 transient registers instead of 2 * NCOL
+// a pointer field of the argument block, read from the kernel-argument segment WHERE IT IS USED (the offset passes through an empty asm,
+// so the load stays behind it).  The PE forms read their four pointers this way: read as P.field they are loaded at the kernel's entry
+// and held in scalar registers through the tile, step and iteration loops -- on forms whose scalar registers already spill into
+// vector lanes, that cost vector registers and put rematerialised instructions into the iteration loop.  SolveArgs is the kernel's one
+// parameter: a field's offset in the segment is its offset in the struct
+template <class T>
+__device__ __forceinline__ T* late_arg(unsigned offset) {
+    asm volatile("" : "+s"(offset));
+    const char __attribute__((address_space(4)))* seg = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(T* const __attribute__((address_space(4)))*)(seg + offset);
+}
 template <int COL0, int NCOL>
 __device__ __forceinline__ void plant_chain(double& acc, const double src, const double* m) {
     if constexpr (NCOL > 0) {
@@ -824,6 +858,15 @@ __device__ __forceinline__ void plant_chain(double& acc, const double src, const
 // that cell back behind the next step's loop (step 0 reads x0), the index formed behind an empty asm as in `disturbed`; the measurement
 // of the NEXT step is formed right there from the value in hand.  A step that ran no iteration takes no plant step: its true state
 // stays.  Composes with everything PP composes with.  Run-time instantiated only; bit 7 of the sixth template argument (MODE | 128).
+// PE: a fixed-gain state estimator (SolveArgs::est_gain, est_xp, est_log, est_model) between the measurement and the solve.  MPC step k
+// solves from xhat = xp + M (xm - xp): e = fl(xm - xp) (ONE subtraction, plant_sub), then row j of M over the row's e on the accumulator
+// that starts at xp[j] -- plant_chain<0, NX>, the DPP blocks whatever MODE says -- so X[0], the slack of slot 0 and the whole solve see
+// xhat.  Behind the iteration loop the MODEL predicts the next xp from X[0] = xhat and X[1] = u0 (plant_by over est_model: the chain of
+// PP), the plant steps the TRUE state as under PM, the next step's measurement is formed and corrected right there: the prediction is
+// consumed in registers, est_xp is read at the top of a tile and stored behind the launch's last step only.  A step that ran no
+// iteration (max_iter = 0: then no step of the launch runs one) takes neither plant step nor prediction, and the next step's xp is the
+// record's.  PE implies PM and PP (a launch without a noise sequence binds an empty one); composes with everything PM composes with.
+// Run-time instantiated only; bit 8 of the sixth template argument (MODE | 256).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -837,7 +880,12 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PD = (MODE_PB & 32) != 0;
     constexpr bool PP = (MODE_PB & 64) != 0;
     constexpr bool PM = (MODE_PB & 128) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 256, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise");
+    constexpr bool PE = (MODE_PB & 256) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 512, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator");
+    static_assert(!PE || (PM && PP), "a state estimator: a form that solves from a measured state (PM, bit 7) on a plant block (PP, bit 6)");
+    static_assert(!PE || !ADAPT, "a state estimator: not with adaptive rho (refused)");
+    static_assert(!PE || !HALF, "a state estimator: not the half-row form");
+    static_assert(!PE || !PF, "a state estimator: not the prefetch form");
     static_assert(!PM || PP, "measurement noise: a form with a plant block (PP, bit 6): the true state is stepped through it");
     static_assert(!PM || !ADAPT, "measurement noise: not with adaptive rho (refused)");
     static_assert(!PM || !HALF, "measurement noise: not the half-row form");
@@ -1287,6 +1335,21 @@ void admm_solve_kernel(const SolveArgs P) {
             (void)measured;
             double x0v_in = is_state ? (PF ? pf_x0 : P.x0[(size_t)b * NX + j]) : 0.0;      // tiny_set_x0
             if constexpr (PM) x0v_in = measured(x0v_in, 0);
+            // PE: what the solver is handed for the measurement xm under the predicted estimate xp -- row j of the instance's gain over
+            // the row's innovation, on the accumulator that starts at xp (the input lanes' rows of the block are zero, and so are their
+            // xm and xp).  Called at the top of a tile and behind the iteration loop only; everything it needs is formed there
+            auto corrected = [&](const double xm, const double xp) -> double {
+                const double e = plant_sub(xm, xp);
+                int g_b = b;
+                asm volatile("" : "+v"(g_b));
+                const unsigned long long raw = reinterpret_cast<unsigned long long>(late_arg<const double>(__builtin_offsetof(SolveArgs, est_gain)));
+                const double* gt = reinterpret_cast<const double*>(raw & ~1ull) + ((raw & 1ull) ? (size_t)0 : (size_t)g_b * (NX * 16)) + j;
+                double acc = xp;
+                plant_chain<0, NX>(acc, e, gt);
+                return is_state ? acc : 0.0;
+            };
+            (void)corrected;
+            if constexpr (PE) x0v_in = corrected(x0v_in, is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[(size_t)b * NX + j] : 0.0);
             const int cl = grp * N * CSL + (j < NZ ? j : NZ);  // LIN: this lane's cell of slot 0 (slot s: + s * CSL)
             double VL[LSR ? N : 1], GL[LSR ? N : 1], VT[LTR ? N : 1], GT[LTR ? N : 1];
             double Qd[DBG ? N : 1], Pd[DBG ? N : 1], Dd[DBG ? N : 1];
@@ -1402,17 +1465,24 @@ void admm_solve_kernel(const SolveArgs P) {
             (void)disturbed;
             // PP: what the plant hands on for this lane -- the chain above over the row's x0 (slot 0 of the state lanes) and u0 (slot 1 of
             // the input lanes); like `disturbed` called behind the iteration loop only, and everything it needs is formed there
-            auto plant_step = [&](const double x0_row, const double u0_row) -> double {
+            auto plant_by = [&](const double* const blocks, const double x0_row, const double u0_row) -> double {
                 int p_b = b;
                 asm volatile("" : "+v"(p_b));
-                const unsigned long long raw = reinterpret_cast<unsigned long long>(P.plant);
+                const unsigned long long raw = reinterpret_cast<unsigned long long>(blocks);
                 const double* pt = reinterpret_cast<const double*>(raw & ~1ull) + ((raw & 1ull) ? (size_t)0 : (size_t)p_b * ((NZ + 1) * 16)) + j;
                 double acc = pt[NZ * 16];
                 plant_chain<0, NX>(acc, x0_row, pt);
                 plant_chain<NX, NU>(acc, u0_row, pt + NX * 16);
                 return acc;
             };
+            auto plant_step = [&](const double x0_row, const double u0_row) -> double { return plant_by(P.plant, x0_row, u0_row); };
             (void)plant_step;
+            // PE: the estimate the MODEL predicts from the row's xhat and u0 -- the same chain over SolveArgs::est_model
+            auto predicted = [&](const double xhat_row, const double u0_row) -> double {
+                const double xn = plant_by(late_arg<const double>(__builtin_offsetof(SolveArgs, est_model)), xhat_row, u0_row);
+                return is_state ? xn : 0.0;
+            };
+            (void)predicted;
             // PM: the true state MPC step `at_step` of this launch started from, re-read behind its iteration loop from where the plant
             // step before put it (this lane's own cell of x0_next; step 0: x0) -- no register carries it through the loop.  x0_next need
             // not be x0 (it is, in every launch the library makes): step 0 reads x0, every later step what the step before it stored to
@@ -1909,6 +1979,10 @@ void admm_solve_kernel(const SolveArgs P) {
                 // (the logs of a single-step launch: a stretch of a fused launch that batch_dispatch.hip cut up, "step_regroup")
                 if (P.iter_log && j == 0) P.iter_log[(size_t)step * P.batch + b] = solved ? iter : -iter;
                 if (P.u0_log && is_input) P.u0_log[((size_t)step * P.batch + b) * NU + (j - NX)] = X[1];
+                if constexpr (PE) {                            // (the xhat this step solved from: the state lanes still hold it in slot 0)
+                    double* const elog = late_arg<double>(__builtin_offsetof(SolveArgs, est_log));
+                    if (elog && is_state) elog[((size_t)step * P.batch + b) * NX + j] = X[0];
+                }
                 if (nsteps > 1) {
                     // plant step x0 <- A x0 + B u_0 + f (== forward_pass x_1).  Input lanes hold u_0 in slot 1: their
                     // slot 0 is the neutral dummy and must stay 0, or its "slack" would enter the dual residual
@@ -1917,6 +1991,8 @@ void admm_solve_kernel(const SolveArgs P) {
                         if (step + 1 < nsteps) {
                             const size_t cell = true_cell();
                             double xt = true_x0(step, cell);
+                            [[maybe_unused]] double est_next = 0.0;             // PE: the xp the next step corrects -- predicted here, or (no iteration ran) the record's
+                            if constexpr (PE) est_next = (iter > iter0) ? predicted(X[0], X[1]) : (is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[cell] : 0.0);
                             if (iter > iter0) {
                                 const double xp = plant_step(xt, X[1]);
                                 xt = is_state ? xp : 0.0;
@@ -1925,6 +2001,7 @@ void admm_solve_kernel(const SolveArgs P) {
                             if (P.x0_next && is_state) P.x0_next[cell] = xt;      // (where true_x0 finds it; a step without a plant step: unchanged)
                             if (P.state_log && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = xt;
                             x0v = measured(xt, step + 1);
+                            if constexpr (PE) x0v = corrected(x0v, est_next);
                         }
                     } else {
                     if constexpr (PP) {                        // (likewise; the chain runs on every lane of the row, the input lanes' rows are zero)
@@ -2021,6 +2098,12 @@ void admm_solve_kernel(const SolveArgs P) {
             }
             if constexpr (PM) {                              // (the plant step of the launch's LAST MPC step, from the true state)
                 const double xt = true_x0(nsteps - 1, true_cell());
+                if constexpr (PE) {                          // (... and the model's prediction from its xhat: the xp the next launch corrects)
+                    if (P.x0_next && acc_iter > 0) {
+                        const double xpn = predicted(X[0], X[1]);
+                        if (is_state) late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[(size_t)b * NX + j] = xpn;
+                    }
+                }
                 if (P.x0_next && acc_iter > 0) {
                     double xn = plant_step(xt, X[1]);
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);

@@ -68,6 +68,19 @@ bool measurement_active(const TinyBatch* b);
 int meas_step_base(const TinyBatch* b);
 int enqueue_coverage_measurement(TinyBatch* b, long step, const double** x0_of_launch);
 int enqueue_state_log_row(TinyBatch* b, int row);
+// a state estimator: installed AND the next launch takes a plant step / the gain blocks of the PE forms and the MODEL's plant block,
+// built where they are missing or out of date / the pointers a PE form reads (SolveArgs::est_gain, est_model: bit 0 says "one block
+// for all") / room for `rows` rows of the estimate log / the coverage path's two helper kernels around one single-step launch: in
+// front, xhat <- the correction of the measurement `*x0_of_launch` names (x0, or the measurement helper's array) under xp, handed to
+// the launch as its x0 and written to row `log_row` of the log; behind, xp <- the model's prediction from xhat and the u0 of the x|u
+// record, for the instances whose launch ran an iteration
+bool estimator_active(const TinyBatch* b);
+int ensure_estimator_blocks(TinyBatch* b);
+const double* estimator_gain_pointer(const TinyBatch* b);
+const double* model_kernel_pointer(const TinyBatch* b);
+int begin_estimate_log(TinyBatch* b, int rows);
+int enqueue_coverage_correction(TinyBatch* b, int log_row, const double** x0_of_launch);
+int enqueue_coverage_prediction(TinyBatch* b);
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>
 void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }

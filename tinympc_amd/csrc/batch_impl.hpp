@@ -106,8 +106,25 @@ struct MeasurementNoise {
     double *model[3] = {nullptr, nullptr, nullptr}, *model_built = nullptr, *xm = nullptr;
     template <class F> void each_buffer(F f) { f(seq); for (double*& p : model) f(p); f(model_built); f(xm); }
 };
+// a fixed-gain state estimator between the measurement and the solve (tiny_batch_set_estimator) and the log of what every MPC step
+// solved from (option "estimate_log").  src: the caller's M, kept on the device as given ([batch][nx*nx] column-major, or ONE with kind
+// 1) -- what the getter and the coverage path's helper kernel read; built: the blocks the one-row kernel's PE forms read (gain_entry of
+// lane_tables.hpp: [batch or 1][nx][16]), made in front of the next launch; xp [batch][nx]: the predicted estimate, STATE of the batch
+// like x0 (it lives as long as an estimator is installed); xhat [batch][nx]: where the coverage path forms the corrected estimates its
+// launch takes as x0; log: [log_steps][batch][nx].  The model's block and arrays, which predict, are MeasurementNoise's (both features
+// step through them)
+struct Estimator {
+    int kind = 0;                                  // 0 none, 1 one gain for all, 2 every instance its own
+    bool dirty = false, last = false;              // (... went through it: installed and a plant step taken)
+    double *src = nullptr, *built = nullptr, *xp = nullptr, *xhat = nullptr;
+    bool log_on = false;                           // option "estimate_log"
+    double* log = nullptr;
+    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
+    int log_rows = 0;
+    template <class F> void each_buffer(F f) { f(src); f(built); f(xp); f(xhat); f(log); }
+};
 
-constexpr size_t KPI_SKEW_BYTES = 0;             // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
+constexpr size_t KPI_SKEW_BYTES = 0;            // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
     int nx = 0, nu = 0, N = 0, batch = 0, device = 0, num_cus = 256;
     const tinympc_amd::KernelEntry* kernel = nullptr;
@@ -195,7 +212,7 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -353,13 +353,18 @@ int meas_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->meas.st
 // what a launch steps the state by: the plant installed, else -- a launch under measurement noise, which always goes through a plant
 // block -- the batch's own model: every instance's own A | B | f of a tiny_batch_setup_hetero batch, or the shared family's (uploaded once)
 struct PlantSource { const double* src[3]; bool per_instance; double* const* built; };
+// (the model alone: what a state estimator predicts by, whatever plant is installed)
+static PlantSource model_source(const TinyBatch* b) {
+    if (b->hetero) return {{b->d_hA, b->d_hB, b->d_hf}, true, &b->meas.model_built};
+    return {{b->meas.model[0], b->meas.model[1], b->meas.model[2]}, false, &b->meas.model_built};
+}
 static PlantSource plant_source(const TinyBatch* b) {
     if (b->plant.kind) return {{b->plant.src[0], b->plant.src[1], b->plant.src[2]}, b->plant.kind == 2, &b->plant.built};
     if (b->hetero) return {{b->d_hA, b->d_hB, b->d_hf}, true, &b->meas.model_built};
     return {{b->meas.model[0], b->meas.model[1], b->meas.model[2]}, false, &b->meas.model_built};
 }
-static int ensure_model_source(TinyBatch* b) {
-    if (b->plant.kind || b->hetero || b->meas.model[0]) return TINY_OK;
+static int ensure_model_source(TinyBatch* b, bool under_a_plant = false) {
+    if ((b->plant.kind && !under_a_plant) || b->hetero || b->meas.model[0]) return TINY_OK;
     const UploadPart parts[3] = {{b->A.a.data(), b->A.a.size()}, {b->B.a.data(), b->B.a.size()}, {b->f.a.data(), b->f.a.size()}};
     return upload_fresh(b, parts, b->meas.model, 3, TINY_HOST, "model as plant");
 }
@@ -370,19 +375,22 @@ const double* plant_kernel_pointer(const TinyBatch* b) {
 // (only the one-row kernel's PP forms read the blocks: the launch that binds one asks for them -- a launch without a plant step, and
 // the coverage path, which reads the caller's arrays, build and read no block.  Under measurement noise with no plant installed the
 // arrays are the model's: a shared family's A | B | f are uploaded once, by whichever path asks first: ensure_model_source)
+// the model's own block, made once -- with no plant installed what the PP forms step by, and under a state estimator what predicts,
+// next to whatever plant is installed
+static int ensure_model_block(TinyBatch* b) {
+    if (b->meas.model_built) return TINY_OK;
+    if (int rc = ensure_model_source(b, true)) return rc;
+    const PlantSource p = model_source(b);
+    const int plants = p.per_instance ? b->batch : 1;
+    const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
+    HIP_TRY(b, hipMalloc(&b->meas.model_built, total * sizeof(double)));
+    hipLaunchKernelGGL(fill_plant_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, b->meas.model_built, p.src[0], p.src[1], p.src[2], plants, b->nx, b->nu);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
 int ensure_plant_blocks(TinyBatch* b) {
     PlantStep& s = b->plant;
-    if (!s.kind) {                                    // (no plant installed: the model's own block, made once)
-        if (b->meas.model_built) return TINY_OK;
-        if (int rc = ensure_model_source(b)) return rc;
-        const PlantSource p = plant_source(b);
-        const int plants = p.per_instance ? b->batch : 1;
-        const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
-        HIP_TRY(b, hipMalloc(&b->meas.model_built, total * sizeof(double)));
-        hipLaunchKernelGGL(fill_plant_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, b->meas.model_built, p.src[0], p.src[1], p.src[2], plants, b->nx, b->nu);
-        HIP_TRY(b, hipGetLastError());
-        return TINY_OK;
-    }
+    if (!s.kind) return ensure_model_block(b);        // (no plant installed: the model's own block)
     if (!s.dirty) return TINY_OK;
     const int plants = s.kind == 1 ? 1 : b->batch;
     const size_t total = (size_t)plants * plant_block_doubles(b->nx, b->nu);
@@ -457,6 +465,107 @@ int enqueue_state_log_row(TinyBatch* b, int row) {
     return TINY_OK;
 }
 
+// ---- a state estimator between the measurement and the solve (tiny_batch_set_estimator): the caller's M -> [gains][nx][16 lanes], one
+// thread per (gain, column, lane); what lands there: gain_entry (lane_tables.hpp), nothing else.  One gain for all: one block
+static __global__ __launch_bounds__(256) void fill_gain_kernel(double* __restrict__ out, const double* __restrict__ M, int gains, int nx) {
+    const size_t total = (size_t)gains * nx * 16;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % 16), c = (int)((e / 16) % nx);
+        const size_t g = e / ((size_t)16 * nx);
+        out[e] = gain_entry(M + g * nx * nx, nx, c, lane);
+    }
+}
+bool estimator_active(const TinyBatch* b) { return b->est.kind != 0 && (b->advance_x0 || b->steps_per_launch > 1); }
+const double* estimator_gain_pointer(const TinyBatch* b) {
+    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(b->est.built) | (b->est.kind == 2 ? (uintptr_t)0 : (uintptr_t)1));
+}
+const double* model_kernel_pointer(const TinyBatch* b) {
+    const PlantSource p = model_source(b);
+    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(*p.built) | (p.per_instance ? (uintptr_t)0 : (uintptr_t)1));
+}
+// (only the one-row kernel's PE forms read the blocks; the coverage path reads the caller's array and the model's arrays)
+int ensure_estimator_blocks(TinyBatch* b) {
+    Estimator& s = b->est;
+    if (int rc = ensure_model_block(b)) return rc;
+    if (!s.kind || !s.dirty) return TINY_OK;
+    const int gains = s.kind == 1 ? 1 : b->batch;
+    const size_t total = (size_t)gains * gain_block_doubles(b->nx);
+    if (!s.built) HIP_TRY(b, hipMalloc(&s.built, total * sizeof(double)));
+    hipLaunchKernelGGL(fill_gain_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.built, s.src, gains, b->nx);
+    HIP_TRY(b, hipGetLastError());
+    s.dirty = false;
+    return TINY_OK;
+}
+int begin_estimate_log(TinyBatch* b, int rows) {
+    Estimator& s = b->est;
+    s.log_rows = 0;
+    if (s.log_steps < rows) {
+        if (s.log) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(s.log); }
+        s.log = nullptr; s.log_steps = 0;
+        HIP_TRY(b, hipMalloc(&s.log, (size_t)rows * b->batch * b->nx * sizeof(double)));
+        s.log_steps = rows;
+    }
+    s.log_rows = rows;
+    return TINY_OK;
+}
+// the coverage path's correction in front of one single-step launch: one thread per (instance, state row), the chain of
+// tiny_batch_set_estimator in explicit fma()s over e[c] = fl(xm[c] - xp[c]) -- what plant_sub and plant_chain do on the one-row kernel
+static __global__ __launch_bounds__(256) void coverage_correction_kernel(double* __restrict__ xhat, double* __restrict__ log, const double* __restrict__ xm,
+                                                                         const double* __restrict__ xp, const double* __restrict__ M, int per_instance, int batch,
+                                                                         int nx) {
+    const size_t total = (size_t)batch * nx;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(e % nx);
+        const size_t bb = e / nx;
+        const double* G = M + (per_instance ? bb : 0) * nx * nx;
+        double acc = xp[e];
+        for (int c = 0; c < nx; ++c) {
+            const double inno = xm[bb * nx + c] - xp[bb * nx + c];
+            acc = fma(inno, G[j + nx * c], acc);
+        }
+        xhat[e] = acc;
+        if (log) log[e] = acc;
+    }
+}
+int enqueue_coverage_correction(TinyBatch* b, int log_row, const double** x0_of_launch) {
+    Estimator& s = b->est;
+    const size_t total = (size_t)b->batch * b->nx;
+    if (!s.xhat) HIP_TRY(b, hipMalloc(&s.xhat, total * sizeof(double)));
+    double* const log = (s.log && log_row < s.log_rows) ? s.log + (size_t)log_row * total : nullptr;
+    hipLaunchKernelGGL(coverage_correction_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.xhat, log, *x0_of_launch, s.xp, s.src, s.kind == 2 ? 1 : 0,
+                       b->batch, b->nx);
+    HIP_TRY(b, hipGetLastError());
+    *x0_of_launch = s.xhat;
+    return TINY_OK;
+}
+// ... and its prediction behind the launch: xp <- the MODEL's step from xhat and the u0 of the x|u record, the chain of
+// coverage_plant_step_kernel.  xhat and xp are arrays of their own: a thread may write its xp while others still read xhat.  An instance
+// whose launch ran no iteration keeps its xp
+static __global__ __launch_bounds__(256) void coverage_prediction_kernel(double* __restrict__ xp, const double* __restrict__ xhat, const double* __restrict__ prim,
+                                                                         const int4* __restrict__ status, const double* __restrict__ A_m, const double* __restrict__ B_m,
+                                                                         const double* __restrict__ f_m, int per_instance, int batch, int nx, int nu, int N) {
+    const size_t total = (size_t)batch * nx;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int j = (int)(e % nx);
+        const size_t bb = e / nx, p = per_instance ? bb : 0;
+        if (status[bb].x <= 0) continue;
+        const double *A = A_m + p * nx * nx, *B = B_m + p * nx * nu, *u0 = prim + bb * N * (nx + nu) + nx;
+        double acc = f_m ? f_m[p * nx + j] : 0.0;
+        for (int k = 0; k < nx; ++k) acc = fma(xhat[bb * nx + k], A[j + nx * k], acc);
+        for (int k = 0; k < nu; ++k) acc = fma(u0[k], B[j + nx * k], acc);
+        xp[e] = acc;
+    }
+}
+int enqueue_coverage_prediction(TinyBatch* b) {
+    Estimator& s = b->est;
+    if (int rc = ensure_model_source(b, true)) return rc;
+    const PlantSource p = model_source(b);
+    const size_t total = (size_t)b->batch * b->nx;
+    hipLaunchKernelGGL(coverage_prediction_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.xp, s.xhat, b->d_prim, b->d_status, p.src[0], p.src[1], p.src[2],
+                       p.per_instance ? 1 : 0, b->batch, b->nx, b->nu, b->N);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
 
 // ---- what a launch and tiny_batch_update_settings call (batch_dispatch.hpp)
 int ensure_instance_data(TinyBatch* b) {
@@ -472,6 +581,8 @@ void note_instance_data_read(TinyBatch* b) {
     b->plant.log_rows = 0;                            // (the state log is the LAST solve call's: a launch that logs sizes it anew)
     b->meas.last = measurement_active(b);             // (the one-row kernel's PM forms, or the helper kernel in front of the coverage kernel)
     b->plant.last = plant_active(b);                  // (likewise: the one-row kernel's PP forms, or the helper kernel behind the coverage kernel)
+    b->est.last = estimator_active(b);                // (likewise: the one-row kernel's PE forms, or the helper kernels around the coverage kernel)
+    b->est.log_rows = 0;                              // (the estimate log is the LAST solve call's, as the state log)
 }
 void instance_data_settings_changed(TinyBatch* b) {
     if (b->ibox.on) b->ibox.dirty = true;             // (a disabled family is (-inf, +inf) in the array the kernels read)
@@ -624,6 +735,98 @@ int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps) {
     HIP_TRY(b, hipSetDevice(b->device));
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     if (x0_next) HIP_TRY(b, hipMemcpy(x0_next, b->plant.log, (size_t)steps * b->batch * b->nx * sizeof(double), hipMemcpyDeviceToHost));
+    return TINY_OK;
+}
+
+// a state estimator between the measurement and the solve: M [batch][nx*nx] column-major (TINY_BROADCAST: one), kept on the device as
+// given; the blocks the one-row kernel reads are built from it in front of the next launch (ensure_estimator_blocks).  Installing one
+// where none is installed starts the estimate record at the x0 record as it stands; replacing the gain keeps it.  Everything that can
+// fail happens before anything installed is touched
+int tiny_batch_set_estimator(TinyBatch* b, const double* M, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    Estimator& s = b->est;
+    if (!M) {                                                            // remove: freed once the stream has run dry of its readers
+        if (s.kind) { if (int rc = drop_buffers(b, s)) return rc; }
+        s.kind = 0; s.dirty = false; s.log_steps = 0; s.log_rows = 0;
+        return TINY_OK;
+    }
+    const size_t gains = (flags & TINY_BROADCAST) ? 1 : (size_t)b->batch, row = (size_t)b->batch * b->nx;
+    const UploadPart given = {M, gains * b->nx * b->nx};
+    double *fresh = nullptr, *xp = nullptr;
+    if (int rc = upload_fresh(b, &given, &fresh, 1, flags, "estimator gain")) return rc;
+    if (!s.kind) {                                                       // (the estimate starts at what x0 holds now)
+        hipError_t err = hipMalloc(&xp, row * sizeof(double));
+        if (err == hipSuccess) err = hipMemcpyAsync(xp, b->d_x0, row * sizeof(double), hipMemcpyDeviceToDevice, b->stream);
+        if (err == hipSuccess) err = hipStreamSynchronize(b->stream);
+        if (err != hipSuccess) {
+            (void)hipGetLastError();
+            if (xp) (void)hipFree(xp);
+            (void)hipFree(fresh);
+            return fail(b, TINY_ERR_HIP, "estimator: %s", hipGetErrorString(err));
+        }
+        s.xp = xp;
+    }
+    if (s.src) (void)hipFree(s.src);
+    if (s.built) (void)hipFree(s.built);                                 // (its size follows the kind; the estimate, the log and `xhat` stay)
+    s.src = fresh; s.built = nullptr;
+    s.kind = (flags & TINY_BROADCAST) ? 1 : 2;
+    s.dirty = true;
+    return TINY_OK;
+}
+// the gain instance `instance` is corrected by, as set: M_out [nx*nx]
+int tiny_batch_get_estimator(TinyBatch* b, int instance, double* M_out) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->est.kind) return fail(b, TINY_ERR_ARG, "no estimator installed");
+    if (!M_out) return fail(b, TINY_ERR_ARG, "null output");
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    return read_instance(b, M_out, b->est.src, b->est.kind == 2 ? instance : 0, (size_t)b->nx * b->nx);
+}
+// the predicted estimate: xp [batch][nx] (TINY_BROADCAST: one [nx] for all, expanded on the device).  The fresh record is complete
+// before it takes the place of the one installed
+int tiny_batch_set_estimate(TinyBatch* b, const double* xp, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->est.kind) return fail(b, TINY_ERR_ARG, "no estimator installed (tiny_batch_set_estimator)");
+    if (!xp) return fail(b, TINY_ERR_ARG, "null estimate");
+    HIP_TRY(b, hipSetDevice(b->device));
+    const size_t row = (size_t)b->batch * b->nx;
+    const UploadPart given = {xp, (flags & TINY_BROADCAST) ? (size_t)b->nx : row};
+    double* fresh = nullptr;
+    if (int rc = upload_fresh(b, &given, &fresh, 1, flags, "estimate")) return rc;
+    if (flags & TINY_BROADCAST) {
+        double* full = nullptr;
+        hipError_t err = hipMalloc(&full, row * sizeof(double));
+        int rc = TINY_OK;
+        if (err == hipSuccess) rc = expand_disturbance(b, full, fresh, 1);
+        if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);
+        (void)hipFree(fresh);
+        if (err != hipSuccess || rc != TINY_OK) {
+            (void)hipGetLastError();
+            if (full) (void)hipFree(full);
+            return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "estimate: %s", hipGetErrorString(err));
+        }
+        fresh = full;
+    }
+    if (b->est.xp) (void)hipFree(b->est.xp);
+    b->est.xp = fresh;
+    return TINY_OK;
+}
+int tiny_batch_get_estimate(TinyBatch* b, double* xp_out) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->est.kind) return fail(b, TINY_ERR_ARG, "no estimator installed (tiny_batch_set_estimator)");
+    if (!xp_out) return fail(b, TINY_ERR_ARG, "null output");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(xp_out, b->est.xp, (size_t)b->batch * b->nx * sizeof(double), hipMemcpyDeviceToHost));
+    return TINY_OK;
+}
+// the xhat every MPC step of the last solve call solved from (option "estimate_log"): xhat [steps][batch][nx]
+int tiny_batch_get_estimate_log(TinyBatch* b, double* xhat, int steps) {
+    if (!b) return TINY_ERR_NULL;
+    if (steps <= 0 || steps > b->est.log_rows || !b->est.log) return fail(b, TINY_ERR_ARG, "no estimate log recorded (set_option estimate_log; tiny_batch_set_estimator; advance_x0 or steps_per_launch)");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (xhat) HIP_TRY(b, hipMemcpy(xhat, b->est.log, (size_t)steps * b->batch * b->nx * sizeof(double), hipMemcpyDeviceToHost));
     return TINY_OK;
 }
 

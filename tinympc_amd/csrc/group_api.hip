@@ -382,6 +382,26 @@ int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, con
     }
     return TINY_OK;
 }
+// a state estimator (tiny_batch_set_estimator, tiny_batch_set_estimate): M [batch][nx*nx] / xp [batch][nx] over the full batch axis in
+// host memory, the caller's instance order; each shard gets its instances' rows (TINY_BROADCAST: the one, as it is); M == NULL removes
+static int group_set_rows(TinyGroup* g, const double* src, size_t per, int flags, int (*set)(TinyBatch*, const double*, int), const char* what) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "%s of a group: host arrays (TINY_HOST)", what);
+    const bool pass = !src || (flags & TINY_BROADCAST);
+    std::vector<double> stage;
+    for (int k = 0; k < g->n; ++k) {
+        const double* from = pass ? src : shard_slice(g, k, src, per, &stage);
+        const int rc = set(g->shard[k], from, pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
+int tiny_group_set_estimator(TinyGroup* g, const double* M, int flags) {
+    return group_set_rows(g, M, g ? (size_t)g->nx * g->nx : 0, flags, tiny_batch_set_estimator, "estimator");
+}
+int tiny_group_set_estimate(TinyGroup* g, const double* xp, int flags) {
+    return group_set_rows(g, xp, g ? (size_t)g->nx : 0, flags, tiny_batch_set_estimate, "estimate");
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

@@ -42,6 +42,7 @@ struct PathFacts {
     bool plant = false;                 // a plant of its own is installed AND the launch takes a plant step
     bool state_log = false;             // the state log is on AND the launch takes a plant step
     bool measurement = false;           // a measurement-noise sequence is installed AND the launch takes a plant step
+    bool estimator = false;             // a state estimator is installed AND the launch takes a plant step
 };
 
 // what path_facts can produce: the sweep of tests/dropin/kernel_path_driver.cpp counts these combinations only
@@ -61,7 +62,7 @@ enum KernelPath { ONE_ROW = 0, TILE = 1, COVERAGE = 2 };
 // (REFUSE_ADAPTIVE_INSTANCE_CONES came last and keeps the values of the others; it is REPORTED in front of the overlapping cones: decide_path)
 enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIVE_HALFSPACES, REFUSE_ADAPTIVE_OVERLAPPING_CONES, REFUSE_ADAPTIVE_NO_REGISTER_FORM,
                    REFUSE_ADAPTIVE_INSTANCE_CONES, REFUSE_ADAPTIVE_DISTURBANCE, REFUSE_ADAPTIVE_PLANT,
-                   REFUSE_ADAPTIVE_STATE_LOG, REFUSE_ADAPTIVE_MEASUREMENT };      // (the last four are the last ones reported, too, in this order)
+                   REFUSE_ADAPTIVE_STATE_LOG, REFUSE_ADAPTIVE_MEASUREMENT, REFUSE_ADAPTIVE_ESTIMATOR };      // (the last five are the last ones reported, too, in this order)
 constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
@@ -79,8 +80,9 @@ constexpr const char* PATH_REFUSAL_DISTURBANCE = "adaptive rho does not combine 
 constexpr const char* PATH_REFUSAL_PLANT = "adaptive rho does not combine with a plant of its own at the plant step (tiny_batch_set_plant)";
 constexpr const char* PATH_REFUSAL_STATE_LOG = "adaptive rho does not combine with the state log (option state_log)";
 constexpr const char* PATH_REFUSAL_MEASUREMENT = "adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)";
+constexpr const char* PATH_REFUSAL_ESTIMATOR = "adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)";
 inline const char* path_refusal_message(PathRefusal r) {
-    return r == REFUSE_ADAPTIVE_MEASUREMENT ? PATH_REFUSAL_MEASUREMENT : r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
+    return r == REFUSE_ADAPTIVE_ESTIMATOR ? PATH_REFUSAL_ESTIMATOR : r == REFUSE_ADAPTIVE_MEASUREMENT ? PATH_REFUSAL_MEASUREMENT : r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
 }
 
 struct PathDecision {
@@ -93,6 +95,7 @@ struct PathDecision {
     int pd = 0;                    // ONE_ROW: the per-instance disturbance form (of whatever form the fields above name)
     int pp = 0;                    // ONE_ROW: the form with a plant of its own (likewise; with or without pd)
     int pm = 0;                    // ONE_ROW: the form that solves from a measured state (likewise; always with pp)
+    int pe = 0;                    // ONE_ROW: the form with a state estimator in front of the solve (likewise; always with pm and pp)
 };
 
 // a one-row kernel exists for the shape: compiled in (counted even under no_jit), or one that run-time instantiation can make
@@ -114,9 +117,10 @@ inline PathDecision decide_path(const PathFacts& f) {
                                 : f.plant          ? REFUSE_ADAPTIVE_PLANT
                                 : f.state_log      ? REFUSE_ADAPTIVE_STATE_LOG
                                 : f.measurement    ? REFUSE_ADAPTIVE_MEASUREMENT
+                                : f.estimator      ? REFUSE_ADAPTIVE_ESTIMATOR
                                                    : REFUSE_NONE;
-    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0}; };
-    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0}; };
+    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0}; };
+    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0}; };
     // every instance its own disturbance at the plant step: ONE rule pair, applied to whatever one-row answer the rules below give --
     // the PD form of that very form (PB, PL and PC forms take the bit as well and keep their rule's name; every other one-row answer
     // is "one_row:pd"), run-time instantiated only, so where hipRTC may not be tried, with debug outputs, under force_general and with
@@ -126,13 +130,15 @@ inline PathDecision decide_path(const PathFacts& f) {
     // PP forms: with neither installed it rides on the PD form with an empty sequence, which adds nothing (rule names: pd's)
     // Measurement noise: the same rule pair once more, "one_row:pm" / "cover:pm" -- the PM form of that very form.  A PM form steps the
     // TRUE state through a plant block, so the fact forces pp on: with no plant installed the launch forms the block from the model
+    // A state estimator: the same rule pair, "one_row:pe" / "cover:pe" -- the PE form of that very form.  It corrects a MEASURED state
+    // and the true one is stepped apart from it, so the fact forces pm and pp on: with no noise sequence the launch binds an empty one
     const bool pd_form = f.fits && hiprtc && !f.force_general && !f.debug && !f.adaptive;
-    const bool pm = f.measurement, pp = f.plant || pm, pd = f.disturbance || (f.state_log && !pp);
+    const bool pe = f.estimator, pm = f.measurement || pe, pp = f.plant || pm, pd = f.disturbance || (f.state_log && !pp);
     auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) {
-        if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0};
-        if (!pd_form) return cover(pm ? "cover:pm" : pp ? "cover:pp" : "cover:pd");
-        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : pm ? "one_row:pm" : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0,
-                            pm ? 1 : 0};
+        if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0, 0};
+        if (!pd_form) return cover(pe ? "cover:pe" : pm ? "cover:pm" : pp ? "cover:pp" : "cover:pd");
+        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : pe ? "one_row:pe" : pm ? "one_row:pm" : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0,
+                            pm ? 1 : 0, pe ? 1 : 0};
     };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
@@ -147,7 +153,7 @@ inline PathDecision decide_path(const PathFacts& f) {
     // half-space / EXT forms and every form of a shape outside tile_dims.txt are run-time instantiated; EXT forms are for the shapes
     // the one-row kernel does not hold)
     const bool ext = f.tile_ext || f.hetero;
-    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log && !f.measurement &&
+    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log && !f.measurement && !f.estimator &&
                           !((f.tile_is_jit || f.soc || lf || ext) && (f.no_jit || f.tile_soc_failed)) && !(ext && regs);
 
     // ---- the rules, in order
@@ -184,7 +190,7 @@ inline PathDecision decide_path(const PathFacts& f) {
 }
 
 // tiny_batch_kernel_path: 0 the one-row kernel, compiled in; 1 the tile kernel; 2 the coverage kernel; 3 the one-row kernel, instantiated at
-// run time (every form with a per-instance box, half-space set, cone coefficients, disturbance, plant or measurement noise is); 4 the tile kernel, instantiated at run time
+// run time (every form with a per-instance box, half-space set, cone coefficients, disturbance, plant, measurement noise or state estimator is); 4 the tile kernel, instantiated at run time
 inline int kernel_path_code(const PathDecision& d, const PathFacts& f) {
     if (d.kernel == TILE) return f.tile_is_jit ? 4 : 1;
     if (d.kernel == COVERAGE) return 2;

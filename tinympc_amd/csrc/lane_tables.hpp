@@ -188,4 +188,12 @@ __host__ __device__ inline double plant_entry(const double* A_p, const double* B
     return f_p ? f_p[lane] : 0.0;
 }
 
+// ---- a state estimator's innovation gain (tiny_batch_set_estimator): what entry (column c, lane) of a gain block [nx columns][16 lanes]
+// holds (SolveArgs::est_gain).  State lane j keeps row j of M, column-major as the caller gave it; every other lane 0
+__host__ __device__ constexpr int gain_block_doubles(int nx) { return nx * 16; }
+__host__ __device__ inline double gain_entry(const double* M, int nx, int c, int lane) {
+    if (lane >= nx || c >= nx) return 0.0;
+    return M[lane + nx * c];
+}
+
 }  // namespace tinympc_amd

@@ -3,7 +3,7 @@
 the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
 by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
 (device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
-    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--package DIR] [--launches L] [--batch 65536]
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--estimator G [--estimator-shared 1]] [--package DIR] [--launches L] [--batch 65536]
 --workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
                     reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
 --workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
@@ -17,6 +17,9 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
                     run, the counter rewound per episode.  A = 0: an all-zero sequence -- fl(x + 0) = x, so a PM form solves exactly the
                     problems the PP form with the model as plant solves, and the times differ by what the PM form costs
                     (profiles/measurement_noise.md).  With --plant none the PM form steps by the model's own block
+--estimator G       a state estimator installed (tiny_batch_set_estimator): every instance its own gain G * I (--estimator-shared 1: one for all), the estimate put at x0 at the start
+                    of every episode.  With --noise 0 the innovation is zero at every step, so a PE form solves exactly the problems the PM
+                    form solves, and the times differ by what the PE form costs (profiles/estimator.md)
 Prints one JSON line: the median, minimum and maximum time in ms over the timed launches (episodes), the iterations accumulated and
 the read-backs that say which form ran.  profiles/plant.md is where the numbers go."""
 import argparse
@@ -39,6 +42,8 @@ def main():
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--state-log", type=int, default=0)
     ap.add_argument("--noise", type=float, default=None, help="measurement noise of this amplitude (0: an all-zero sequence)")
+    ap.add_argument("--estimator", type=float, default=None, help="a state estimator with the gain G * I per instance")
+    ap.add_argument("--estimator-shared", type=int, default=0, help="1: ONE gain for all (TINY_BROADCAST) instead of [batch] copies")
     a = ap.parse_args()
     sys.path.insert(0, a.package)
     import tinympc_amd as tm
@@ -109,11 +114,15 @@ def main():
         if a.noise is not None:
             rows = a.steps if a.steps > 1 else a.warmup + launches
             s.set_measurement_noise(a.noise * np.random.default_rng(7).uniform(-1.0, 1.0, (rows, B, nx)))
+        if a.estimator is not None:
+            s.set_estimator(a.estimator * np.eye(nx) if a.estimator_shared else np.ascontiguousarray(np.broadcast_to(a.estimator * np.eye(nx), (B, nx, nx))))
         if a.steps > 1:
             for e in range(2 + launches):                 # every episode is the same work; the first two settle the dispatch
                 start()
                 if a.noise is not None:
                     s.set_option("measurement_step", 0)
+                if a.estimator is not None:
+                    s.set_estimate(s.get("x0"))
                 s.set_option("timing", 1)
                 s.solve_async()
                 t = float(np.sum(s.timing_ms()))
@@ -121,6 +130,8 @@ def main():
                     ms.append(t)
         else:
             start()
+            if a.estimator is not None:
+                s.set_estimate(s.get("x0"))
             for _ in range(a.warmup):
                 s.solve_async()
             s.synchronize()
@@ -139,6 +150,8 @@ def main():
         out.update(plant_kind=int(s.get_option("plant")), last_plant=int(s.get_option("last_plant")))
     if a.noise is not None:
         out.update(noise=a.noise, measurement_noise=int(s.get_option("measurement_noise")), last_measurement_noise=int(s.get_option("last_measurement_noise")))
+    if a.estimator is not None:
+        out.update(estimator_gain=a.estimator, estimator=int(s.get_option("estimator")), last_estimator=int(s.get_option("last_estimator")))
     print(json.dumps(out), flush=True)
     s.close()
 
