@@ -330,6 +330,44 @@ int tiny_batch_get_estimator(TinyBatch* b, int instance, double* M_out);        
 int tiny_batch_set_estimate(TinyBatch* b, const double* xp, int flags);            /* [batch][nx]; HOST | DEVICE | BROADCAST ([nx]); TINY_ERR_ARG with no estimator */
 int tiny_batch_get_estimate(TinyBatch* b, double* xp_out);                         /* [batch][nx], host */
 int tiny_batch_get_estimate_log(TinyBatch* b, double* xhat, int steps);            /* option "estimate_log" = 1: [steps][batch][nx], the xhat every MPC step solved from */
+/* a per-instance score of a closed loop (advance_x0, steps_per_launch > 1): what the realised trajectory cost and whether the true
+ * state and the applied control left their limits, accumulated on the device -- a study reads four numbers per instance instead of
+ * pulling the state log and the step log to the host.
+ * All four arrays run over z = [x | u], nx + nu entries, states first: weight, target, lo, hi.  Each [batch][nx+nu], or with
+ * TINY_BROADCAST one [nx+nu] for all; TINY_HOST | TINY_DEVICE; copied, the caller may free.  target == NULL means zeros, lo == NULL /
+ * hi == NULL mean -inf / +inf.  weight == NULL removes the score and frees it.  A failed call leaves what was installed.
+ * Meaning: while a score is installed, once per MPC step of a launch that takes a plant step, for instance i: xn is the state the
+ * plant step handed on -- exactly what the state log records: by the plant installed or the model, plus the disturbance row, the TRUE
+ * state under measurement noise or a state estimator --, u0 the applied control, what the step log records, z = [xn | u0].
+ *   Cost: for c = 0 .. nx+nu-1 ascending: d = fl(z[c] - target[c]); s = fl(fl(weight[c] * d) * d); cost = fl(cost + s) -- three separate
+ *     IEEE roundings per term, nothing fused; ONE running sum in this order on every kernel path, whatever dpp_mode says.
+ *   Violation: e[c] = max(fl(z[c] - hi[c]), fl(lo[c] - z[c]), 0); m = max over c of e[c]; worst = max(worst, m); where m > 0:
+ *     violated_steps += 1 and, if first_violation < 0, first_violation = k.
+ *   Counter: k is a score step counter with the disturbance counter's rules: the setter and tiny_batch_reset_score rewind it, every MPC
+ *     step of a launch with a plant step advances it (inside the stretches of "step_regroup" too), option "score_step" moves it.
+ *   A zeroed record is cost = 0, worst = 0, violated_steps = 0, first_violation = -1.  Installing or replacing a score zeroes the
+ *     record and rewinds the counter; tiny_batch_reset_score does the same and keeps the setup; tiny_batch_reset leaves setup, record
+ *     and counter alone, as it does for the disturbance.
+ *   The record is indexed by instance and accumulates over launches: 2 + 3 steps equal 5, bit for bit, whatever the launch form.
+ *   A step that ran no iteration (max_iter = 0) takes no plant step and is not scored; the counter still advances.
+ *   A launch without a plant step reads nothing, leaves record and counter alone and runs the form it runs without a score.
+ *   Only the record moves: every other output of the solve keeps the bits it has without a score.
+ *   Non-finite z: the record's values are unspecified.
+ * Read-backs (tiny_batch_get_option): "score" 0 none, 1 one setup for all, 2 per instance; "score_step" the counter; "last_score" 1 when
+ * the last solve's launches scored.
+ * Where it runs: the one-row kernel's PS forms (run-time instantiated; every form the PD / PP / PM / PE forms exist for; with nothing
+ * else installed the PD form with an empty sequence); everywhere else (tile-kernel shapes, overlapping cones, "debug", "force_general",
+ * "no_jit", a missing hipRTC) one helper kernel behind the plant step of each single-step launch of the coverage kernel, same bits.
+ * Adaptive rho on such a launch fails the solve with TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with a closed-loop score
+ * (tiny_batch_set_score)").
+ * Out of scope: a moving target (the reference window); cone and half-space violations; sums over the batch on the device; the tile
+ * kernel; the half-row and PREFETCH forms; tiny_codegen; tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_score(TinyBatch* b, const double* weight, const double* target, const double* lo, const double* hi, int flags);
+/* the setup instance `instance` is scored by: [nx+nu] each, any may be NULL; TINY_ERR_ARG with none installed */
+int tiny_batch_get_score_setup(TinyBatch* b, int instance, double* weight, double* target, double* lo, double* hi);
+/* the record: [batch] each, host, any may be NULL; TINY_ERR_ARG with none installed */
+int tiny_batch_get_score(TinyBatch* b, double* cost, double* worst, int* violated_steps, int* first_violation);
+int tiny_batch_reset_score(TinyBatch* b);                                          /* zeroes the record, rewinds the counter, keeps the setup */
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -620,6 +658,10 @@ int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps,
  * and the estimate are read shard by shard (tiny_group_shard) */
 int tiny_group_set_estimator(TinyGroup* g, const double* M, int flags);
 int tiny_group_set_estimate(TinyGroup* g, const double* xp, int flags);
+/* a closed-loop score (tiny_batch_set_score): host, [batch][nx+nu] each over the full batch axis in the caller's order, or with
+ * TINY_BROADCAST one; weight == NULL removes.  tiny_group_set_option forwards "score_step"; the record is read shard by shard
+ * (tiny_group_shard) */
+int tiny_group_set_score(TinyGroup* g, const double* weight, const double* target, const double* lo, const double* hi, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

@@ -44,6 +44,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_disturbance", "tiny_batch_get_disturbance", "tiny_batch_set_plant", "tiny_batch_get_plant", "tiny_batch_get_state_log",
     "tiny_batch_set_measurement_noise", "tiny_batch_get_measurement_noise",
     "tiny_batch_set_estimator", "tiny_batch_get_estimator", "tiny_batch_set_estimate", "tiny_batch_get_estimate", "tiny_batch_get_estimate_log",
+    "tiny_batch_set_score", "tiny_batch_get_score_setup", "tiny_batch_get_score", "tiny_batch_reset_score",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -56,7 +57,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -189,6 +190,10 @@ def lib():
         L.tiny_batch_set_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.tiny_batch_get_estimate.argtypes = [C.c_void_p, _dp]
         L.tiny_batch_get_estimate_log.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.tiny_batch_set_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_score_setup.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+        L.tiny_batch_get_score.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.tiny_batch_reset_score.argtypes = [C.c_void_p]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -261,6 +266,7 @@ def lib():
         L.tiny_group_set_measurement_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_set_estimator.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_estimate.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.tiny_group_set_score.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int]
         L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -610,6 +616,58 @@ class TinyBatchSolver:
         out = np.zeros((steps, self.batch, self.nx))
         self._check(lib().tiny_batch_get_estimate_log(self._h, out.ctypes.data_as(_dp), int(steps)), "get_estimate_log")
         return out
+
+    def _score(self, weight, target, lo, hi):
+        """four arrays over z = [x | u], (batch, nx+nu) | (nx+nu,) each (target, lo, hi may be None) -> (flat arrays or None, broadcast flag)"""
+        nz = self.nx + self.nu
+        w = _f64(weight)
+        if w.shape not in ((self.batch, nz), (nz,)):
+            raise ValueError(f"score: weight ({self.batch}, {nz}) or ({nz},), got {w.shape}")
+        out = [w.ravel()]
+        for name, a in (("target", target), ("lo", lo), ("hi", hi)):
+            if a is None:
+                out.append(None)
+                continue
+            v = _f64(a)
+            if v.shape != w.shape:
+                raise ValueError(f"score: {name} {w.shape} like weight, got {v.shape}")
+            out.append(v.ravel())
+        return out, (BROADCAST if w.ndim == 1 else 0)
+
+    def set_score(self, weight, target=None, lo=None, hi=None):
+        """a per-instance score of a closed loop (advance_x0, steps_per_launch > 1), accumulated on the device at every plant step: over
+        z = [xn | u0] (the state handed on, what state_log records, and the applied control) cost += (weight * (z - target)) * (z - target)
+        term by term in ascending order, and the largest violation of lo <= z <= hi with the steps that violated and the first of them.
+        Each array (batch, nx+nu), or (nx+nu,) for one setup for all; target None: zeros, lo / hi None: no limit; weight None removes
+        it.  Installing or replacing zeroes the record and rewinds the counter (option "score_step")"""
+        if weight is None:
+            return self._check(lib().tiny_batch_set_score(self._h, None, None, None, None, HOST), "set_score")
+        a, bc = self._score(weight, target, lo, hi)
+        p = [None if v is None else v.ctypes.data_as(C.c_void_p) for v in a]
+        self._check(lib().tiny_batch_set_score(self._h, p[0], p[1], p[2], p[3], HOST | bc), "set_score")
+
+    def set_score_device(self, weight, target=None, lo=None, hi=None, broadcast=False):
+        """the same from device pointers (int; None where an array is left out) to [batch][nx+nu] doubles (one row with broadcast) resident in HBM (copied)"""
+        p = [None if v is None else C.c_void_p(int(v)) for v in (weight, target, lo, hi)]
+        self._check(lib().tiny_batch_set_score(self._h, p[0], p[1], p[2], p[3], DEVICE | (BROADCAST if broadcast else 0)), "set_score_device")
+
+    def get_score_setup(self, i):
+        """(weight, target, lo, hi), (nx+nu,) each: what instance i is scored by, as installed"""
+        out = [np.zeros(self.nx + self.nu) for _ in range(4)]
+        self._check(lib().tiny_batch_get_score_setup(self._h, int(i), *[v.ctypes.data_as(_dp) for v in out]), "get_score_setup")
+        return tuple(out)
+
+    def get_score(self):
+        """(cost, worst, violated_steps, first_violation), (batch,) each: the record as it stands"""
+        cost, worst = np.zeros(self.batch), np.zeros(self.batch)
+        steps, first = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32)
+        self._check(lib().tiny_batch_get_score(self._h, cost.ctypes.data_as(_dp), worst.ctypes.data_as(_dp), steps.ctypes.data_as(C.POINTER(C.c_int)),
+                                               first.ctypes.data_as(C.POINTER(C.c_int))), "get_score")
+        return cost, worst, steps, first
+
+    def reset_score(self):
+        """zeroes the record and rewinds the counter; the setup stays"""
+        self._check(lib().tiny_batch_reset_score(self._h), "reset_score")
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
         """Half-spaces a_k' z <= b_k (tiny_set_linear_constraints): Alin_x (n_s, nx), blin_x (n_s,), Alin_u (n_i, nu)."""
@@ -1078,6 +1136,40 @@ class TinyGroupSolver:
         if rc != OK:
             raise TinyMPCError(f"get_estimator failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
         return out.reshape(self.nx, self.nx).T.copy()
+
+    def set_score(self, weight, target=None, lo=None, hi=None):
+        """a closed-loop score for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if weight is None:
+            return self._check(lib().tiny_group_set_score(self._h, None, None, None, None, HOST), "set_score")
+        a, bc = TinyBatchSolver._score(self, weight, target, lo, hi)
+        p = [None if v is None else v.ctypes.data_as(_dp) for v in a]
+        self._check(lib().tiny_group_set_score(self._h, p[0], p[1], p[2], p[3], HOST | bc), "set_score")
+
+    def set_score_device(self, *args, **kwargs):
+        raise TinyMPCError("score of a group: host arrays (a device pointer belongs to one shard)")
+
+    def get_score(self):
+        """(cost, worst, violated_steps, first_violation), (batch,) each, gathered from the shards into the caller's order"""
+        cost, worst = np.zeros(self.batch), np.zeros(self.batch)
+        steps, first = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        for k in range(self.shards):
+            idx = self.shard_indices(k)
+            c, w = np.zeros(len(idx)), np.zeros(len(idx))
+            v, f = np.zeros(len(idx), dtype=np.int32), np.zeros(len(idx), dtype=np.int32)
+            h = lib().tiny_group_shard(self._h, k)
+            rc = lib().tiny_batch_get_score(h, c.ctypes.data_as(_dp), w.ctypes.data_as(_dp), v.ctypes.data_as(ip), f.ctypes.data_as(ip))
+            if rc != OK:
+                raise TinyMPCError(f"get_score failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
+            cost[idx], worst[idx], steps[idx], first[idx] = c, w, v, f
+        return cost, worst, steps, first
+
+    def reset_score(self):
+        for k in range(self.shards):
+            h = lib().tiny_group_shard(self._h, k)
+            rc = lib().tiny_batch_reset_score(h)
+            if rc != OK:
+                raise TinyMPCError(f"reset_score failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
 
     def _from_shards(self, steps, read, what):
         out = np.zeros((steps, self.batch, self.nx))

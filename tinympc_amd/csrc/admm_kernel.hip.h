@@ -96,6 +96,14 @@ static inline int tab_lin_offset(int N) { return ROW_TAB.lin_offset(N); }
 static inline int tab_tlin_offset(int N, int kmax = LIN_KMAX) { return ROW_TAB.tlin_offset(N, kmax); }
 static inline int tab_doubles(int N, int kmax = LIN_KMAX) { return ROW_TAB.doubles(N, kmax); }
 
+// what a closed-loop score (tiny_batch_set_score) keeps per instance: the running cost, the largest violation, the MPC steps that
+// violated a limit and the first of them (-1: none)
+struct ScoreRecord {
+    double cost, worst;
+    int violated_steps, first_violation;
+};
+static_assert(sizeof(ScoreRecord) == 24, "ScoreRecord: two doubles and two ints");
+
 struct SolveArgs {
     const double* tab;        // tab_doubles(N) doubles
     const double* x0;         // [batch][nx]
@@ -167,9 +175,22 @@ struct SolveArgs {
             const double* est_model;
         };
     };
-    double* aC2;
-    const double* atab;
-    double arho_min, arho_max;
+    // PS forms: a closed-loop score at the plant step -- score_tab [instances][weight | target | lo | hi][16 lanes] (score_entry of
+    // lane_tables.hpp; bit 0 of the pointer: one block for all, as at `plant`), score_rec [batch] the record (ScoreRecord), read and
+    // written once per scored MPC step by lane 0 of the row, score_step0 the score step counter at the launch's first MPC step.  Indexed
+    // by INSTANCE.  Only ADAPT forms read aC2, atab, arho_min and arho_max, and no PS form is one: the three lie over them
+    union {
+        struct {
+            double* aC2;
+            const double* atab;
+            double arho_min, arho_max;
+        };
+        struct {
+            const double* score_tab;
+            ScoreRecord* score_rec;
+            int score_step0;
+        };
+    };
     int aclip;
     // 1: every instance has the same Xref | Uref record (set with TINY_BROADCAST, or never set): all rows read instance 0's
     // record -- one L2-resident line set instead of 8S bytes of HBM per instance
@@ -253,6 +274,11 @@ static_assert(sizeof(SolveArgs) == 472 && __builtin_offsetof(SolveArgs, het_tabs
 static_assert(__builtin_offsetof(SolveArgs, arho) == 304 && __builtin_offsetof(SolveArgs, est_gain) == 304 && __builtin_offsetof(SolveArgs, est_xp) == 312 &&
               __builtin_offsetof(SolveArgs, est_log) == 320 && __builtin_offsetof(SolveArgs, est_model) == 328 && __builtin_offsetof(SolveArgs, aC1) == 328 &&
               __builtin_offsetof(SolveArgs, aC2) == 336 && __builtin_offsetof(SolveArgs, atab) == 344, "SolveArgs: the estimator's pointers share the adaptive-rho ones' place");
+
+// (the PS fields lie over aC2, atab and arho_min, which stay where they were, and so does everything behind them)
+static_assert(__builtin_offsetof(SolveArgs, aC2) == 336 && __builtin_offsetof(SolveArgs, score_tab) == 336 && __builtin_offsetof(SolveArgs, atab) == 344 &&
+              __builtin_offsetof(SolveArgs, score_rec) == 344 && __builtin_offsetof(SolveArgs, arho_min) == 352 && __builtin_offsetof(SolveArgs, score_step0) == 352 &&
+              __builtin_offsetof(SolveArgs, arho_max) == 360 && __builtin_offsetof(SolveArgs, aclip) == 368, "SolveArgs: the score's fields share the adaptive-rho tables' place");
 
 // ---- DPP row-broadcast FMA blocks ------------------------------------------------------------
 // One asm statement per block so that the two wait states a DPP read needs after a VALU write of
@@ -796,6 +822,13 @@ __device__ __forceinline__ T* late_arg(unsigned offset) {
     const char __attribute__((address_space(4)))* seg = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
     return *(T* const __attribute__((address_space(4)))*)(seg + offset);
 }
+// (... and a plain field of it, read the same way: the PS forms' step counter)
+template <class T>
+__device__ __forceinline__ T late_value(unsigned offset) {
+    asm volatile("" : "+s"(offset));
+    const char __attribute__((address_space(4)))* seg = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(const T __attribute__((address_space(4)))*)(seg + offset);
+}
 template <int COL0, int NCOL>
 __device__ __forceinline__ void plant_chain(double& acc, const double src, const double* m) {
     if constexpr (NCOL > 0) {
@@ -805,6 +838,45 @@ __device__ __forceinline__ void plant_chain(double& acc, const double src, const
         for (int k = 0; k < K; ++k) r[k] = m[k * 16];
         ring1<COL0, K>(acc, src, r);
         plant_chain<COL0 + K, NCOL - K>(acc, src, m + K * 16);
+    }
+}
+// the score of the PS forms, the lane-local part: the cost term s = fl(fl(w * d) * d), d = fl(z - target), and the violation
+// e = max(fl(z - hi), fl(lo - z), 0) of this lane's entry of z -- every operation ONE IEEE rounding, nothing contracted
+struct ScoreTerm { double s, e; };
+__device__ __forceinline__ ScoreTerm score_term(double z, const double w, const double target, const double lo, const double hi) {
+#pragma clang fp contract(off)
+    asm volatile("" : "+v"(z));
+    const double d = z - target;
+    const double wd = w * d;
+    ScoreTerm t;
+    t.s = wd * d;
+    t.e = fmax(fmax(z - hi, lo - z), 0.0);
+    return t;
+}
+// ... the row maximum of the violations, on every lane of the row: four rotations within the DPP row (row_ror 8, 4, 2, 1), no lane index
+// and no LDS crossbar -- the maximum is order-free
+template <int R>
+__device__ __forceinline__ double row_rotated(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, 0x120 + R, 0xf, 0xf, false);   // DPP_ROW_RR0 + R
+    hi = __builtin_amdgcn_update_dpp(0, hi, 0x120 + R, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double score_row_max(double v) {
+    v = fmax(v, row_rotated<8>(v));
+    v = fmax(v, row_rotated<4>(v));
+    v = fmax(v, row_rotated<2>(v));
+    return fmax(v, row_rotated<1>(v));
+}
+// ... and the running sum: cost = fl(cost + bcast(s, lane c)), c = COL0 .. COL0 + NCOL - 1, ONE chain in ascending order -- the DPP fmac
+// chain against ones (fma(s, 1, cost) is exactly fl(cost + s)), in blocks of four columns as plant_chain, whatever MODE says
+template <int COL0, int NCOL>
+__device__ __forceinline__ void score_chain(double& cost, const double s) {
+    if constexpr (NCOL > 0) {
+        constexpr int K = NCOL < 4 ? NCOL : 4;
+        const double one[4] = {1.0, 1.0, 1.0, 1.0};
+        ring1<COL0, K>(cost, s, one);
+        score_chain<COL0 + K, NCOL - K>(cost, s);
     }
 }
 
@@ -867,6 +939,15 @@ __device__ __forceinline__ void plant_chain(double& acc, const double src, const
 // iteration (max_iter = 0: then no step of the launch runs one) takes neither plant step nor prediction, and the next step's xp is the
 // record's.  PE implies PM and PP (a launch without a noise sequence binds an empty one); composes with everything PM composes with.
 // Run-time instantiated only; bit 8 of the sixth template argument (MODE | 256).
+// PS: a closed-loop score (SolveArgs::score_tab, score_rec, score_step0) at the plant step.  Where a PD / PP / PM form hands on a state
+// -- behind the iteration loop of every fused step, and at the x0_next store of the last one -- the row scores z = [xn | u0]: per lane
+// d = fl(z - target), s = fl(fl(w * d) * d), e = max(fl(z - hi), fl(lo - z), 0) (score_term: contraction off), the cost one DPP chain
+// against ones that starts at the record's cost and adds the row's s in ascending order (score_chain), the violation one row maximum;
+// lane 0 reads the record and writes it back.  The record is read and written per step, not carried: on the PM / PE box forms, which sit
+// at the register limit, six more registers through the iteration loop would be six more spills in it.  A step that ran no iteration
+// takes no plant step and is not scored.  Only the record moves.  PS rides on PD or PP (a launch with neither installed binds an
+// empty disturbance sequence, as the state log does); composes with everything they compose with.  Run-time instantiated only; bit 9
+// of the sixth template argument (MODE | 512).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -881,7 +962,12 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PP = (MODE_PB & 64) != 0;
     constexpr bool PM = (MODE_PB & 128) != 0;
     constexpr bool PE = (MODE_PB & 256) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 512, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator");
+    constexpr bool PS = (MODE_PB & 512) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 1024, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator, + 512: a closed-loop score");
+    static_assert(!PS || PD || PP, "a closed-loop score: a form that takes its plant step itself (PD, bit 5, or PP, bit 6)");
+    static_assert(!PS || !ADAPT, "a closed-loop score: not with adaptive rho (refused)");
+    static_assert(!PS || !HALF, "a closed-loop score: not the half-row form");
+    static_assert(!PS || !PF, "a closed-loop score: not the prefetch form");
     static_assert(!PE || (PM && PP), "a state estimator: a form that solves from a measured state (PM, bit 7) on a plant block (PP, bit 6)");
     static_assert(!PE || !ADAPT, "a state estimator: not with adaptive rho (refused)");
     static_assert(!PE || !HALF, "a state estimator: not the half-row form");
@@ -1498,6 +1584,34 @@ void admm_solve_kernel(const SolveArgs P) {
                 return is_state ? from[cell] : 0.0;
             };
             (void)true_cell; (void)true_x0;
+            // PS: the score of the MPC step `at_step` whose plant step handed on `xn_row` (state lanes) under the applied u0 (slot 1 of the
+            // input lanes): z = [xn | u0] across the row, the lane-local terms against the instance's setup block, the cost on ONE chain
+            // that starts at the record's and takes the row's terms in ascending order, the violation by a row maximum (score_row_max); lane 0 of the
+            // row reads and writes the record.  Called behind the iteration loop only, where a plant step was taken, and everything it
+            // needs is formed there: the pointers come from the kernel-argument segment, nothing lives through the loop
+            auto scored = [&](const double xn_row, const double u0_row, const int at_step) {
+                int s_b = b;
+                asm volatile("" : "+v"(s_b));
+                const unsigned long long raw = reinterpret_cast<unsigned long long>(late_arg<const double>(__builtin_offsetof(SolveArgs, score_tab)));
+                const double* st = reinterpret_cast<const double*>(raw & ~1ull) + ((raw & 1ull) ? (size_t)0 : (size_t)s_b * 64) + j;
+                const double z = is_state ? xn_row : (is_input ? u0_row : 0.0);
+                const ScoreTerm t = score_term(z, st[0], st[16], st[32], st[48]);
+                ScoreRecord* const rec = late_arg<ScoreRecord>(__builtin_offsetof(SolveArgs, score_rec)) + s_b;
+                double cost = j == 0 ? rec->cost : 0.0;
+                score_chain<0, NZ>(cost, t.s);
+                const double m = score_row_max(t.e);
+                if (j == 0) {
+                    rec->cost = cost;
+                    if (m > 0.0) {
+                        const double worst = rec->worst;
+                        const int first = rec->first_violation;
+                        rec->worst = fmax(worst, m);
+                        rec->violated_steps += 1;
+                        if (first < 0) rec->first_violation = late_value<int>(__builtin_offsetof(SolveArgs, score_step0)) + at_step;
+                    }
+                }
+            };
+            (void)scored;
             const int iter_first = resumed ? P.iter_base : 0;  // (a multiple of check_termination: the countdown restarts in phase)
             for (int step = 0; step < nsteps; ++step) {        // closed-loop MPC steps fused in one launch
                 X[0] = x0v;                                    // work->x.col(0) = x0
@@ -1999,6 +2113,7 @@ void admm_solve_kernel(const SolveArgs P) {
                                 if constexpr (PD) xt = disturbed(xt, step);
                             }
                             if (P.x0_next && is_state) P.x0_next[cell] = xt;      // (where true_x0 finds it; a step without a plant step: unchanged)
+                            if constexpr (PS) { if (iter > iter0) scored(xt, X[1], step); }
                             if (P.state_log && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = xt;
                             x0v = measured(xt, step + 1);
                             if constexpr (PE) x0v = corrected(x0v, est_next);
@@ -2012,6 +2127,9 @@ void admm_solve_kernel(const SolveArgs P) {
                     }
                     if constexpr (PD || PP) {
                         if (P.state_log && step + 1 < nsteps && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = x0v;
+                    }
+                    if constexpr (PS) {                        // (the score of a step that took its plant step: what it handed on, under the u0 it applied)
+                        if (step + 1 < nsteps && iter > iter0) scored(x0v, X[1], step);
                     }
                     }
                 }
@@ -2109,6 +2227,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);
                     if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
                     if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
+                    if constexpr (PS) scored(xn, X[1], nsteps - 1);
                 } else if (P.state_log && is_state) {
                     P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xt;
                 }
@@ -2120,6 +2239,7 @@ void admm_solve_kernel(const SolveArgs P) {
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);
                     if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
                     if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
+                    if constexpr (PS) scored(xn, X[1], nsteps - 1);
                 } else if (P.state_log && is_state) {        // (no plant step: the x0 the launch left in place)
                     P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = P.x0[(size_t)b * NX + j];
                 }

@@ -81,6 +81,15 @@ const double* model_kernel_pointer(const TinyBatch* b);
 int begin_estimate_log(TinyBatch* b, int rows);
 int enqueue_coverage_correction(TinyBatch* b, int log_row, const double** x0_of_launch);
 int enqueue_coverage_prediction(TinyBatch* b);
+// a closed-loop score: installed AND the next launch takes a plant step / the score step counter as the kernels take it / the setup
+// blocks of the PS forms, built where they are missing or out of date / the pointer a PS form reads (SolveArgs::score_tab: bit 0 says
+// "one block for all") / the coverage path's helper kernel behind one single-step launch and its plant step: the record of every
+// instance whose launch ran an iteration takes z = [x0 as handed on | u0] in, as score step `step`
+bool score_active(const TinyBatch* b);
+int score_step_base(const TinyBatch* b);
+int ensure_score_blocks(TinyBatch* b);
+const double* score_kernel_pointer(const TinyBatch* b);
+int enqueue_coverage_score(TinyBatch* b, long step);
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>
 void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }

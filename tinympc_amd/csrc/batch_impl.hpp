@@ -123,8 +123,22 @@ struct Estimator {
     int log_rows = 0;
     template <class F> void each_buffer(F f) { f(src); f(built); f(xp); f(xhat); f(log); }
 };
+// a closed-loop score at the plant step (tiny_batch_set_score).  src: the caller's weight | target | lo | hi, kept on the device as given
+// ([batch][nx+nu] each, or ONE with kind 1; target, lo and hi may be null) -- what the getter and the coverage path's helper kernel read;
+// built: the blocks the one-row kernel's PS forms read (score_entry of lane_tables.hpp: [batch or 1][4][16]), made in front of the next
+// launch; rec [batch]: the record (ScoreRecord of admm_kernel.hip.h: cost, worst, violated_steps, first_violation), STATE of the batch:
+// it accumulates over launches until the setter or tiny_batch_reset_score zeroes it.  step: the score step counter (the setter and the
+// reset rewind it, option "score_step" moves it, every MPC step of a launch that takes a plant step advances it)
+struct Score {
+    int kind = 0;                                  // 0 none, 1 one setup for all, 2 every instance its own
+    bool dirty = false, last = false;              // (... scored: installed and a plant step taken)
+    double *src[4] = {nullptr, nullptr, nullptr, nullptr}, *built = nullptr;
+    void* rec = nullptr;
+    long step = 0;
+    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(rec); }
+};
 
-constexpr size_t KPI_SKEW_BYTES = 0;            // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
+constexpr size_t KPI_SKEW_BYTES = 0;           // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
     int nx = 0, nu = 0, N = 0, batch = 0, device = 0, num_cus = 256;
     const tinympc_amd::KernelEntry* kernel = nullptr;
@@ -212,7 +226,7 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

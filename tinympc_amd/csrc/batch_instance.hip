@@ -1,5 +1,5 @@
 // batch_instance.hip -- every instance its own problem data: a box, static and time-varying half-spaces, cone coefficients, a
-// disturbance sequence, a plant model with its state log, a measurement-noise sequence (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance, PlantStep, MeasurementNoise of batch_impl.hpp).  Per family: the C ABI setter and
+// disturbance sequence, a plant model with its state log, a measurement-noise sequence, a state estimator, a closed-loop score (InstanceBox, InstanceHalfspaces, InstanceCones, Disturbance, PlantStep, MeasurementNoise, Estimator, Score of batch_impl.hpp).  Per family: the C ABI setter and
 // getter, the drop the shared setters of batch_api.hip call, the fill kernel that turns the caller's arrays into what the solve kernels
 // read (fill rules: lane_tables.hpp) and the ensure_instance_* that runs it when a setter or an enable switch has left the block out of date.
 // The sequences the families share -- upload, drop, read one instance back -- stand once, at the top.  Declarations: batch_dispatch.hpp.
@@ -567,6 +567,85 @@ int enqueue_coverage_prediction(TinyBatch* b) {
     return TINY_OK;
 }
 
+// ---- a closed-loop score at the plant step (tiny_batch_set_score): the caller's weight | target | lo | hi -> [setups][4][16 lanes], one
+// thread per (setup, row, lane); what lands there: score_entry (lane_tables.hpp), nothing else.  One setup for all: one block
+static __global__ __launch_bounds__(256) void fill_score_kernel(double* __restrict__ out, const double* __restrict__ weight, const double* __restrict__ target,
+                                                                const double* __restrict__ lo, const double* __restrict__ hi, int setups, int nx, int nu) {
+    const size_t total = (size_t)setups * score_block_doubles();
+    const int nz = nx + nu;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % 16), r = (int)((e / 16) % 4);
+        const size_t g = e / score_block_doubles();
+        out[e] = score_entry(weight + g * nz, target ? target + g * nz : nullptr, lo ? lo + g * nz : nullptr, hi ? hi + g * nz : nullptr, nx, nu, r, lane);
+    }
+}
+// a zeroed record: cost 0, worst 0, violated_steps 0, first_violation -1
+static __global__ __launch_bounds__(256) void zero_score_kernel(ScoreRecord* __restrict__ rec, int batch) {
+    for (int bb = blockIdx.x * blockDim.x + threadIdx.x; bb < batch; bb += gridDim.x * blockDim.x) rec[bb] = ScoreRecord{0.0, 0.0, 0, -1};
+}
+static int enqueue_zero_score(TinyBatch* b, void* rec) {
+    hipLaunchKernelGGL(zero_score_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, static_cast<ScoreRecord*>(rec), b->batch);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
+bool score_active(const TinyBatch* b) { return b->score.kind != 0 && (b->advance_x0 || b->steps_per_launch > 1); }
+int score_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->score.step, -(1L << 30), 1L << 30); }
+const double* score_kernel_pointer(const TinyBatch* b) {
+    return reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(b->score.built) | (b->score.kind == 2 ? (uintptr_t)0 : (uintptr_t)1));
+}
+// (only the one-row kernel's PS forms read the blocks; the coverage path reads the caller's arrays)
+int ensure_score_blocks(TinyBatch* b) {
+    Score& s = b->score;
+    if (!s.kind || !s.dirty) return TINY_OK;
+    const int setups = s.kind == 1 ? 1 : b->batch;
+    const size_t total = (size_t)setups * score_block_doubles();
+    if (!s.built) HIP_TRY(b, hipMalloc(&s.built, total * sizeof(double)));
+    hipLaunchKernelGGL(fill_score_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.built, s.src[0], s.src[1], s.src[2], s.src[3], setups, b->nx, b->nu);
+    HIP_TRY(b, hipGetLastError());
+    s.dirty = false;
+    return TINY_OK;
+}
+// the coverage path's score behind one single-step launch and its plant step: one thread per instance, the arithmetic of
+// tiny_batch_set_score in its stated order over z = [x0 as handed on | the u0 of the x|u record] -- what score_term, score_chain and the
+// row maximum do on the one-row kernel, same bits.  An instance whose launch ran no iteration took no plant step and is not scored
+static __global__ __launch_bounds__(256) void coverage_score_kernel(ScoreRecord* __restrict__ rec, const double* __restrict__ x0, const double* __restrict__ prim,
+                                                                    const int4* __restrict__ status, const double* __restrict__ weight, const double* __restrict__ target,
+                                                                    const double* __restrict__ lo, const double* __restrict__ hi, int per_instance, int step, int batch,
+                                                                    int nx, int nu, int N) {
+#pragma clang fp contract(off)
+    const int nz = nx + nu;
+    for (int bb = blockIdx.x * blockDim.x + threadIdx.x; bb < batch; bb += gridDim.x * blockDim.x) {
+        if (status[bb].x <= 0) continue;
+        const size_t p = per_instance ? (size_t)bb * nz : 0;
+        const double *xn = x0 + (size_t)bb * nx, *u0 = prim + (size_t)bb * N * nz + nx;
+        ScoreRecord r = rec[bb];
+        double m = 0.0;
+        for (int c = 0; c < nz; ++c) {
+            const double z = c < nx ? xn[c] : u0[c - nx];
+            const double d = z - (target ? target[p + c] : 0.0);
+            const double wd = weight[p + c] * d;
+            const double s = wd * d;
+            r.cost = r.cost + s;
+            const double over = hi ? z - hi[p + c] : -__builtin_huge_val(), under = lo ? lo[p + c] - z : -__builtin_huge_val();
+            m = fmax(m, fmax(over, under));
+        }
+        if (m > 0.0) {
+            r.worst = fmax(r.worst, m);
+            r.violated_steps += 1;
+            if (r.first_violation < 0) r.first_violation = step;
+        }
+        rec[bb] = r;
+    }
+}
+int enqueue_coverage_score(TinyBatch* b, long step) {
+    Score& s = b->score;
+    const int k = (int)std::clamp<long>(step, -(1L << 30), 1L << 30);
+    hipLaunchKernelGGL(coverage_score_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, static_cast<ScoreRecord*>(s.rec), b->d_x0, b->d_prim, b->d_status,
+                       s.src[0], s.src[1], s.src[2], s.src[3], s.kind == 2 ? 1 : 0, k, b->batch, b->nx, b->nu, b->N);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
+
 // ---- what a launch and tiny_batch_update_settings call (batch_dispatch.hpp)
 int ensure_instance_data(TinyBatch* b) {
     if (int rc = ensure_instance_bounds(b)) return rc;   // (first: a rebuilt box may change the UB decision, it sets tab_dirty)
@@ -583,6 +662,7 @@ void note_instance_data_read(TinyBatch* b) {
     b->plant.last = plant_active(b);                  // (likewise: the one-row kernel's PP forms, or the helper kernel behind the coverage kernel)
     b->est.last = estimator_active(b);                // (likewise: the one-row kernel's PE forms, or the helper kernels around the coverage kernel)
     b->est.log_rows = 0;                              // (the estimate log is the LAST solve call's, as the state log)
+    b->score.last = score_active(b);                  // (likewise: the one-row kernel's PS forms, or the helper kernel behind the coverage kernel)
 }
 void instance_data_settings_changed(TinyBatch* b) {
     if (b->ibox.on) b->ibox.dirty = true;             // (a disabled family is (-inf, +inf) in the array the kernels read)
@@ -828,6 +908,75 @@ int tiny_batch_get_estimate_log(TinyBatch* b, double* xhat, int steps) {
     HIP_TRY(b, hipStreamSynchronize(b->stream));
     if (xhat) HIP_TRY(b, hipMemcpy(xhat, b->est.log, (size_t)steps * b->batch * b->nx * sizeof(double), hipMemcpyDeviceToHost));
     return TINY_OK;
+}
+
+// a closed-loop score at the plant step: weight | target | lo | hi [batch][nx+nu] (TINY_BROADCAST: one [nx+nu] each), kept on the device
+// as given; the blocks the one-row kernel reads are built from them in front of the next launch (ensure_score_blocks).  Installing or
+// replacing zeroes the record and rewinds the counter.  Everything that can fail happens before anything installed is touched
+int tiny_batch_set_score(TinyBatch* b, const double* weight, const double* target, const double* lo, const double* hi, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    Score& s = b->score;
+    if (flags & ~(TINY_DEVICE | TINY_BROADCAST)) return fail(b, TINY_ERR_ARG, "score: flags 0x%x (TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST)", flags);
+    if (!weight) {                                                       // remove: freed once the stream has run dry of its readers
+        if (s.kind) { if (int rc = drop_buffers(b, s)) return rc; }
+        s.kind = 0; s.dirty = false; s.step = 0;
+        return TINY_OK;
+    }
+    const size_t nz = (size_t)b->nx + b->nu, doubles = ((flags & TINY_BROADCAST) ? 1 : (size_t)b->batch) * nz;
+    const UploadPart given[4] = {{weight, doubles}, {target, doubles}, {lo, doubles}, {hi, doubles}};
+    double* fresh[4];
+    void* rec = s.rec;
+    if (!rec) {
+        if (hipMalloc(&rec, (size_t)b->batch * sizeof(ScoreRecord)) != hipSuccess) { (void)hipGetLastError(); return fail(b, TINY_ERR_HIP, "score record: out of device memory"); }
+    }
+    if (int rc = upload_fresh(b, given, fresh, 4, flags, "score setup")) { if (!s.rec) (void)hipFree(rec); return rc; }
+    for (int i = 0; i < 4; ++i) { if (s.src[i]) (void)hipFree(s.src[i]); s.src[i] = fresh[i]; }
+    if (s.built) (void)hipFree(s.built);                                 // (its size follows the kind)
+    s.built = nullptr; s.rec = rec;
+    s.kind = (flags & TINY_BROADCAST) ? 1 : 2;
+    s.dirty = true; s.step = 0;
+    return enqueue_zero_score(b, s.rec);
+}
+// the setup instance `instance` is scored by, as set (a null target reads as zeros, null limits as -inf / +inf); any output may be null
+int tiny_batch_get_score_setup(TinyBatch* b, int instance, double* weight, double* target, double* lo, double* hi) {
+    if (!b) return TINY_ERR_NULL;
+    const Score& s = b->score;
+    if (!s.kind) return fail(b, TINY_ERR_ARG, "no score installed");
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    const size_t nz = (size_t)b->nx + b->nu;
+    double* const out[4] = {weight, target, lo, hi};
+    const double none[4] = {0.0, 0.0, -std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity()};
+    for (int i = 0; i < 4; ++i) {
+        if (!out[i]) continue;
+        if (!s.src[i]) { std::fill(out[i], out[i] + nz, none[i]); continue; }
+        if (int rc = read_instance(b, out[i], s.src[i], s.kind == 2 ? instance : 0, nz)) return rc;
+    }
+    return TINY_OK;
+}
+// the record: cost, worst [batch] doubles, violated_steps, first_violation [batch] ints, on the host; any may be null
+int tiny_batch_get_score(TinyBatch* b, double* cost, double* worst, int* violated_steps, int* first_violation) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->score.kind) return fail(b, TINY_ERR_ARG, "no score installed (tiny_batch_set_score)");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    std::vector<ScoreRecord> h((size_t)b->batch);
+    HIP_TRY(b, hipMemcpy(h.data(), b->score.rec, h.size() * sizeof(ScoreRecord), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) {
+        if (cost) cost[i] = h[i].cost;
+        if (worst) worst[i] = h[i].worst;
+        if (violated_steps) violated_steps[i] = h[i].violated_steps;
+        if (first_violation) first_violation[i] = h[i].first_violation;
+    }
+    return TINY_OK;
+}
+// the record zeroed and the counter rewound; the setup stays
+int tiny_batch_reset_score(TinyBatch* b) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->score.kind) return fail(b, TINY_ERR_ARG, "no score installed (tiny_batch_set_score)");
+    HIP_TRY(b, hipSetDevice(b->device));
+    b->score.step = 0;
+    return enqueue_zero_score(b, b->score.rec);
 }
 
 // every instance its own half-spaces, set 0 (static) or 1 (time-varying).  The caller's arrays are kept on the device as given; what

@@ -402,6 +402,23 @@ int tiny_group_set_estimator(TinyGroup* g, const double* M, int flags) {
 int tiny_group_set_estimate(TinyGroup* g, const double* xp, int flags) {
     return group_set_rows(g, xp, g ? (size_t)g->nx : 0, flags, tiny_batch_set_estimate, "estimate");
 }
+// a closed-loop score (tiny_batch_set_score): weight | target | lo | hi [batch][nx+nu] over the full batch axis in host memory, the
+// caller's instance order; each shard gets its instances' rows (TINY_BROADCAST: the one setup, as it is); weight == NULL removes
+int tiny_group_set_score(TinyGroup* g, const double* weight, const double* target, const double* lo, const double* hi, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "score of a group: host arrays (TINY_HOST)");
+    const bool pass = !weight || (flags & TINY_BROADCAST);
+    const size_t nz = (size_t)g->nx + g->nu;
+    const double* src[4] = {weight, target, lo, hi};
+    std::vector<double> stage[4];
+    for (int k = 0; k < g->n; ++k) {
+        const double* from[4] = {weight, target, lo, hi};
+        if (!pass) for (int a = 0; a < 4; ++a) from[a] = shard_slice(g, k, src[a], nz, &stage[a]);
+        const int rc = tiny_batch_set_score(g->shard[k], from[0], from[1], from[2], from[3], pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

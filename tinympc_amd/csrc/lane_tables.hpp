@@ -196,4 +196,16 @@ __host__ __device__ inline double gain_entry(const double* M, int nx, int c, int
     return M[lane + nx * c];
 }
 
+// ---- a closed-loop score's setup (tiny_batch_set_score): what entry (row r, lane) of a score block [weight | target | lo | hi][16 lanes]
+// holds (SolveArgs::score_tab).  Lane c < nx + nu keeps entry c of z = [x | u] of the caller's four arrays; a null target is 0, a null lo
+// -inf, a null hi +inf, and so is every lane outside the row (weight 0 there): such a lane adds a zero and violates nothing
+__host__ __device__ constexpr int score_block_doubles() { return 4 * 16; }
+__host__ __device__ inline double score_entry(const double* weight, const double* target, const double* lo, const double* hi, int nx, int nu, int r, int lane) {
+    const bool in = lane < nx + nu;
+    if (r == 0) return in ? weight[lane] : 0.0;
+    if (r == 1) return (in && target) ? target[lane] : 0.0;
+    if (r == 2) return (in && lo) ? lo[lane] : -__builtin_huge_val();
+    return (in && hi) ? hi[lane] : __builtin_huge_val();
+}
+
 }  // namespace tinympc_amd

@@ -3,7 +3,7 @@
 the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
 by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
 (device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
-    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--estimator G [--estimator-shared 1]] [--package DIR] [--launches L] [--batch 65536]
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--estimator G [--estimator-shared 1]] [--score device|host] [--package DIR] [--launches L] [--batch 65536]
 --workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
                     reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
 --workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
@@ -20,6 +20,13 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
 --estimator G       a state estimator installed (tiny_batch_set_estimator): every instance its own gain G * I (--estimator-shared 1: one for all), the estimate put at x0 at the start
                     of every episode.  With --noise 0 the innovation is zero at every step, so a PE form solves exactly the problems the PM
                     form solves, and the times differ by what the PE form costs (profiles/estimator.md)
+--score device      a closed-loop score installed (tiny_batch_set_score): every instance its own weights, the workload's reference as the target and
+                    limits at 0.8 of the workload's box, no log on; per episode the four arrays are read back (tiny_batch_get_score).  The
+                    launch time is what the PS form costs over the form without it; wall_ms is the episode with its read-back
+                    (profiles/score.md)
+--score host        what it took before: nothing installed, "state_log" and "step_log" on, both logs pulled to the host after the
+                    episode and scored there in numpy (the same arithmetic, vectorised over the instances); wall_ms is the episode with all
+                    of that.  Both need --steps > 1
 Prints one JSON line: the median, minimum and maximum time in ms over the timed launches (episodes), the iterations accumulated and
 the read-backs that say which form ran.  profiles/plant.md is where the numbers go."""
 import argparse
@@ -44,6 +51,7 @@ def main():
     ap.add_argument("--noise", type=float, default=None, help="measurement noise of this amplitude (0: an all-zero sequence)")
     ap.add_argument("--estimator", type=float, default=None, help="a state estimator with the gain G * I per instance")
     ap.add_argument("--estimator-shared", type=int, default=0, help="1: ONE gain for all (TINY_BROADCAST) instead of [batch] copies")
+    ap.add_argument("--score", choices=("device", "host"), default=None, help="a closed-loop score on the device, or both logs pulled and scored in numpy")
     a = ap.parse_args()
     sys.path.insert(0, a.package)
     import tinympc_amd as tm
@@ -116,9 +124,39 @@ def main():
             s.set_measurement_noise(a.noise * np.random.default_rng(7).uniform(-1.0, 1.0, (rows, B, nx)))
         if a.estimator is not None:
             s.set_estimator(a.estimator * np.eye(nx) if a.estimator_shared else np.ascontiguousarray(np.broadcast_to(a.estimator * np.eye(nx), (B, nx, nx))))
+        wall, scored = [], None
+        if a.score is not None:
+            lim = m if a.workload == "rocket" else h
+            target = np.concatenate([xg if a.workload == "rocket" else np.array(h["xref"], dtype=float).reshape(nx), np.zeros(nu)])
+            hi = 0.8 * np.concatenate([np.broadcast_to(np.asarray(lim["x_max"], dtype=float).ravel(), (nx,)), np.broadcast_to(np.asarray(lim["u_max"], dtype=float).ravel(), (nu,))])
+            lo = 0.8 * np.concatenate([np.broadcast_to(np.asarray(lim["x_min"], dtype=float).ravel(), (nx,)), np.broadcast_to(np.asarray(lim["u_min"], dtype=float).ravel(), (nu,))])
+            setup = (np.random.default_rng(11).uniform(0.5, 2.0, (B, nx + nu)),) + tuple(np.ascontiguousarray(np.broadcast_to(v, (B, nx + nu))) for v in (target, lo, hi))
+            if a.score == "device":
+                s.set_score(*setup)
+            else:
+                s.set_option("state_log", 1)
+                s.set_option("step_log", 1)
+
+        def host_score(states, u0):
+            w, tg, l, u = setup
+            cost, worst, count, first = np.zeros(B), np.zeros(B), np.zeros(B, dtype=np.int32), np.full(B, -1, dtype=np.int32)
+            for k in range(len(states)):
+                z = np.concatenate([states[k], u0[k]], axis=1)
+                for c in range(nx + nu):
+                    d = z[:, c] - tg[:, c]
+                    cost = cost + (w[:, c] * d) * d
+                e = np.maximum(np.max(np.maximum(z - u, l - z), axis=1), 0.0)
+                worst = np.maximum(worst, e)
+                first = np.where((e > 0.0) & (first < 0), k, first).astype(np.int32)
+                count += e > 0.0
+            return cost, worst, count, first
         if a.steps > 1:
             for e in range(2 + launches):                 # every episode is the same work; the first two settle the dispatch
                 start()
+                if a.score == "device":
+                    s.reset_score()
+                s.synchronize()
+                t0 = time.perf_counter()
                 if a.noise is not None:
                     s.set_option("measurement_step", 0)
                 if a.estimator is not None:
@@ -126,8 +164,13 @@ def main():
                 s.set_option("timing", 1)
                 s.solve_async()
                 t = float(np.sum(s.timing_ms()))
+                if a.score == "device":
+                    scored = s.get_score()
+                elif a.score == "host":
+                    scored = host_score(s.state_log(a.steps), s.step_log(a.steps)[1])
                 if e >= 2:
                     ms.append(t)
+                    wall.append(1e3 * (time.perf_counter() - t0))
         else:
             start()
             if a.estimator is not None:
@@ -152,6 +195,9 @@ def main():
         out.update(noise=a.noise, measurement_noise=int(s.get_option("measurement_noise")), last_measurement_noise=int(s.get_option("last_measurement_noise")))
     if a.estimator is not None:
         out.update(estimator_gain=a.estimator, estimator=int(s.get_option("estimator")), last_estimator=int(s.get_option("last_estimator")))
+    if a.score is not None and a.steps > 1:
+        out.update(score=a.score, score_kind=int(s.get_option("score")), last_score=int(s.get_option("last_score")), wall_median_ms=float(np.median(wall)), wall_min_ms=float(min(wall)),
+                   wall_max_ms=float(max(wall)), cost_median=float(np.median(scored[0])), violated_share=float(np.mean(scored[2] > 0)))
     print(json.dumps(out), flush=True)
     s.close()
 
