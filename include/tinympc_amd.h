@@ -84,6 +84,7 @@ typedef enum {
 #define TINY_HOST        0   /* pointer is host memory, [batch] matrices back to back          */
 #define TINY_DEVICE      1   /* pointer is device (HBM) memory on the batch's GPU               */
 #define TINY_BROADCAST   2   /* (set only) ONE matrix, replicated to every instance              */
+#define TINY_NOISE_FACTOR 4  /* (TinyNoiseSpec only) scale is an nx x nx factor, not a diagonal   */
 
 /* ---- problem family ---------------------------------------------------------------------- */
 int tiny_batch_device_count(void);
@@ -294,6 +295,50 @@ int tiny_batch_get_state_log(TinyBatch* b, double* x0_next, int steps);
 int tiny_batch_set_measurement_noise(TinyBatch* b, const double* v, int n_steps, int flags);
 /* row `step` of instance `instance` as installed: v_out [nx]; TINY_ERR_ARG with none installed or an index outside it */
 int tiny_batch_get_measurement_noise(TinyBatch* b, int step, int instance, double* v_out);
+/* the same two sequences GENERATED on the device from a seed: a Monte-Carlo episode takes a seed and a few scale vectors up instead of
+ * [n_steps][batch][nx] doubles drawn on the host.  Every entry is a pure function of (seed, stream, instance id, row, entry): the noise
+ * of an instance does not depend on how a study is batched or sharded, and one instance can be run again alone (a batch of one with
+ * id_base = its id).  The whole definition (csrc/noise_gen.hpp holds it as code, for host and device from one text):
+ *   Ids: instance i of the batch has the 64-bit id = id_base + i * id_stride (wrapping).  stream is 0 for the disturbance, 1 for the
+ *     measurement noise; k is the sequence row -- the value the step counters index; p = 0 .. ceil(nx/2) - 1 the pair index.
+ *   Bits: (r0, r1, r2, r3) = Philox4x32-10 of counter (id low 32, id high 32, k, (stream << 16) | p) under key (seed low 32, seed
+ *     high 32): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, key increments 0x9E3779B9, 0xBB67AE85, ten rounds, one round being
+ *     c' = (hi(M1*c2) ^ c1 ^ k0, lo(M1*c2), hi(M0*c0) ^ c3 ^ k1, lo(M0*c0)) on 32 x 32 -> 64 bit products, then key += increments.
+ *   Uniforms (exact): n1 = (r0 << 20) | (r1 >> 12), u1 = (2 n1 + 1) * 2^-53;  n2 = (r2 << 20) | (r3 >> 12), octant q = n2 >> 49,
+ *     m = n2 & (2^49 - 1), t = (2 m + 1) * 2^-50;  the angle is theta = (q + t) * pi/4.
+ *   Box-Muller: R = sqrt(-2 ln u1), g[2p] = R cos(theta), g[2p+1] = R sin(theta); |g| < 8.6.  ln, sin and cos are fma Horner chains of
+ *     the library's own in a fixed order, on integer operations, + - * /, sqrt and fma alone (no libm): with K = 2 n1 + 1, P its top
+ *     bit, e = P - 53, F = (K << (52 - P)) & (2^52 - 1): if F > 0x6A09E667F3BCD then mr = (1 + F 2^-52) / 2, e += 1, else
+ *     mr = 1 + F 2^-52;  f = mr - 1, d = 2 + f, s = f / d, z = s * s;  w = 1/23, then w = fma(w, z, 1/(2j+1)) for j = 10 .. 1;
+ *     zw = z * w, h = fma(s, zw, s), ln u1 = fma((double)e, LN2, h + h), LN2 = 0x3FE62E42FEFA39EF.  With a = t for even q and 1 - t for
+ *     odd q: x = a * PIO4 (0x3FE921FB54442D18), y = x * x;  ws = -1/19!, then ws = fma(ws, y, c) for c = +1/17!, -1/15!, ..., -1/3!,
+ *     yw = y * ws, sn = fma(x, yw, x);  wc = 1/20!, then wc = fma(wc, y, c) for c = -1/18!, +1/16!, ..., -1/2!, cs = fma(y, wc, 1);
+ *     cos(theta) = (q in {1, 2, 5, 6} ? sn : cs), negated for q in {2, 3, 4, 5}; sin(theta) = (q in {1, 2, 5, 6} ? cs : sn), negated
+ *     for q >= 4.  Every constant 1/n is the rounded division of the two doubles.  Host and device give the same bits.
+ *   Row k of instance i: with a diagonal scale  row[j] = fma(g[j], scale[j], mean[j]);  with TINY_NOISE_FACTOR scale is an nx x nx
+ *     column-major matrix S (a Cholesky factor: correlated noise; the upper triangle is read like any other entry) and
+ *     acc = mean[j]; for c = 0 .. nx-1 ascending: acc = fma(g[c], S[j + nx*c], acc); row[j] = acc.  mean == NULL means zeros.  For odd
+ *     nx the last pair's second deviate is dropped.
+ * TinyNoiseSpec: flags is TINY_HOST or TINY_DEVICE for scale and mean (copied; the caller may free), [batch][nx] each ([batch][nx*nx]
+ * for a factor), or with TINY_BROADCAST one of each for all; TINY_NOISE_FACTOR as above.
+ * Installing: the call fills a fresh [n_steps][batch][nx] device buffer (one fill kernel on the batch's stream; synchronous) and
+ * installs it exactly as tiny_batch_set_disturbance / tiny_batch_set_measurement_noise install a caller's sequence: the step counter
+ * is rewound, a failed call leaves what was installed, tiny_batch_reset leaves it alone, and removal stays
+ * tiny_batch_set_disturbance(b, NULL, 0, 0).  Everything downstream sees an ordinary sequence: the kernel forms, the getters, the options
+ * "disturbance", "disturbance_step", "last_disturbance" and their measurement twins.
+ * Read-backs: "disturbance_generated" / "measurement_noise_generated" read 1 while the installed sequence came from these calls, 0 once
+ * a setter replaced or removed it.
+ * TINY_ERR_ARG: a NULL spec or scale, n_steps <= 0, id_stride < 1, id_base < 0, unknown flag bits (a row of more than 65 536 pairs
+ * cannot occur: nx <= 32).
+ * Out of scope: generating inside the solve kernels instead of filling the buffer they read; distributions other than the normal;
+ * tiny_codegen, tiny_solve_batch and the drop-in structs. */
+typedef struct { unsigned long long seed; long long id_base, id_stride; int n_steps; int flags;
+                 const double* scale; const double* mean; } TinyNoiseSpec;
+int tiny_batch_generate_disturbance(TinyBatch* b, const TinyNoiseSpec* spec);
+int tiny_batch_generate_measurement_noise(TinyBatch* b, const TinyNoiseSpec* spec);
+/* host only, no GPU touched: rows [n_steps][batch][nx] exactly as the device fills them; stream 0 / 1; scale / mean host arrays
+ * (TINY_DEVICE, a NULL out, batch <= 0, nx <= 0, nx > 131 072 or another stream: TINY_ERR_ARG) */
+int tiny_noise_generate(const TinyNoiseSpec* spec, int stream, int batch, int nx, double* out);
 /* a state estimator in a closed loop (advance_x0, steps_per_launch > 1): between the sensor and the MPC sits a fixed-gain observer --
  * output-feedback MPC without the host in the loop.  One nx x nx innovation gain M per instance, or with TINY_BROADCAST one for all:
  * M = L*C covers a Luenberger observer or a steady-state Kalman filter with any output matrix C.  Unmeasured states are zero columns
@@ -653,6 +698,11 @@ int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, con
 /* measurement noise (tiny_batch_set_measurement_noise): host, [n_steps][batch][nx] over the full batch axis in the caller's order, or
  * with TINY_BROADCAST one [n_steps][nx]; NULL removes.  tiny_group_set_option forwards "measurement_step" */
 int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps, int flags);
+/* the two sequences generated on the shards' devices (tiny_batch_generate_disturbance / ..._measurement_noise): id_base / id_stride name
+ * the CALLER-order instance; scale / mean host arrays over the full batch axis in the caller's order, or with TINY_BROADCAST one.
+ * Every shard fills its own instances' rows: the noise of caller-order instance i does not depend on the sharding */
+int tiny_group_generate_disturbance(TinyGroup* g, const TinyNoiseSpec* spec);
+int tiny_group_generate_measurement_noise(TinyGroup* g, const TinyNoiseSpec* spec);
 /* a state estimator (tiny_batch_set_estimator, tiny_batch_set_estimate): host, M [batch][nx*nx] / xp [batch][nx] over the full batch
  * axis in the caller's order, or with TINY_BROADCAST one; M == NULL removes.  tiny_group_set_option forwards "estimate_log"; the log
  * and the estimate are read shard by shard (tiny_group_shard) */

@@ -26,6 +26,14 @@ _fp = C.POINTER(C.c_float)
 
 OK, ERR_DIM, ERR_NULL, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_HIP, ERR_ARG = 0, 1, -1, -2, -3, -4, -5
 HOST, DEVICE, BROADCAST = 0, 1, 2
+NOISE_FACTOR = 4                                 # TinyNoiseSpec.flags: scale is an nx x nx factor
+
+
+class NoiseSpec(C.Structure):
+    """TinyNoiseSpec (include/tinympc_amd.h)"""
+    _fields_ = [("seed", C.c_ulonglong), ("id_base", C.c_longlong), ("id_stride", C.c_longlong), ("n_steps", C.c_int), ("flags", C.c_int),
+                ("scale", C.POINTER(C.c_double)), ("mean", C.POINTER(C.c_double))]
+
 
 # TinyField (include/tinympc_amd.h)
 FIELDS = ("x0", "Xref", "Uref", "x", "u", "vnew", "znew", "g", "y", "v", "z", "vcnew", "zcnew", "gc", "yc",
@@ -43,6 +51,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_instance_cone_coefficients", "tiny_batch_get_instance_cone_coefficients",
     "tiny_batch_set_disturbance", "tiny_batch_get_disturbance", "tiny_batch_set_plant", "tiny_batch_get_plant", "tiny_batch_get_state_log",
     "tiny_batch_set_measurement_noise", "tiny_batch_get_measurement_noise",
+    "tiny_batch_generate_disturbance", "tiny_batch_generate_measurement_noise", "tiny_noise_generate",
     "tiny_batch_set_estimator", "tiny_batch_get_estimator", "tiny_batch_set_estimate", "tiny_batch_get_estimate", "tiny_batch_get_estimate_log",
     "tiny_batch_set_score", "tiny_batch_get_score_setup", "tiny_batch_get_score", "tiny_batch_reset_score",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
@@ -57,7 +66,7 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_generate_disturbance", "tiny_group_generate_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -185,6 +194,9 @@ def lib():
         L.tiny_batch_get_disturbance.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
         L.tiny_batch_set_measurement_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.tiny_batch_get_measurement_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.tiny_batch_generate_disturbance.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
+        L.tiny_batch_generate_measurement_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
+        L.tiny_noise_generate.argtypes = [C.POINTER(NoiseSpec), C.c_int, C.c_int, C.c_int, _dp]
         L.tiny_batch_set_estimator.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.tiny_batch_get_estimator.argtypes = [C.c_void_p, C.c_int, _dp]
         L.tiny_batch_set_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -264,6 +276,8 @@ def lib():
         L.tiny_group_set_instance_cone_coefficients.argtypes = [C.c_void_p, _dp, _dp, C.c_int]
         L.tiny_group_set_disturbance.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_set_measurement_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
+        L.tiny_group_generate_disturbance.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
+        L.tiny_group_generate_measurement_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
         L.tiny_group_set_estimator.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_estimate.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_score.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int]
@@ -328,6 +342,41 @@ def _colmajor(a, shape):
         a = a.reshape(-1, 1)
     a = np.broadcast_to(a, shape)
     return np.ascontiguousarray(a.T).ravel()
+
+
+def noise_spec(batch, nx, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+    """TinyNoiseSpec from numpy arrays.  scale: (nx,) or (batch, nx) -- with factor=True the MATRIX S (nx, nx) or (batch, nx, nx), passed
+    on column-major --; mean: None, (nx,) or (batch, nx); a 1-D scale (2-D factor) is one for all, and then the mean is (nx,) too.
+    Returns (spec, the arrays it points into: keep them alive across the call)"""
+    S = np.asarray(scale, dtype=np.float64)
+    one = S.ndim == (2 if factor else 1)
+    n = 1 if one else batch
+    want = (n, nx, nx) if factor else (n, nx)
+    if one:
+        S = S[None]
+    if S.shape != want:
+        raise ValueError(f"noise scale: {want[1:]} or {(batch,) + want[1:]}, got {np.shape(scale)}")
+    flat = np.ascontiguousarray(S.transpose(0, 2, 1) if factor else S).ravel()
+    mu = None
+    if mean is not None:
+        mu = _f64(mean)
+        if mu.shape != ((nx,) if one else (batch, nx)):
+            raise ValueError(f"noise mean: {(nx,) if one else (batch, nx)} with this scale, got {mu.shape}")
+        mu = mu.ravel()
+    spec = NoiseSpec(int(seed) & (2**64 - 1), int(id_base), int(id_stride), int(n_steps), HOST | (BROADCAST if one else 0) | (NOISE_FACTOR if factor else 0),
+                     flat.ctypes.data_as(_dp), None if mu is None else mu.ctypes.data_as(_dp))
+    return spec, (flat, mu)
+
+
+def noise_generate(seed, stream, n_steps, batch, nx, scale, mean=None, factor=False, id_base=0, id_stride=1):
+    """the rows tiny_batch_generate_disturbance (stream 0) / ..._measurement_noise (stream 1) fill, on the host (no GPU touched):
+    (n_steps, batch, nx), bit for bit what the device writes.  scale / mean: see noise_spec"""
+    spec, keep = noise_spec(batch, nx, seed, n_steps, scale, mean, factor, id_base, id_stride)
+    out = np.zeros((max(int(n_steps), 0), batch, nx))
+    rc = lib().tiny_noise_generate(C.byref(spec), int(stream), int(batch), int(nx), out.ctypes.data_as(_dp))
+    if rc != OK:
+        raise TinyMPCError(f"noise_generate failed ({rc}): a refused argument")
+    return out
 
 
 class TinyBatchSolver:
@@ -518,6 +567,19 @@ class TinyBatchSolver:
         out = np.zeros(self.nx)
         self._check(lib().tiny_batch_get_measurement_noise(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_measurement_noise")
         return out
+
+    def generate_disturbance(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """a disturbance sequence of n_steps rows GENERATED on the device: row k of instance i is mean + scale * g, g the standard normals
+        of (seed, stream 0, id_base + i * id_stride, k) -- a pure function of those, so the noise of an instance does not depend on the
+        batch it sits in.  scale (nx,) | (batch, nx); factor=True: a matrix S (nx, nx) | (batch, nx, nx), row = mean + S g (correlated
+        noise from a Cholesky factor).  Installed like set_disturbance's; set_disturbance(None) removes it"""
+        spec, keep = noise_spec(self.batch, self.nx, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_batch_generate_disturbance(self._h, C.byref(spec)), "generate_disturbance")
+
+    def generate_measurement_noise(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """the same for the measurement noise (stream 1: other deviates than the disturbance's under the same seed)"""
+        spec, keep = noise_spec(self.batch, self.nx, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_batch_generate_measurement_noise(self._h, C.byref(spec)), "generate_measurement_noise")
 
     def _plant(self, A_p, B_p, f_p):
         """A_p (batch, nx, nx) | (nx, nx), B_p (batch, nx, nu) | (nx, nu), f_p (batch, nx) | (nx,) | None -> (flat column-major arrays,
@@ -1089,6 +1151,17 @@ class TinyGroupSolver:
             return self._check(lib().tiny_group_set_measurement_noise(self._h, None, 0, HOST), "set_measurement_noise")
         flat, n, bc = TinyBatchSolver._disturbance(self, v)
         self._check(lib().tiny_group_set_measurement_noise(self._h, flat.ctypes.data_as(_dp), n, HOST | bc), "set_measurement_noise")
+
+    def generate_disturbance(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """TinyBatchSolver.generate_disturbance over the full batch axis: id_base / id_stride name the caller-order instance, so every
+        instance gets the noise it gets on a single batch, whatever the sharding"""
+        spec, keep = noise_spec(self.batch, self.nx, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_group_generate_disturbance(self._h, C.byref(spec)), "generate_disturbance")
+
+    def generate_measurement_noise(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """TinyBatchSolver.generate_measurement_noise over the full batch axis (see generate_disturbance)"""
+        spec, keep = noise_spec(self.batch, self.nx, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_group_generate_measurement_noise(self._h, C.byref(spec)), "generate_measurement_noise")
 
     def get_disturbance(self, step, i):
         """w[step, i] of instance i (the caller's order): asked of the shard that holds it"""

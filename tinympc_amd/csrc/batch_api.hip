@@ -1035,6 +1035,8 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_instance_cones")) return b->icone.last ? 1 : 0;   // the last solve's kernel read them: installed and a cone family on
     if (!strcmp(name, "disturbance")) return b->dist.seq ? b->dist.steps : 0;   // steps of the per-instance disturbance sequence installed (tiny_batch_set_disturbance); 0: none
     if (!strcmp(name, "disturbance_step")) return b->dist.step;               // the row the next plant step takes
+    if (!strcmp(name, "disturbance_generated")) return (b->dist.seq && b->dist.generated) ? 1 : 0;   // the installed sequence came from tiny_batch_generate_disturbance
+    if (!strcmp(name, "measurement_noise_generated")) return (b->meas.seq && b->meas.generated) ? 1 : 0;   // ... from tiny_batch_generate_measurement_noise
     if (!strcmp(name, "last_disturbance")) return b->dist.last ? 1 : 0;       // the last solve's launches applied the sequence: installed and a plant step taken
     if (!strcmp(name, "measurement_noise")) return b->meas.seq ? b->meas.steps : 0;   // steps of the measurement-noise sequence installed (tiny_batch_set_measurement_noise); 0: none
     if (!strcmp(name, "measurement_step")) return b->meas.step;               // the row the next MPC step's measurement takes

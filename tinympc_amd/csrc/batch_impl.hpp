@@ -74,6 +74,7 @@ struct Disturbance {
     int steps = 0;
     long step = 0;
     bool last = false;                             // (... applied the sequence: installed and a plant step taken)
+    bool generated = false;                        // the sequence came from tiny_batch_generate_disturbance (option "disturbance_generated")
     template <class F> void each_buffer(F f) { f(seq); }
 };
 // a plant model of its own at the plant step (tiny_batch_set_plant) and the log of what the plant step handed on (option "state_log").
@@ -103,6 +104,7 @@ struct MeasurementNoise {
     int steps = 0;
     long step = 0;
     bool last = false;                             // (... applied the sequence: installed and a plant step taken)
+    bool generated = false;                        // the sequence came from tiny_batch_generate_measurement_noise (option "measurement_noise_generated")
     double *model[3] = {nullptr, nullptr, nullptr}, *model_built = nullptr, *xm = nullptr;
     template <class F> void each_buffer(F f) { f(seq); for (double*& p : model) f(p); f(model_built); f(xm); }
 };

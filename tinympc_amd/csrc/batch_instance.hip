@@ -6,6 +6,7 @@
 #include "batch_impl.hpp"
 #include "batch_dispatch.hpp"
 #include "lane_tables.hpp"
+#include "noise_gen.hpp"
 
 #include <algorithm>
 #include <limits>
@@ -289,7 +290,7 @@ static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, in
     HIP_TRY(b, hipSetDevice(b->device));
     if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
         if (s.seq) { if (int rc = drop_buffers(b, s)) return rc; }
-        s.steps = 0; s.step = 0;
+        s.steps = 0; s.step = 0; s.generated = false;
         return TINY_OK;
     }
     const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row;
@@ -318,7 +319,88 @@ static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, in
         }
     }
     if (s.seq) (void)hipFree(s.seq);
-    s.seq = fresh; s.steps = n_steps; s.step = 0;
+    s.seq = fresh; s.steps = n_steps; s.step = 0; s.generated = false;
+    return TINY_OK;
+}
+// ---- a sequence generated on the device (tiny_batch_generate_disturbance / ..._measurement_noise): out [n_steps][batch][nx] filled with
+// the counter-based normals of noise_gen.hpp -- every entry a pure function of (seed, stream, instance id, row, entry), the same bits as
+// tiny_noise_generate gives on the host.  No LDS, no atomics, no scratch; measured, the arithmetic of a pair binds, not the stores
+// (profiles/noise_generator.md).
+// Diagonal form: one thread per pair (step, instance, p) in the order of the step-major block, so that consecutive threads write
+// consecutive addresses: one 16-byte store for an even nx (every pair then starts on a 16-byte boundary), two 8-byte stores otherwise,
+// one where the last pair's second half is dropped
+static __global__ __launch_bounds__(256) void generate_diagonal_kernel(double* __restrict__ out, const NoiseFill F) {
+    const int np = noise_pairs(F.nx);
+    const size_t per_step = (size_t)F.batch * np, total = (size_t)F.n_steps * per_step;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(e % np);
+        const size_t i = (e / np) % F.batch;
+        const uint32_t k = (uint32_t)(e / per_step);
+        double two[2];
+        noise_diagonal_pair(F, k, i, p, two);
+        double* at = out + ((size_t)k * F.batch + i) * F.nx + 2 * p;
+        if (!(F.nx & 1)) *reinterpret_cast<double2*>(at) = make_double2(two[0], two[1]);
+        else { at[0] = two[0]; if (2 * p + 1 < F.nx) at[1] = two[1]; }
+    }
+}
+// Factor form: one thread per row (step, instance): at most 16 Philox calls, the nx accumulators in registers (noise_factor_row32).  The
+// one shared S is read at wave-uniform addresses; a per-instance S is read by each thread from its own block
+static __global__ __launch_bounds__(256) void generate_factor_kernel(double* __restrict__ out, const NoiseFill F) {
+    const size_t total = (size_t)F.n_steps * F.batch;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
+        noise_factor_row32(F, (uint32_t)(e / F.batch), e % F.batch, out + e * F.nx);
+}
+// the checks tiny_batch_generate_* and tiny_noise_generate share: null (fine) or why the spec is refused
+static const char* noise_spec_refusal(const TinyNoiseSpec* spec, int nx) {
+    if (!spec) return "null spec";
+    if (!spec->scale) return "null scale";
+    if (spec->n_steps <= 0) return "n_steps <= 0";
+    if (spec->id_stride < 1) return "id_stride < 1";
+    if (spec->id_base < 0) return "id_base < 0";
+    if (spec->flags & ~(TINY_DEVICE | TINY_BROADCAST | TINY_NOISE_FACTOR)) return "flags: TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST and TINY_NOISE_FACTOR";
+    if (nx > 2 * 65536) return "more than 65 536 pairs a row";
+    return nullptr;
+}
+static NoiseFill noise_fill_of(const TinyNoiseSpec* spec, int stream, int batch, int nx, const double* scale, const double* mean) {
+    NoiseFill F = {};
+    F.seed = spec->seed; F.id_base = (uint64_t)spec->id_base; F.id_stride = (uint64_t)spec->id_stride;
+    F.stream = (uint32_t)stream; F.n_steps = spec->n_steps; F.batch = batch; F.nx = nx;
+    F.factor = (spec->flags & TINY_NOISE_FACTOR) != 0; F.broadcast = (spec->flags & TINY_BROADCAST) != 0;
+    F.scale = scale; F.mean = mean;
+    return F;
+}
+// the generated block takes the place install_sequence gives a caller's: a fresh buffer, complete before it replaces what is installed,
+// the counter rewound.  scale and mean are copied to the device for the fill and freed behind it.  Everything that can fail happens
+// before anything installed is touched
+template <class S>
+static int install_generated(TinyBatch* b, S& s, const TinyNoiseSpec* spec, int stream, const char* what) {
+    if (const char* why = noise_spec_refusal(spec, b->nx)) return fail(b, TINY_ERR_ARG, "%s: %s", what, why);
+    if (b->nx > 32) return fail(b, TINY_ERR_ARG, "%s: nx %d (a batch has nx <= 32: at most 16 pairs a row)", what, b->nx);
+    HIP_TRY(b, hipSetDevice(b->device));
+    const size_t row = (size_t)b->batch * b->nx, full = (size_t)spec->n_steps * row;
+    if (full / row != (size_t)spec->n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
+        return fail(b, TINY_ERR_ARG, "%s: %d steps of %d instances do not fit an address", what, spec->n_steps, b->batch);
+    const bool factor = (spec->flags & TINY_NOISE_FACTOR) != 0;
+    const size_t sets = (spec->flags & TINY_BROADCAST) ? 1 : (size_t)b->batch;
+    // the block is allocated FIRST: a step count no device memory holds fails there
+    double* fresh = nullptr;
+    if (hipMalloc(&fresh, full * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(b, TINY_ERR_HIP, "%s: out of device memory", what); }
+    const UploadPart parts[2] = {{spec->scale, sets * b->nx * (factor ? b->nx : 1)}, {spec->mean, sets * b->nx}};
+    double* staged[2];
+    if (int rc = upload_fresh(b, parts, staged, 2, spec->flags & TINY_DEVICE, what)) { (void)hipFree(fresh); return rc; }
+    const NoiseFill F = noise_fill_of(spec, stream, b->batch, b->nx, staged[0], staged[1]);
+    if (factor) hipLaunchKernelGGL(generate_factor_kernel, dim3(helper_grid(b, (size_t)spec->n_steps * b->batch)), dim3(256), 0, b->stream, fresh, F);
+    else hipLaunchKernelGGL(generate_diagonal_kernel, dim3(helper_grid(b, (size_t)spec->n_steps * b->batch * noise_pairs(b->nx))), dim3(256), 0, b->stream, fresh, F);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);         // (nothing reads the old sequence any more; the staged arrays may go)
+    for (double* p : staged) if (p) (void)hipFree(p);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(fresh);
+        return fail(b, TINY_ERR_HIP, "%s: %s", what, hipGetErrorString(err));
+    }
+    if (s.seq) (void)hipFree(s.seq);
+    s.seq = fresh; s.steps = spec->n_steps; s.step = 0; s.generated = true;
     return TINY_OK;
 }
 // row `step` of instance `instance` of such a sequence, as set: out [nx]
@@ -766,6 +848,22 @@ int tiny_batch_set_measurement_noise(TinyBatch* b, const double* v, int n_steps,
 int tiny_batch_get_measurement_noise(TinyBatch* b, int step, int instance, double* v_out) {
     if (!b) return TINY_ERR_NULL;
     return read_sequence_row(b, b->meas, step, instance, v_out, "no measurement-noise sequence installed");
+}
+// the same two sequences generated on the device from a seed (noise_gen.hpp); installed as the setters install a caller's
+int tiny_batch_generate_disturbance(TinyBatch* b, const TinyNoiseSpec* spec) {
+    if (!b) return TINY_ERR_NULL;
+    return install_generated(b, b->dist, spec, 0, "generated disturbance");
+}
+int tiny_batch_generate_measurement_noise(TinyBatch* b, const TinyNoiseSpec* spec) {
+    if (!b) return TINY_ERR_NULL;
+    return install_generated(b, b->meas, spec, 1, "generated measurement noise");
+}
+// the rows on the host, no GPU touched: out [n_steps][batch][nx] exactly as the device fills them
+int tiny_noise_generate(const TinyNoiseSpec* spec, int stream, int batch, int nx, double* out) {
+    if (noise_spec_refusal(spec, nx) || (spec->flags & TINY_DEVICE) || !out || batch <= 0 || nx <= 0 || (stream != 0 && stream != 1)) return TINY_ERR_ARG;
+    std::vector<double> g((size_t)2 * noise_pairs(nx));
+    noise_fill_host(noise_fill_of(spec, stream, batch, nx, spec->scale, spec->mean), out, g.data());
+    return TINY_OK;
 }
 // row `step` of instance `instance`, as set: w_out [nx]
 int tiny_batch_get_disturbance(TinyBatch* b, int step, int instance, double* w_out) {

@@ -364,6 +364,34 @@ int tiny_group_set_disturbance(TinyGroup* g, const double* w, int n_steps, int f
 int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps, int flags) {
     return group_set_sequence(g, v, n_steps, flags, tiny_batch_set_measurement_noise, "measurement noise");
 }
+// the same sequences generated on the shards' devices (tiny_batch_generate_disturbance / ..._measurement_noise): id_base / id_stride name
+// the CALLER-order instance, so shard k gets id_base + first * id_stride (contiguous shards) or id_base + k * id_stride with the stride
+// id_stride * n (round-robin), and its slice of per-instance scale / mean: the noise of an instance does not depend on the sharding
+static int group_generate(TinyGroup* g, const TinyNoiseSpec* spec, int (*gen)(TinyBatch*, const TinyNoiseSpec*), const char* what) {
+    if (!g) return TINY_ERR_NULL;
+    if (!spec) return gfail(g, TINY_ERR_ARG, "%s of a group: null spec", what);
+    if (spec->flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "%s of a group: host arrays (TINY_HOST)", what);
+    const bool pass = (spec->flags & TINY_BROADCAST) != 0;
+    const size_t nx = (size_t)g->nx;
+    std::vector<double> stage[2];
+    for (int k = 0; k < g->n; ++k) {
+        TinyNoiseSpec mine = *spec;
+        if (spec->id_stride >= 1) {                                       // (otherwise every shard refuses it)
+            mine.id_base = (long long)((unsigned long long)spec->id_base + (unsigned long long)first_of(g, k) * (unsigned long long)spec->id_stride);
+            if (g->interleaved) mine.id_stride = (long long)((unsigned long long)spec->id_stride * (unsigned long long)g->n);
+        }
+        if (!pass) {
+            mine.scale = shard_slice(g, k, spec->scale, (spec->flags & TINY_NOISE_FACTOR) ? nx * nx : nx, &stage[0]);
+            mine.mean = shard_slice(g, k, spec->mean, nx, &stage[1]);
+        }
+        if (int rc = gen(g->shard[k], &mine)) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
+int tiny_group_generate_disturbance(TinyGroup* g, const TinyNoiseSpec* spec) { return group_generate(g, spec, tiny_batch_generate_disturbance, "generated disturbance"); }
+int tiny_group_generate_measurement_noise(TinyGroup* g, const TinyNoiseSpec* spec) {
+    return group_generate(g, spec, tiny_batch_generate_measurement_noise, "generated measurement noise");
+}
 // a plant of its own at the plant step: A_p | B_p | f_p over the full batch axis in host memory, the caller's instance order; each shard
 // gets its instances' rows (TINY_BROADCAST: the one plant, as it is); A_p == NULL removes
 int tiny_group_set_plant(TinyGroup* g, const double* A_p, const double* B_p, const double* f_p, int flags) {

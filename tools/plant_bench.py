@@ -3,7 +3,7 @@
 the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
 by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
 (device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
-    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A] [--estimator G [--estimator-shared 1]] [--score device|host] [--package DIR] [--launches L] [--batch 65536]
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A|generated|host [--noise-form diagonal|factor]] [--estimator G [--estimator-shared 1]] [--score device|host] [--package DIR] [--launches L] [--batch 65536]
 --workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
                     reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
 --workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
@@ -17,6 +17,13 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
                     run, the counter rewound per episode.  A = 0: an all-zero sequence -- fl(x + 0) = x, so a PM form solves exactly the
                     problems the PP form with the model as plant solves, and the times differ by what the PM form costs
                     (profiles/measurement_noise.md).  With --plant none the PM form steps by the model's own block
+--noise generated   a DISTURBANCE sequence of one row per MPC step generated on the device (tiny_batch_generate_disturbance: seed 7, one scale for
+                    all -- --noise-form diagonal: --noise-scale on every entry; factor: a lower-triangular nx x nx factor), installed six
+                    times; install_* is the wall clock of the synchronous call over the last five, install_gbs the block's bytes over the
+                    median.  The run then goes on under that sequence, the counter rewound per episode (profiles/noise_generator.md)
+--noise host        the only route a tree without the generator has to the same state: numpy.random.default_rng(7).standard_normal of
+                    the block's shape, scaled (factor: multiplied by the factor) in numpy, and tiny_batch_set_disturbance(TINY_HOST);
+                    install_* is the wall clock of all three, draw_ms / scale_ms / set_ms their medians
 --estimator G       a state estimator installed (tiny_batch_set_estimator): every instance its own gain G * I (--estimator-shared 1: one for all), the estimate put at x0 at the start
                     of every episode.  With --noise 0 the innovation is zero at every step, so a PE form solves exactly the problems the PM
                     form solves, and the times differ by what the PE form costs (profiles/estimator.md)
@@ -48,11 +55,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--state-log", type=int, default=0)
-    ap.add_argument("--noise", type=float, default=None, help="measurement noise of this amplitude (0: an all-zero sequence)")
+    ap.add_argument("--noise", default=None, help="a number: measurement noise of this amplitude (0: an all-zero sequence); generated | host: a disturbance sequence from the device's generator / drawn in numpy")
+    ap.add_argument("--noise-form", choices=("diagonal", "factor"), default="diagonal")
+    ap.add_argument("--noise-scale", type=float, default=0.01)
     ap.add_argument("--estimator", type=float, default=None, help="a state estimator with the gain G * I per instance")
     ap.add_argument("--estimator-shared", type=int, default=0, help="1: ONE gain for all (TINY_BROADCAST) instead of [batch] copies")
     ap.add_argument("--score", choices=("device", "host"), default=None, help="a closed-loop score on the device, or both logs pulled and scored in numpy")
     a = ap.parse_args()
+    noise_source = a.noise if a.noise in ("generated", "host") else None
+    a.noise = None if (a.noise is None or noise_source) else float(a.noise)
     sys.path.insert(0, a.package)
     import tinympc_amd as tm
     B = a.batch
@@ -122,6 +133,28 @@ def main():
         if a.noise is not None:
             rows = a.steps if a.steps > 1 else a.warmup + launches
             s.set_measurement_noise(a.noise * np.random.default_rng(7).uniform(-1.0, 1.0, (rows, B, nx)))
+        install = None
+        if noise_source:
+            rows = a.steps if a.steps > 1 else a.warmup + launches
+            factor = a.noise_form == "factor"
+            scale = a.noise_scale * (np.tril(np.ones((nx, nx))) / np.sqrt(np.arange(1, nx + 1))[:, None] if factor else np.ones(nx))
+            install = dict(total=[], draw=[], scale=[], set=[])
+            for r in range(6):
+                s.synchronize()
+                t0 = time.perf_counter()
+                if noise_source == "generated":
+                    s.generate_disturbance(7, rows, scale, factor=factor)
+                    t1 = t2 = t0
+                else:
+                    g = np.random.default_rng(7).standard_normal((rows, B, nx))
+                    t1 = time.perf_counter()
+                    w = g @ scale.T if factor else g * scale
+                    t2 = time.perf_counter()
+                    s.set_disturbance(w)
+                t3 = time.perf_counter()
+                if r >= 1:
+                    for k, v in (("total", t3 - t0), ("draw", t1 - t0), ("scale", t2 - t1), ("set", t3 - t2)):
+                        install[k].append(1e3 * v)
         if a.estimator is not None:
             s.set_estimator(a.estimator * np.eye(nx) if a.estimator_shared else np.ascontiguousarray(np.broadcast_to(a.estimator * np.eye(nx), (B, nx, nx))))
         wall, scored = [], None
@@ -159,6 +192,8 @@ def main():
                 t0 = time.perf_counter()
                 if a.noise is not None:
                     s.set_option("measurement_step", 0)
+                if noise_source:
+                    s.set_option("disturbance_step", 0)
                 if a.estimator is not None:
                     s.set_estimate(s.get("x0"))
                 s.set_option("timing", 1)
@@ -193,6 +228,15 @@ def main():
         out.update(plant_kind=int(s.get_option("plant")), last_plant=int(s.get_option("last_plant")))
     if a.noise is not None:
         out.update(noise=a.noise, measurement_noise=int(s.get_option("measurement_noise")), last_measurement_noise=int(s.get_option("last_measurement_noise")))
+    if noise_source and a.plant != "host":
+        med = float(np.median(install["total"]))
+        out.update(noise_source=noise_source, noise_form=a.noise_form, disturbance=int(s.get_option("disturbance")), last_disturbance=int(s.get_option("last_disturbance")),
+                   install_median_ms=med, install_min_ms=float(min(install["total"])), install_max_ms=float(max(install["total"])),
+                   install_gbs=float(int(s.get_option("disturbance")) * B * nx * 8 / (med * 1e6)))
+        if noise_source == "host":
+            out.update(draw_ms=float(np.median(install["draw"])), scale_ms=float(np.median(install["scale"])), set_ms=float(np.median(install["set"])))
+        elif "disturbance_generated" in open(os.path.join(a.package, "include", "tinympc_amd.h")).read():
+            out.update(disturbance_generated=int(s.get_option("disturbance_generated")))
     if a.estimator is not None:
         out.update(estimator_gain=a.estimator, estimator=int(s.get_option("estimator")), last_estimator=int(s.get_option("last_estimator")))
     if a.score is not None and a.steps > 1:

@@ -2,7 +2,8 @@
 """CPU only: register / scratch / occupancy report of every kernel instantiation compiled into the library
 (hipcc -Rpass-analysis=kernel-resource-usage on tinympc_amd/csrc/_gen/{k,t}_*.hip).  Scratch > 0 = spilled to memory.
 The one-row forms csrc/jit_prebuilt.txt names (run-time instantiated, never in a unit) are compiled here as explicit instantiations and
-listed after the compiled-in ones; the setup kernels of batch_dispatch.hip (riccati_kernel, sensitivity_kernel) come last.
+listed after the compiled-in ones; then the setup kernels of batch_dispatch.hip (riccati_kernel, sensitivity_kernel) and, last, the helper
+kernels of batch_instance.hip (the fill kernels of the per-instance data and of the generated noise, the coverage path's helpers).
     python tools/register_audit.py [--all] > profiles/rNN_register_audit.md"""
 import concurrent.futures
 import glob
@@ -52,6 +53,11 @@ def setup_kernel_rows():
     return [r for r in usage("batch_dispatch.hip", cwd=CSRC, extra=("--cuda-device-only",)) if re.search(r"riccati_kernel|sensitivity_kernel", r["name"])]
 
 
+def helper_kernel_rows():
+    """every __global__ of batch_instance.hip: fill kernels (generate_diagonal_kernel / generate_factor_kernel among them) and coverage helpers"""
+    return usage("batch_instance.hip", cwd=CSRC, extra=("--cuda-device-only",))
+
+
 def main():
     srcs = sorted(glob.glob(os.path.join(GEN, "u_*.hip")))
     if not srcs:
@@ -99,6 +105,12 @@ def main():
     for r in setup_kernel_rows():
         kname = "sensitivity_kernel" if "sensitivity_kernel" in r["name"] else "riccati_kernel"
         print(f"| {kname} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
+    print("\nhelper kernels of batch_instance.hip (256 threads a block, grid-stride):\n")
+    print("| kernel | VGPR | AGPR | scratch B/lane | waves/SIMD | LDS B |")
+    print("|---|---|---|---|---|---|")
+    for r in helper_kernel_rows():
+        kname = re.search(r"tinympc_amdL?\d+([a-z_]+_kernel)", r["name"])
+        print(f"| {kname.group(1) if kname else r['name']} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
 
 
 if __name__ == "__main__":
