@@ -413,6 +413,63 @@ int tiny_batch_get_score_setup(TinyBatch* b, int instance, double* weight, doubl
 /* the record: [batch] each, host, any may be NULL; TINY_ERR_ARG with none installed */
 int tiny_batch_get_score(TinyBatch* b, double* cost, double* worst, int* violated_steps, int* first_violation);
 int tiny_batch_reset_score(TinyBatch* b);                                          /* zeroes the record, rewinds the counter, keeps the setup */
+/* an actuator model between the command and the plant step of a closed loop (advance_x0, steps_per_launch > 1): motors that saturate
+ * earlier than the controller's box says, follow a command with a lag, lose effectiveness or carry a trim error, and whose thrust is
+ * noisy -- the plant receives the APPLIED control ua, no longer the u0 the solver computed.
+ * Setup: lo, hi, alpha, gain, offset, each [batch][nu], or with TINY_BROADCAST one [nu] for all; TINY_HOST | TINY_DEVICE; copied, the
+ * caller may free.  Any may be NULL (its stage is absent); all five NULL removes the actuator.  lo[c] > hi[c] anywhere is TINY_ERR_ARG.
+ * A failed call leaves what was installed.
+ * Meaning: while an actuator or an actuation-noise sequence is installed, every MPC step of a launch that takes a plant step (fused
+ * steps, advance_x0, the stretches of "step_regroup") turns the commanded control into the applied one.  For instance i, input
+ * c = 0 .. nu-1 and actuation step counter k, uc = u0[c] is the command -- what the step log, the u record and the estimator's
+ * prediction keep on seeing:
+ *   1. Limits: s = uc < lo[c] ? lo[c] : (uc > hi[c] ? hi[c] : uc) -- two comparisons and two selects, no fmin / fmax: inside the limits
+ *      s has uc's own bits, the sign of a zero included.  NULL lo / hi mean -inf / +inf.
+ *   2. Lag (only if alpha is installed): d = fl(s - a[c]); m = fma(alpha[c], d, a[c]); a[c] <- m, where a [batch][nu] is the actuator
+ *      state record.  Without alpha m = s: no arithmetic happens and no record exists.
+ *   3. Gain and offset: g = fma(m, gain[c], offset[c]).  NULL gain means 1.0 and NULL offset means -0.0, so the neutral stage returns
+ *      m's bits for every m.
+ *   4. Noise: ua[c] = fl(g + n[k][i][c]) where row k of an installed sequence applies; otherwise ua[c] = g: no addition, not one of zero.
+ * ua replaces u0 in exactly two places: the plant step -- the fma chain tiny_batch_set_plant documents, over the installed plant or,
+ * with none, over the batch's own model block, as under measurement noise -- and the u entries of the score's z.  The estimator's
+ * prediction uses uc: a controller does not know what its actuator did.
+ *   The state log records the state handed on under ua.  Option "actuation_log" = 1 keeps ua per step: tiny_batch_get_actuation_log
+ *     returns [steps][batch][nu] of the last solve call.
+ *   A step that ran no iteration (max_iter = 0) takes no plant step: no stage runs, a stays, and the counter still advances.
+ *   A launch without a plant step reads nothing and runs the form it runs without an actuator.
+ *   Counter: k has the disturbance counter's rules: tiny_batch_set_actuation_noise and tiny_batch_generate_actuation_noise rewind it,
+ *     every MPC step of a launch with a plant step advances it (inside the stretches of "step_regroup" too), option "actuation_step"
+ *     moves it, rows outside [0, n_steps) add nothing.
+ *   Installing a lag where none was installed zeroes a; replacing the setup keeps a.  tiny_batch_reset leaves the setup, the record,
+ *     the sequence and the counter alone.
+ *   An actuator with gain = ones and nothing else, on a handle whose plant equals its model, reproduces the run with nothing
+ *     installed, bit for bit.
+ * Read-backs (tiny_batch_get_option): "actuator" 0 none, 1 one setup for all, 2 per instance; "actuator_lag" 1 while a lag is
+ * installed; "actuation_noise" n_steps as installed; "actuation_noise_generated" 1 while the installed sequence came from the
+ * generator; "actuation_step" the counter; "last_actuator" 1 when the last solve's launches went through the actuator;
+ * "actuation_log" the log switch.
+ * Where it runs: the one-row kernel's PA forms (run-time instantiated; always on a PP form, with the PD / PM / PE / PS bits as
+ * installed); everywhere else (tile-kernel shapes, overlapping cones, "debug", "force_general", "no_jit", a missing hipRTC) one helper
+ * kernel behind each single-step launch of the coverage kernel, same bits.  Adaptive rho on such a launch fails the solve with
+ * TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)").
+ * Out of scope: pure transport delays; rate limits; an estimator that is told ua; the tile kernel; the half-row and PREFETCH forms;
+ * tiny_codegen; tiny_solve_batch and the drop-in structs. */
+int tiny_batch_set_actuator(TinyBatch* b, const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int flags);
+/* the setup instance `instance` is actuated by, as installed, defaults filled in (alpha reads 1.0 with no lag): [nu] each, any may be
+ * NULL; TINY_ERR_ARG with none installed */
+int tiny_batch_get_actuator(TinyBatch* b, int instance, double* lo, double* hi, double* alpha, double* gain, double* offset);
+int tiny_batch_set_actuator_state(TinyBatch* b, const double* a, int flags);       /* [batch][nu]; HOST | DEVICE | BROADCAST ([nu]); TINY_ERR_ARG with no lag */
+int tiny_batch_get_actuator_state(TinyBatch* b, double* a_out);                    /* [batch][nu], host; TINY_ERR_ARG with no lag */
+/* the noise of stage 4: n [n_steps][batch][nu] step-major, or with TINY_BROADCAST [n_steps][nu]; tiny_batch_set_disturbance's rules
+ * (NULL / n_steps <= 0 removes; the setter rewinds the counter).  Noise alone, with no actuator, is allowed: only stage 4 runs */
+int tiny_batch_set_actuation_noise(TinyBatch* b, const double* n, int n_steps, int flags);
+int tiny_batch_get_actuation_noise(TinyBatch* b, int step, int instance, double* n_out);    /* [nu] */
+/* ... generated on the device (tiny_batch_generate_disturbance's rules): stream 2, rows of nu entries -- scale and mean [batch][nu]
+ * ([nu] with TINY_BROADCAST; TINY_NOISE_FACTOR: scale [..][nu*nu]) */
+int tiny_batch_generate_actuation_noise(TinyBatch* b, const TinyNoiseSpec* spec);
+/* ... and the same rows on the host, no GPU touched: out [n_steps][batch][nu] (tiny_noise_generate keeps to streams 0 and 1) */
+int tiny_actuation_noise_generate(const TinyNoiseSpec* spec, int batch, int nu, double* out);
+int tiny_batch_get_actuation_log(TinyBatch* b, double* ua, int steps);             /* option "actuation_log" = 1: [steps][batch][nu], the control every plant step of the last solve call received */
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -712,6 +769,13 @@ int tiny_group_set_estimate(TinyGroup* g, const double* xp, int flags);
  * TINY_BROADCAST one; weight == NULL removes.  tiny_group_set_option forwards "score_step"; the record is read shard by shard
  * (tiny_group_shard) */
 int tiny_group_set_score(TinyGroup* g, const double* weight, const double* target, const double* lo, const double* hi, int flags);
+/* an actuator model (tiny_batch_set_actuator and its neighbours): host, [batch][nu] each over the full batch axis in the caller's order,
+ * or with TINY_BROADCAST one; the noise [n_steps][batch][nu]; generated noise does not depend on the sharding.  tiny_group_set_option
+ * forwards "actuation_step" and "actuation_log"; the record and the log are read shard by shard (tiny_group_shard) */
+int tiny_group_set_actuator(TinyGroup* g, const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int flags);
+int tiny_group_set_actuator_state(TinyGroup* g, const double* a, int flags);
+int tiny_group_set_actuation_noise(TinyGroup* g, const double* n, int n_steps, int flags);
+int tiny_group_generate_actuation_noise(TinyGroup* g, const TinyNoiseSpec* spec);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

@@ -54,6 +54,9 @@ BATCH_SYMBOLS = (
     "tiny_batch_generate_disturbance", "tiny_batch_generate_measurement_noise", "tiny_noise_generate",
     "tiny_batch_set_estimator", "tiny_batch_get_estimator", "tiny_batch_set_estimate", "tiny_batch_get_estimate", "tiny_batch_get_estimate_log",
     "tiny_batch_set_score", "tiny_batch_get_score_setup", "tiny_batch_get_score", "tiny_batch_reset_score",
+    "tiny_batch_set_actuator", "tiny_batch_get_actuator", "tiny_batch_set_actuator_state", "tiny_batch_get_actuator_state",
+    "tiny_batch_set_actuation_noise", "tiny_batch_get_actuation_noise", "tiny_batch_generate_actuation_noise", "tiny_actuation_noise_generate",
+    "tiny_batch_get_actuation_log",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -66,7 +69,8 @@ GROUP_SYMBOLS = (
     "tiny_group_setup", "tiny_group_destroy", "tiny_group_shards", "tiny_group_shard", "tiny_group_shard_indices",
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
-    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_generate_disturbance", "tiny_group_generate_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score", "tiny_group_update_settings",
+    "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_generate_disturbance", "tiny_group_generate_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score",
+    "tiny_group_set_actuator", "tiny_group_set_actuator_state", "tiny_group_set_actuation_noise", "tiny_group_generate_actuation_noise", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -206,6 +210,15 @@ def lib():
         L.tiny_batch_get_score_setup.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
         L.tiny_batch_get_score.argtypes = [C.c_void_p, _dp, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.tiny_batch_reset_score.argtypes = [C.c_void_p]
+        L.tiny_batch_set_actuator.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_actuator.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp]
+        L.tiny_batch_set_actuator_state.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_actuator_state.argtypes = [C.c_void_p, _dp]
+        L.tiny_batch_set_actuation_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.tiny_batch_get_actuation_noise.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+        L.tiny_batch_generate_actuation_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
+        L.tiny_actuation_noise_generate.argtypes = [C.POINTER(NoiseSpec), C.c_int, C.c_int, _dp]
+        L.tiny_batch_get_actuation_log.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -281,6 +294,10 @@ def lib():
         L.tiny_group_set_estimator.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_estimate.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_score.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, C.c_int]
+        L.tiny_group_set_actuator.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, C.c_int]
+        L.tiny_group_set_actuator_state.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.tiny_group_set_actuation_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
+        L.tiny_group_generate_actuation_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
         L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -376,6 +393,17 @@ def noise_generate(seed, stream, n_steps, batch, nx, scale, mean=None, factor=Fa
     rc = lib().tiny_noise_generate(C.byref(spec), int(stream), int(batch), int(nx), out.ctypes.data_as(_dp))
     if rc != OK:
         raise TinyMPCError(f"noise_generate failed ({rc}): a refused argument")
+    return out
+
+
+def actuation_noise_generate(seed, n_steps, batch, nu, scale, mean=None, factor=False, id_base=0, id_stride=1):
+    """the rows tiny_batch_generate_actuation_noise fills (stream 2, rows of nu entries), on the host (no GPU touched): (n_steps, batch, nu),
+    bit for bit what the device writes.  scale / mean: see noise_spec, with nu for nx"""
+    spec, keep = noise_spec(batch, nu, seed, n_steps, scale, mean, factor, id_base, id_stride)
+    out = np.zeros((max(int(n_steps), 0), batch, nu))
+    rc = lib().tiny_actuation_noise_generate(C.byref(spec), int(batch), int(nu), out.ctypes.data_as(_dp))
+    if rc != OK:
+        raise TinyMPCError(f"actuation_noise_generate failed ({rc}): a refused argument")
     return out
 
 
@@ -730,6 +758,96 @@ class TinyBatchSolver:
     def reset_score(self):
         """zeroes the record and rewinds the counter; the setup stays"""
         self._check(lib().tiny_batch_reset_score(self._h), "reset_score")
+
+    def _actuator(self, lo, hi, alpha, gain, offset):
+        """five arrays over the inputs, (batch, nu) | (nu,) each or None -> (flat arrays or None, broadcast flag)"""
+        shape, out = None, []
+        for name, a in (("lo", lo), ("hi", hi), ("alpha", alpha), ("gain", gain), ("offset", offset)):
+            if a is None:
+                out.append(None)
+                continue
+            v = _f64(a)
+            if v.shape not in ((self.batch, self.nu), (self.nu,)) or (shape is not None and v.shape != shape):
+                raise ValueError(f"actuator: {name} ({self.batch}, {self.nu}) or ({self.nu},), all alike, got {v.shape}")
+            shape = v.shape
+            out.append(v.ravel())
+        return out, (BROADCAST if shape is not None and len(shape) == 1 else 0)
+
+    def set_actuator(self, lo=None, hi=None, alpha=None, gain=None, offset=None):
+        """an actuator model between the command and the plant step of a closed loop (advance_x0, steps_per_launch > 1): per input the
+        applied control is the command limited to [lo, hi], lagged (a += alpha * (s - a), one fma; a: actuator_state), scaled and offset
+        (fma(m, gain, offset)) and, with set_actuation_noise, disturbed.  It replaces u0 at the plant step and in the score, nowhere
+        else.  Each array (batch, nu), or (nu,) for one setup for all, or None (the stage is absent); all None removes it"""
+        a, bc = self._actuator(lo, hi, alpha, gain, offset)
+        p = [None if v is None else v.ctypes.data_as(C.c_void_p) for v in a]
+        self._check(lib().tiny_batch_set_actuator(self._h, p[0], p[1], p[2], p[3], p[4], HOST | bc), "set_actuator")
+
+    def set_actuator_device(self, lo=None, hi=None, alpha=None, gain=None, offset=None, broadcast=False):
+        """the same from device pointers (int; None where an array is left out) to [batch][nu] doubles (one row with broadcast) resident in HBM (copied)"""
+        p = [None if v is None else C.c_void_p(int(v)) for v in (lo, hi, alpha, gain, offset)]
+        self._check(lib().tiny_batch_set_actuator(self._h, p[0], p[1], p[2], p[3], p[4], DEVICE | (BROADCAST if broadcast else 0)), "set_actuator_device")
+
+    def get_actuator(self, i):
+        """(lo, hi, alpha, gain, offset), (nu,) each: what instance i is actuated by, as installed, defaults filled in"""
+        out = [np.zeros(self.nu) for _ in range(5)]
+        self._check(lib().tiny_batch_get_actuator(self._h, int(i), *[v.ctypes.data_as(_dp) for v in out]), "get_actuator")
+        return tuple(out)
+
+    def set_actuator_state(self, a):
+        """the lag's record a: (batch, nu), or (nu,) for all"""
+        v = _f64(a)
+        if v.shape not in ((self.batch, self.nu), (self.nu,)):
+            raise ValueError(f"actuator state: ({self.batch}, {self.nu}) or ({self.nu},), got {v.shape}")
+        self._check(lib().tiny_batch_set_actuator_state(self._h, v.ctypes.data_as(C.c_void_p), HOST | (BROADCAST if v.ndim == 1 else 0)), "set_actuator_state")
+
+    def set_actuator_state_device(self, a, broadcast=False):
+        self._check(lib().tiny_batch_set_actuator_state(self._h, C.c_void_p(int(a)), DEVICE | (BROADCAST if broadcast else 0)), "set_actuator_state_device")
+
+    def get_actuator_state(self):
+        """a (batch, nu) as it stands"""
+        out = np.zeros((self.batch, self.nu))
+        self._check(lib().tiny_batch_get_actuator_state(self._h, out.ctypes.data_as(_dp)), "get_actuator_state")
+        return out
+
+    def _actuation_noise(self, n):
+        """(n_steps, batch, nu), or (n_steps, nu) for one sequence for all -> (flat array, n_steps, broadcast flag)"""
+        n = np.ascontiguousarray(n, dtype=np.float64)
+        if n.ndim == 2 and n.shape[1] == self.nu and n.shape[0] > 0:
+            return n.ravel(), n.shape[0], BROADCAST
+        if n.ndim != 3 or n.shape[0] == 0 or n.shape[1:] != (self.batch, self.nu):
+            raise ValueError(f"actuation noise: (n_steps, {self.batch}, {self.nu}) or (n_steps, {self.nu}), got {n.shape}")
+        return n.ravel(), n.shape[0], 0
+
+    def set_actuation_noise(self, n):
+        """the noise of the actuator's last stage: the applied control of MPC step k takes + n[k, i].  n: (n_steps, batch, nu), or
+        (n_steps, nu) for one sequence for all; None removes it.  The counter (option "actuation_step") starts at 0; steps outside n add
+        nothing.  Allowed with no actuator installed"""
+        if n is None:
+            return self._check(lib().tiny_batch_set_actuation_noise(self._h, None, 0, HOST), "set_actuation_noise")
+        flat, k, bc = self._actuation_noise(n)
+        self._check(lib().tiny_batch_set_actuation_noise(self._h, flat.ctypes.data_as(C.c_void_p), k, HOST | bc), "set_actuation_noise")
+
+    def set_actuation_noise_device(self, n, n_steps, broadcast=False):
+        """the same from a device pointer (int) to [n_steps][batch][nu] doubles ([n_steps][nu] with broadcast) resident in HBM (copied)"""
+        self._check(lib().tiny_batch_set_actuation_noise(self._h, C.c_void_p(int(n)), int(n_steps), DEVICE | (BROADCAST if broadcast else 0)),
+                    "set_actuation_noise_device")
+
+    def get_actuation_noise(self, step, i):
+        """n[step, i] (nu,) as installed"""
+        out = np.zeros(self.nu)
+        self._check(lib().tiny_batch_get_actuation_noise(self._h, int(step), int(i), out.ctypes.data_as(_dp)), "get_actuation_noise")
+        return out
+
+    def generate_actuation_noise(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """generate_disturbance's twin for the actuation noise (stream 2, rows of nu entries: scale (nu,) | (batch, nu), ...)"""
+        spec, keep = noise_spec(self.batch, self.nu, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_batch_generate_actuation_noise(self._h, C.byref(spec)), "generate_actuation_noise")
+
+    def actuation_log(self, steps):
+        """ua[steps, batch, nu]: the control every plant step of the last solve call received (option "actuation_log" = 1)"""
+        out = np.zeros((steps, self.batch, self.nu))
+        self._check(lib().tiny_batch_get_actuation_log(self._h, out.ctypes.data_as(_dp), int(steps)), "get_actuation_log")
+        return out
 
     def set_linear_constraints(self, Alin_x, blin_x, Alin_u, blin_u):
         """Half-spaces a_k' z <= b_k (tiny_set_linear_constraints): Alin_x (n_s, nx), blin_x (n_s,), Alin_u (n_i, nu)."""
@@ -1244,11 +1362,48 @@ class TinyGroupSolver:
             if rc != OK:
                 raise TinyMPCError(f"reset_score failed ({rc}): {lib().tiny_batch_last_error(h).decode()}")
 
-    def _from_shards(self, steps, read, what):
-        out = np.zeros((steps, self.batch, self.nx))
+    def set_actuator(self, lo=None, hi=None, alpha=None, gain=None, offset=None):
+        """an actuator model for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); all None removes"""
+        a, bc = TinyBatchSolver._actuator(self, lo, hi, alpha, gain, offset)
+        p = [None if v is None else v.ctypes.data_as(_dp) for v in a]
+        self._check(lib().tiny_group_set_actuator(self._h, p[0], p[1], p[2], p[3], p[4], HOST | bc), "set_actuator")
+
+    def set_actuator_device(self, *args, **kwargs):
+        raise TinyMPCError("actuator of a group: host arrays (a device pointer belongs to one shard)")
+
+    def set_actuator_state(self, a):
+        """the lag's record of every instance (the caller's order), or (nu,) for all"""
+        v = _f64(a)
+        if v.shape not in ((self.batch, self.nu), (self.nu,)):
+            raise ValueError(f"actuator state: ({self.batch}, {self.nu}) or ({self.nu},), got {v.shape}")
+        self._check(lib().tiny_group_set_actuator_state(self._h, v.ctypes.data_as(_dp), HOST | (BROADCAST if v.ndim == 1 else 0)), "set_actuator_state")
+
+    def set_actuation_noise(self, n):
+        """actuation noise for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if n is None:
+            return self._check(lib().tiny_group_set_actuation_noise(self._h, None, 0, HOST), "set_actuation_noise")
+        flat, k, bc = TinyBatchSolver._actuation_noise(self, n)
+        self._check(lib().tiny_group_set_actuation_noise(self._h, flat.ctypes.data_as(_dp), k, HOST | bc), "set_actuation_noise")
+
+    def generate_actuation_noise(self, seed, n_steps, scale, mean=None, factor=False, id_base=0, id_stride=1):
+        """TinyBatchSolver.generate_actuation_noise over the full batch axis (see generate_disturbance)"""
+        spec, keep = noise_spec(self.batch, self.nu, seed, n_steps, scale, mean, factor, id_base, id_stride)
+        self._check(lib().tiny_group_generate_actuation_noise(self._h, C.byref(spec)), "generate_actuation_noise")
+
+    def get_actuator_state(self):
+        """a (batch, nu), gathered from the shards into the caller's order"""
+        return self._from_shards(1, lambda h, part: lib().tiny_batch_get_actuator_state(h, part.ctypes.data_as(_dp)), "get_actuator_state", self.nu)[0]
+
+    def actuation_log(self, steps):
+        """ua[steps, batch, nu] of the last solve call (option "actuation_log" = 1), gathered from the shards into the caller's order"""
+        return self._from_shards(steps, lambda h, part: lib().tiny_batch_get_actuation_log(h, part.ctypes.data_as(_dp), int(steps)), "get_actuation_log", self.nu)
+
+    def _from_shards(self, steps, read, what, width=None):
+        width = self.nx if width is None else width
+        out = np.zeros((steps, self.batch, width))
         for k in range(self.shards):
             idx = self.shard_indices(k)
-            part = np.zeros((steps, len(idx), self.nx))
+            part = np.zeros((steps, len(idx), width))
             h = lib().tiny_group_shard(self._h, k)
             rc = read(h, part)
             if rc != OK:

@@ -104,6 +104,21 @@ struct ScoreRecord {
 };
 static_assert(sizeof(ScoreRecord) == 24, "ScoreRecord: two doubles and two ints");
 
+// what the PA forms read of an actuator model (tiny_batch_set_actuator, tiny_batch_set_actuation_noise): ONE device-resident record per
+// solve call, written on the batch's stream in front of its first launch -- SolveArgs has room for one pointer to it and one int.
+// tab: [instances][lo | hi | alpha | gain | offset][16 lanes] (actuator_entry of lane_tables.hpp), bit 0 of the pointer: one block for
+// all, as at `plant`, bit 1: a lag is installed; the rest null: no actuator, the noise alone.  state [batch][NU]: the lag's record a.
+// noise [noise_steps][batch][NU], step-major like dist, or null.  log: null, or [rows][batch][NU], the applied control of every MPC step
+// of the solve call; the step whose actuation counter is k writes row k - log_step0.  All indexed by INSTANCE
+struct ActuatorLaunch {
+    const double* tab;
+    double* state;
+    const double* noise;
+    double* log;
+    int noise_steps, log_step0;
+};
+static_assert(sizeof(ActuatorLaunch) == 40, "ActuatorLaunch: four pointers and two ints");
+
 struct SolveArgs {
     const double* tab;        // tab_doubles(N) doubles
     const double* x0;         // [batch][nx]
@@ -189,6 +204,10 @@ struct SolveArgs {
             const double* score_tab;
             ScoreRecord* score_rec;
             int score_step0;
+            // PA forms: an actuator model between the command and the plant step -- act_step0 the actuation step counter at the launch's
+            // first MPC step, in the padding behind score_step0; act the solve call's record, over arho_max.  No PA form is an ADAPT form
+            int act_step0;
+            const ActuatorLaunch* act;
         };
     };
     int aclip;
@@ -279,6 +298,10 @@ static_assert(__builtin_offsetof(SolveArgs, arho) == 304 && __builtin_offsetof(S
 static_assert(__builtin_offsetof(SolveArgs, aC2) == 336 && __builtin_offsetof(SolveArgs, score_tab) == 336 && __builtin_offsetof(SolveArgs, atab) == 344 &&
               __builtin_offsetof(SolveArgs, score_rec) == 344 && __builtin_offsetof(SolveArgs, arho_min) == 352 && __builtin_offsetof(SolveArgs, score_step0) == 352 &&
               __builtin_offsetof(SolveArgs, arho_max) == 360 && __builtin_offsetof(SolveArgs, aclip) == 368, "SolveArgs: the score's fields share the adaptive-rho tables' place");
+
+// (the PA fields: the padding behind score_step0 and the place of arho_max; aclip and everything behind stay where they were)
+static_assert(__builtin_offsetof(SolveArgs, act_step0) == 356 && __builtin_offsetof(SolveArgs, act) == 360 && __builtin_offsetof(SolveArgs, arho_max) == 360 &&
+              __builtin_offsetof(SolveArgs, aclip) == 368 && __builtin_offsetof(SolveArgs, ref_shared) == 372, "SolveArgs: the actuator's fields share arho_max's place");
 
 // ---- DPP row-broadcast FMA blocks ------------------------------------------------------------
 // One asm statement per block so that the two wait states a DPP read needs after a VALU write of
@@ -879,6 +902,16 @@ __device__ __forceinline__ void score_chain(double& cost, const double s) {
         score_chain<COL0 + K, NCOL - K>(cost, s);
     }
 }
+// the actuator of the PA forms, the lane-local arithmetic of one input: limits by two comparisons and two selects (inside them the
+// command keeps its bits, the sign of a zero included; no fmin / fmax), the lag d = fl(s - a), m = fma(alpha, d, a), gain and offset
+// g = fma(m, gain, offset) -- every operation ONE IEEE rounding, nothing contracted
+__device__ __forceinline__ double actuator_limits(const double uc, const double lo, const double hi) { return uc < lo ? lo : (uc > hi ? hi : uc); }
+__device__ __forceinline__ double actuator_lag(const double s, const double a, const double alpha) {
+#pragma clang fp contract(off)
+    const double d = s - a;
+    return __builtin_fma(alpha, d, a);
+}
+__device__ __forceinline__ double actuator_gain(const double m, const double gain, const double offset) { return __builtin_fma(m, gain, offset); }
 
 // LIN: bit 0 = static half-spaces (admm.cpp:137-173), bit 1 = time-varying ones (:176-211); 0 = neither
 // HET: per-instance problem data (riccati_kernel.hip.h): the matrix rows are re-loaded for every instance
@@ -948,6 +981,15 @@ __device__ __forceinline__ void score_chain(double& cost, const double s) {
 // takes no plant step and is not scored.  Only the record moves.  PS rides on PD or PP (a launch with neither installed binds an
 // empty disturbance sequence, as the state log does); composes with everything they compose with.  Run-time instantiated only; bit 9
 // of the sixth template argument (MODE | 512).
+// PA: an actuator model (SolveArgs::act, act_step0) between the command and the plant step.  Where a PP form takes a plant step the input
+// lanes turn the command uc = u0 (slot 1) into the applied control ua: limits, lag, gain and offset, noise (actuator_limits, actuator_lag,
+// actuator_gain, plant_add) against the instance's setup block, each stage only where it is installed -- an absent stage leaves the bits
+// alone.  ua takes u0's place in the plant chain and in the score's z, nowhere else: the step log, the x|u record and the estimator's
+// prediction keep the command.  Each input lane reads and writes its own cell of the lag's record once per step and stores its entry of the
+// actuation log behind the score; whether a lag is installed is wave-uniform (bit 1 of the block pointer).  Everything is formed behind the iteration loop, from
+// the kernel-argument segment (late_arg): nothing of it lives through the loop.  A step that ran no iteration takes no plant step and
+// runs no stage.  PA implies PP (a launch with no plant installed forms the model's block, as PM does); composes with PD, PM, PE, PS,
+// PB / PL / PC and HET; not HALF, PF or ADAPT.  Run-time instantiated only; bit 10 of the sixth template argument (MODE | 1024).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -963,7 +1005,12 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PM = (MODE_PB & 128) != 0;
     constexpr bool PE = (MODE_PB & 256) != 0;
     constexpr bool PS = (MODE_PB & 512) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 1024, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator, + 512: a closed-loop score");
+    constexpr bool PA = (MODE_PB & 1024) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 2048, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator, + 512: a closed-loop score, + 1024: an actuator model");
+    static_assert(!PA || PP, "an actuator model: a form with a plant block (PP, bit 6): the plant step is a chain over the applied control");
+    static_assert(!PA || !ADAPT, "an actuator model: not with adaptive rho (refused)");
+    static_assert(!PA || !HALF, "an actuator model: not the half-row form");
+    static_assert(!PA || !PF, "an actuator model: not the prefetch form");
     static_assert(!PS || PD || PP, "a closed-loop score: a form that takes its plant step itself (PD, bit 5, or PP, bit 6)");
     static_assert(!PS || !ADAPT, "a closed-loop score: not with adaptive rho (refused)");
     static_assert(!PS || !HALF, "a closed-loop score: not the half-row form");
@@ -1612,6 +1659,52 @@ void admm_solve_kernel(const SolveArgs P) {
                 }
             };
             (void)scored;
+            // PA: the control the plant receives at MPC step `at_step` for the command `u0_row` (slot 1 of the input lanes): on an input
+            // lane the four stages against the instance's block, elsewhere u0_row as it is (the plant chain and the score read the input
+            // lanes only).  Called behind the iteration loop only, ONCE per step that takes a plant step -- it moves the lag's record --
+            // and everything it needs is formed there.  A form without PA: the command itself
+            auto applied = [&](const double u0_row, const int at_step) -> double {
+                if constexpr (PA) {
+                    int a_b = b;
+                    asm volatile("" : "+v"(a_b));
+                    const ActuatorLaunch* const act = late_arg<const ActuatorLaunch>(__builtin_offsetof(SolveArgs, act));
+                    const unsigned long long raw = reinterpret_cast<unsigned long long>(act->tab);
+                    const int k = late_value<int>(__builtin_offsetof(SolveArgs, act_step0)) + at_step;
+                    double ua = u0_row;
+                    // (the limits and the gain run on every lane of the row: a lane outside the inputs reads neutral entries, and nothing reads
+                    // what it computes.  Only the lag's record, the noise and the log are per input lane)
+                    if (raw & ~3ull) {
+                        const double* const t = reinterpret_cast<const double*>(raw & ~3ull) + ((raw & 1ull) ? (size_t)0 : (size_t)a_b * 80) + j;
+                        ua = actuator_limits(ua, t[0], t[16]);
+                        if ((raw & 2ull) && is_input) {
+                            double* const a = act->state + ((size_t)a_b * NU + (j - NX));
+                            ua = actuator_lag(ua, *a, t[32]);
+                            *a = ua;
+                        }
+                        ua = actuator_gain(ua, t[48], t[64]);
+                    }
+                    if (is_input) {
+                        const size_t cell = (size_t)a_b * NU + (j - NX);
+                        if (act->noise && (unsigned)k < (unsigned)act->noise_steps) ua = plant_add(ua, act->noise[(size_t)k * P.batch * NU + cell]);
+                    }
+                    return ua;
+                } else {
+                    return u0_row;
+                }
+            };
+            (void)applied;
+            // ... and its entry of the actuation log, stored on its own BEHIND the score: next to the other stages the store's address
+            // costs the cone PE + PS form the register pair that keeps a loop-invariant conversion out of the iteration loop
+            auto act_logged = [&](const double ua, const int at_step) {
+                if constexpr (PA) {
+                    int l_b = b;
+                    asm volatile("" : "+v"(l_b));
+                    const ActuatorLaunch* const act = late_arg<const ActuatorLaunch>(__builtin_offsetof(SolveArgs, act));
+                    const int k = late_value<int>(__builtin_offsetof(SolveArgs, act_step0)) + at_step;
+                    if (act->log && is_input) act->log[(size_t)(k - act->log_step0) * P.batch * NU + (size_t)l_b * NU + (j - NX)] = ua;
+                }
+            };
+            (void)act_logged;
             const int iter_first = resumed ? P.iter_base : 0;  // (a multiple of check_termination: the countdown restarts in phase)
             for (int step = 0; step < nsteps; ++step) {        // closed-loop MPC steps fused in one launch
                 X[0] = x0v;                                    // work->x.col(0) = x0
@@ -2107,18 +2200,25 @@ void admm_solve_kernel(const SolveArgs P) {
                             double xt = true_x0(step, cell);
                             [[maybe_unused]] double est_next = 0.0;             // PE: the xp the next step corrects -- predicted here, or (no iteration ran) the record's
                             if constexpr (PE) est_next = (iter > iter0) ? predicted(X[0], X[1]) : (is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[cell] : 0.0);
+                            double ua = X[1];                                   // (PA: what the plant receives; else the command)
                             if (iter > iter0) {
-                                const double xp = plant_step(xt, X[1]);
+                                ua = applied(X[1], step);
+                                const double xp = plant_step(xt, ua);
                                 xt = is_state ? xp : 0.0;
                                 if constexpr (PD) xt = disturbed(xt, step);
                             }
                             if (P.x0_next && is_state) P.x0_next[cell] = xt;      // (where true_x0 finds it; a step without a plant step: unchanged)
-                            if constexpr (PS) { if (iter > iter0) scored(xt, X[1], step); }
+                            if constexpr (PS) { if (iter > iter0) scored(xt, ua, step); }
+                            if constexpr (PA) { if (iter > iter0) act_logged(ua, step); }
                             if (P.state_log && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = xt;
                             x0v = measured(xt, step + 1);
                             if constexpr (PE) x0v = corrected(x0v, est_next);
                         }
                     } else {
+                    [[maybe_unused]] double ua = X[1];         // (PA: what the plant receives)
+                    if constexpr (PA) {                        // (a PP form: the chain over the applied control)
+                        if (step + 1 < nsteps && iter > iter0) { ua = applied(X[1], step); const double xp = plant_step(X[0], ua); x0v = is_state ? xp : 0.0; }
+                    } else
                     if constexpr (PP) {                        // (likewise; the chain runs on every lane of the row, the input lanes' rows are zero)
                         if (step + 1 < nsteps && iter > iter0) { const double xp = plant_step(X[0], X[1]); x0v = is_state ? xp : 0.0; }
                     }
@@ -2129,7 +2229,10 @@ void admm_solve_kernel(const SolveArgs P) {
                         if (P.state_log && step + 1 < nsteps && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = x0v;
                     }
                     if constexpr (PS) {                        // (the score of a step that took its plant step: what it handed on, under the u0 it applied)
-                        if (step + 1 < nsteps && iter > iter0) scored(x0v, X[1], step);
+                        if (step + 1 < nsteps && iter > iter0) scored(x0v, PA ? ua : X[1], step);
+                    }
+                    if constexpr (PA) {
+                        if (step + 1 < nsteps && iter > iter0) act_logged(ua, step);
                     }
                     }
                 }
@@ -2223,11 +2326,13 @@ void admm_solve_kernel(const SolveArgs P) {
                     }
                 }
                 if (P.x0_next && acc_iter > 0) {
-                    double xn = plant_step(xt, X[1]);
+                    const double ua = applied(X[1], nsteps - 1);
+                    double xn = plant_step(xt, ua);
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);
                     if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
                     if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
-                    if constexpr (PS) scored(xn, X[1], nsteps - 1);
+                    if constexpr (PS) scored(xn, ua, nsteps - 1);
+                    if constexpr (PA) act_logged(ua, nsteps - 1);
                 } else if (P.state_log && is_state) {
                     P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xt;
                 }
@@ -2235,11 +2340,14 @@ void admm_solve_kernel(const SolveArgs P) {
             if constexpr (PD || PP) {                        // (the plant step of the launch's LAST MPC step)
                 if (P.x0_next && acc_iter > 0) {
                     double xn = X[1];
+                    [[maybe_unused]] double ua = X[1];       // (PA: what the plant receives)
+                    if constexpr (PA) { ua = applied(X[1], nsteps - 1); xn = plant_step(X[0], ua); } else
                     if constexpr (PP) xn = plant_step(X[0], X[1]);
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);
                     if (is_state) P.x0_next[(size_t)b * NX + j] = xn;
                     if (P.state_log && is_state) P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = xn;
-                    if constexpr (PS) scored(xn, X[1], nsteps - 1);
+                    if constexpr (PS) scored(xn, PA ? ua : X[1], nsteps - 1);
+                    if constexpr (PA) act_logged(ua, nsteps - 1);
                 } else if (P.state_log && is_state) {        // (no plant step: the x0 the launch left in place)
                     P.state_log[((size_t)(nsteps - 1) * P.batch + b) * NX + j] = P.x0[(size_t)b * NX + j];
                 }

@@ -90,6 +90,16 @@ int score_step_base(const TinyBatch* b);
 int ensure_score_blocks(TinyBatch* b);
 const double* score_kernel_pointer(const TinyBatch* b);
 int enqueue_coverage_score(TinyBatch* b, long step);
+// an actuator model: it or an actuation-noise sequence is installed AND the next launch takes a plant step / the actuation step counter
+// as the kernels take it / the setup blocks, the log of `rows` MPC steps and the record the PA forms read (SolveArgs::act), made and
+// written on the stream in front of a solve call's first launch / the coverage path's helper kernel behind one single-step launch: the
+// applied control of actuation step `step` into Actuator::ua (what the plant and score helpers behind it read), the lag's record and
+// row `log_row` of the log / the log sized for a coverage launch
+bool actuator_active(const TinyBatch* b);
+int actuation_step_base(const TinyBatch* b);
+int ensure_actuator_launch(TinyBatch* b, int rows, const ActuatorLaunch** out);
+int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row);
+int begin_actuation_log(TinyBatch* b, int rows);
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>
 void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }

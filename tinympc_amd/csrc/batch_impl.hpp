@@ -139,8 +139,39 @@ struct Score {
     long step = 0;
     template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(rec); }
 };
+// an actuator model between the command and the plant step (tiny_batch_set_actuator).  src: the caller's lo | hi | alpha | gain | offset,
+// kept on the device as given ([batch][nu] each, or ONE with kind 1; any may be null) -- what the getter and the coverage path's helper
+// kernel read; built: the blocks the one-row kernel's PA forms read (actuator_entry of lane_tables.hpp: [batch or 1][5][16]), made in
+// front of the next launch; state [batch][nu]: the lag's record a, STATE of the batch, there while a lag (alpha) is installed; ua
+// [batch][nu]: where the coverage path's helper kernel puts the applied control for the plant and score helpers behind it; log
+// [log_steps][batch][nu]: the applied control of every MPC step of the last solve call (option "actuation_log"); desc: the record the PA
+// forms read (ActuatorLaunch of admm_kernel.hip.h), written on the stream in front of a solve call's first launch.  last: the last
+// solve's launches went through the actuator -- this setup or the noise sequence below
+struct Actuator {
+    int kind = 0;                                  // 0 none, 1 one setup for all, 2 every instance its own
+    bool lag = false;                              // alpha is installed
+    bool dirty = false, last = false;
+    double *src[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *built = nullptr, *state = nullptr, *ua = nullptr;
+    bool log_on = false;                           // option "actuation_log"
+    double* log = nullptr;
+    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
+    int log_rows = 0;
+    void* desc = nullptr;
+    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(state); f(ua); f(log); f(desc); }
+};
+// actuation noise, the last stage of the actuator (tiny_batch_set_actuation_noise): seq [steps][batch][nu], step-major like the
+// disturbance's, a broadcast sequence expanded on the device; step: the actuation step counter (the disturbance counter's rules: this
+// setter rewinds it, option "actuation_step" moves it, every MPC step of a launch that takes a plant step under an actuator or this
+// sequence advances it)
+struct ActuationNoise {
+    double* seq = nullptr;
+    int steps = 0;
+    long step = 0;
+    bool generated = false;                        // the sequence came from tiny_batch_generate_actuation_noise (option "actuation_noise_generated")
+    template <class F> void each_buffer(F f) { f(seq); }
+};
 
-constexpr size_t KPI_SKEW_BYTES = 0;           // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
+constexpr size_t KPI_SKEW_BYTES = 0;         // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
 struct TinyBatch {
     int nx = 0, nu = 0, N = 0, batch = 0, device = 0, num_cus = 256;
     const tinympc_amd::KernelEntry* kernel = nullptr;
@@ -228,7 +259,7 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score; Actuator act; ActuationNoise anoise;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

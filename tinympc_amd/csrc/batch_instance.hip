@@ -276,24 +276,25 @@ static __global__ __launch_bounds__(256) void expand_disturbance_kernel(double* 
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x)
         out[e] = seq[(e / row) * nx + e % nx];
 }
-static int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps) {
-    const size_t total = (size_t)n_steps * b->batch * b->nx;
-    hipLaunchKernelGGL(expand_disturbance_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, out, seq, total, b->batch, b->nx);
+static int expand_disturbance(TinyBatch* b, double* out, const double* seq, int n_steps, int width) {
+    const size_t total = (size_t)n_steps * b->batch * width;
+    hipLaunchKernelGGL(expand_disturbance_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, out, seq, total, b->batch, width);
     HIP_TRY(b, hipGetLastError());
     return TINY_OK;
 }
 // a step-major sequence [n_steps][batch][nx] (TINY_BROADCAST: [n_steps][nx], expanded on the device so that the kernels know one
-// layout), copied into S::seq with its counter rewound -- the disturbance and the measurement noise.  Everything that can fail happens
-// before anything installed is touched
+// layout), copied into S::seq with its counter rewound -- the disturbance and the measurement noise, and with rows of `width` = nu
+// entries the actuation noise (0: nx).  Everything that can fail happens before anything installed is touched
 template <class S>
-static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, int flags, const char* what, const char* what_short) {
+static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, int flags, const char* what, const char* what_short, int width = 0) {
+    if (width <= 0) width = b->nx;
     HIP_TRY(b, hipSetDevice(b->device));
     if (!w || n_steps <= 0) {                                            // remove: freed once the stream has run dry of its readers
         if (s.seq) { if (int rc = drop_buffers(b, s)) return rc; }
         s.steps = 0; s.step = 0; s.generated = false;
         return TINY_OK;
     }
-    const size_t row = (size_t)b->batch * b->nx, full = (size_t)n_steps * row;
+    const size_t row = (size_t)b->batch * width, full = (size_t)n_steps * row;
     if (full / row != (size_t)n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
         return fail(b, TINY_ERR_ARG, "%s: %d steps of %d instances do not fit an address", what_short, n_steps, b->batch);
     double* fresh = nullptr;
@@ -303,13 +304,13 @@ static int install_sequence(TinyBatch* b, S& s, const double* w, int n_steps, in
     } else {
         // one sequence for all, staged and expanded.  The expanded buffer is allocated FIRST: a step count no device memory holds fails
         // there, before the stage is sized by it and a byte of the caller's (then far shorter) array is read
-        const size_t given = (size_t)n_steps * b->nx;
+        const size_t given = (size_t)n_steps * width;
         double* stage = nullptr;
         hipError_t err = hipMalloc(&fresh, full * sizeof(double));
         int rc = TINY_OK;
         if (err == hipSuccess) err = hipMalloc(&stage, given * sizeof(double));
         if (err == hipSuccess) err = hipMemcpyAsync(stage, w, given * sizeof(double), (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, b->stream);
-        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps);
+        if (err == hipSuccess) rc = expand_disturbance(b, fresh, stage, n_steps, width);
         if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);      // (the caller may free its array; nothing reads the old one any more)
         if (stage) (void)hipFree(stage);
         if (err != hipSuccess || rc != TINY_OK) {
@@ -373,11 +374,12 @@ static NoiseFill noise_fill_of(const TinyNoiseSpec* spec, int stream, int batch,
 // the counter rewound.  scale and mean are copied to the device for the fill and freed behind it.  Everything that can fail happens
 // before anything installed is touched
 template <class S>
-static int install_generated(TinyBatch* b, S& s, const TinyNoiseSpec* spec, int stream, const char* what) {
-    if (const char* why = noise_spec_refusal(spec, b->nx)) return fail(b, TINY_ERR_ARG, "%s: %s", what, why);
-    if (b->nx > 32) return fail(b, TINY_ERR_ARG, "%s: nx %d (a batch has nx <= 32: at most 16 pairs a row)", what, b->nx);
+static int install_generated(TinyBatch* b, S& s, const TinyNoiseSpec* spec, int stream, const char* what, int width = 0) {
+    const int nx = width > 0 ? width : b->nx;        // (the row's width: nx, or nu for the actuation noise)
+    if (const char* why = noise_spec_refusal(spec, nx)) return fail(b, TINY_ERR_ARG, "%s: %s", what, why);
+    if (nx > 32) return fail(b, TINY_ERR_ARG, "%s: width %d (a batch has rows of at most 32 entries: at most 16 pairs a row)", what, nx);
     HIP_TRY(b, hipSetDevice(b->device));
-    const size_t row = (size_t)b->batch * b->nx, full = (size_t)spec->n_steps * row;
+    const size_t row = (size_t)b->batch * nx, full = (size_t)spec->n_steps * row;
     if (full / row != (size_t)spec->n_steps || full > (std::numeric_limits<size_t>::max)() / sizeof(double))
         return fail(b, TINY_ERR_ARG, "%s: %d steps of %d instances do not fit an address", what, spec->n_steps, b->batch);
     const bool factor = (spec->flags & TINY_NOISE_FACTOR) != 0;
@@ -385,12 +387,12 @@ static int install_generated(TinyBatch* b, S& s, const TinyNoiseSpec* spec, int 
     // the block is allocated FIRST: a step count no device memory holds fails there
     double* fresh = nullptr;
     if (hipMalloc(&fresh, full * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); return fail(b, TINY_ERR_HIP, "%s: out of device memory", what); }
-    const UploadPart parts[2] = {{spec->scale, sets * b->nx * (factor ? b->nx : 1)}, {spec->mean, sets * b->nx}};
+    const UploadPart parts[2] = {{spec->scale, sets * nx * (factor ? nx : 1)}, {spec->mean, sets * nx}};
     double* staged[2];
     if (int rc = upload_fresh(b, parts, staged, 2, spec->flags & TINY_DEVICE, what)) { (void)hipFree(fresh); return rc; }
-    const NoiseFill F = noise_fill_of(spec, stream, b->batch, b->nx, staged[0], staged[1]);
+    const NoiseFill F = noise_fill_of(spec, stream, b->batch, nx, staged[0], staged[1]);
     if (factor) hipLaunchKernelGGL(generate_factor_kernel, dim3(helper_grid(b, (size_t)spec->n_steps * b->batch)), dim3(256), 0, b->stream, fresh, F);
-    else hipLaunchKernelGGL(generate_diagonal_kernel, dim3(helper_grid(b, (size_t)spec->n_steps * b->batch * noise_pairs(b->nx))), dim3(256), 0, b->stream, fresh, F);
+    else hipLaunchKernelGGL(generate_diagonal_kernel, dim3(helper_grid(b, (size_t)spec->n_steps * b->batch * noise_pairs(nx))), dim3(256), 0, b->stream, fresh, F);
     hipError_t err = hipGetLastError();
     if (err == hipSuccess) err = hipStreamSynchronize(b->stream);         // (nothing reads the old sequence any more; the staged arrays may go)
     for (double* p : staged) if (p) (void)hipFree(p);
@@ -405,12 +407,13 @@ static int install_generated(TinyBatch* b, S& s, const TinyNoiseSpec* spec, int 
 }
 // row `step` of instance `instance` of such a sequence, as set: out [nx]
 template <class S>
-static int read_sequence_row(TinyBatch* b, const S& s, int step, int instance, double* out, const char* none) {
+static int read_sequence_row(TinyBatch* b, const S& s, int step, int instance, double* out, const char* none, int width = 0) {
+    if (width <= 0) width = b->nx;
     if (!out) return fail(b, TINY_ERR_ARG, "null output");
     if (!s.seq) return fail(b, TINY_ERR_ARG, "%s", none);
     if (step < 0 || step >= s.steps) return fail(b, TINY_ERR_ARG, "step %d of %d", step, s.steps);
     if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
-    return read_instance(b, out, s.seq + (size_t)step * b->batch * b->nx, instance, b->nx);
+    return read_instance(b, out, s.seq + (size_t)step * b->batch * width, instance, width);
 }
 bool disturbance_active(const TinyBatch* b) { return b->dist.seq && b->dist.steps > 0 && (b->advance_x0 || b->steps_per_launch > 1); }
 // (the kernels count steps in an int; a counter moved beyond +-2^30 is outside every sequence either way)
@@ -496,8 +499,10 @@ int begin_state_log(TinyBatch* b, int rows) {
 }
 // the coverage path's plant step: one thread per (instance, state row), the chain of tiny_batch_set_plant in explicit fma()s.  Every
 // thread reads x0 and u0 and writes `next`, never x0 itself: the rows of an instance are read by its other threads.  An instance whose
-// launch ran no iteration took no plant step: its x0 passes through
+// launch ran no iteration took no plant step: its x0 passes through.  ua: null, or [batch][nu], the applied control under an actuator
+// model (coverage_actuator_kernel), read in place of the record's u0
 static __global__ __launch_bounds__(256) void coverage_plant_step_kernel(double* __restrict__ next, const double* __restrict__ x0, const double* __restrict__ prim,
+                                                                         const double* __restrict__ ua,
                                                                          const int4* __restrict__ status, const double* __restrict__ A_p, const double* __restrict__ B_p,
                                                                          const double* __restrict__ f_p, int per_instance, const double* __restrict__ dist, int batch,
                                                                          int nx, int nu, int N) {
@@ -506,7 +511,7 @@ static __global__ __launch_bounds__(256) void coverage_plant_step_kernel(double*
         const int j = (int)(e % nx);
         const size_t bb = e / nx, p = per_instance ? bb : 0;
         if (status[bb].x <= 0) { next[e] = x0[e]; continue; }
-        const double *A = A_p + p * nx * nx, *B = B_p + p * nx * nu, *u0 = prim + bb * N * (nx + nu) + nx;
+        const double *A = A_p + p * nx * nx, *B = B_p + p * nx * nu, *u0 = ua ? ua + bb * nu : prim + bb * N * (nx + nu) + nx;
         double acc = f_p ? f_p[p * nx + j] : 0.0;
         for (int k = 0; k < nx; ++k) acc = fma(x0[bb * nx + k], A[j + nx * k], acc);
         for (int k = 0; k < nu; ++k) acc = fma(u0[k], B[j + nx * k], acc);
@@ -519,7 +524,8 @@ int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block) {
     const PlantSource p = plant_source(b);
     const size_t total = (size_t)b->batch * b->nx;
     if (!s.next) HIP_TRY(b, hipMalloc(&s.next, total * sizeof(double)));
-    hipLaunchKernelGGL(coverage_plant_step_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.next, b->d_x0, b->d_prim, b->d_status, p.src[0], p.src[1],
+    hipLaunchKernelGGL(coverage_plant_step_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.next, b->d_x0, b->d_prim,
+                       b->act.last ? b->act.ua : nullptr, b->d_status, p.src[0], p.src[1],
                        p.src[2], p.per_instance ? 1 : 0, dist_block, b->batch, b->nx, b->nu, b->N);
     HIP_TRY(b, hipGetLastError());
     HIP_TRY(b, hipMemcpyAsync(b->d_x0, s.next, total * sizeof(double), hipMemcpyDeviceToDevice, b->stream));
@@ -691,6 +697,7 @@ int ensure_score_blocks(TinyBatch* b) {
 // tiny_batch_set_score in its stated order over z = [x0 as handed on | the u0 of the x|u record] -- what score_term, score_chain and the
 // row maximum do on the one-row kernel, same bits.  An instance whose launch ran no iteration took no plant step and is not scored
 static __global__ __launch_bounds__(256) void coverage_score_kernel(ScoreRecord* __restrict__ rec, const double* __restrict__ x0, const double* __restrict__ prim,
+                                                                    const double* __restrict__ ua,
                                                                     const int4* __restrict__ status, const double* __restrict__ weight, const double* __restrict__ target,
                                                                     const double* __restrict__ lo, const double* __restrict__ hi, int per_instance, int step, int batch,
                                                                     int nx, int nu, int N) {
@@ -699,7 +706,7 @@ static __global__ __launch_bounds__(256) void coverage_score_kernel(ScoreRecord*
     for (int bb = blockIdx.x * blockDim.x + threadIdx.x; bb < batch; bb += gridDim.x * blockDim.x) {
         if (status[bb].x <= 0) continue;
         const size_t p = per_instance ? (size_t)bb * nz : 0;
-        const double *xn = x0 + (size_t)bb * nx, *u0 = prim + (size_t)bb * N * nz + nx;
+        const double *xn = x0 + (size_t)bb * nx, *u0 = ua ? ua + (size_t)bb * nu : prim + (size_t)bb * N * nz + nx;
         ScoreRecord r = rec[bb];
         double m = 0.0;
         for (int c = 0; c < nz; ++c) {
@@ -722,8 +729,108 @@ static __global__ __launch_bounds__(256) void coverage_score_kernel(ScoreRecord*
 int enqueue_coverage_score(TinyBatch* b, long step) {
     Score& s = b->score;
     const int k = (int)std::clamp<long>(step, -(1L << 30), 1L << 30);
-    hipLaunchKernelGGL(coverage_score_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, static_cast<ScoreRecord*>(s.rec), b->d_x0, b->d_prim, b->d_status,
+    hipLaunchKernelGGL(coverage_score_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, static_cast<ScoreRecord*>(s.rec), b->d_x0, b->d_prim,
+                       b->act.last ? b->act.ua : nullptr, b->d_status,
                        s.src[0], s.src[1], s.src[2], s.src[3], s.kind == 2 ? 1 : 0, k, b->batch, b->nx, b->nu, b->N);
+    HIP_TRY(b, hipGetLastError());
+    return TINY_OK;
+}
+
+// ---- an actuator model between the command and the plant step (tiny_batch_set_actuator): the caller's lo | hi | alpha | gain | offset ->
+// [setups][5][16 lanes], one thread per (setup, row, lane); what lands there: actuator_entry (lane_tables.hpp), nothing else
+static __global__ __launch_bounds__(256) void fill_actuator_kernel(double* __restrict__ out, const double* __restrict__ lo, const double* __restrict__ hi,
+                                                                   const double* __restrict__ alpha, const double* __restrict__ gain, const double* __restrict__ offset,
+                                                                   int setups, int nx, int nu) {
+    const size_t total = (size_t)setups * actuator_block_doubles();
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(e % 16), r = (int)((e / 16) % 5);
+        const size_t g = e / actuator_block_doubles() * nu;
+        out[e] = actuator_entry(lo ? lo + g : nullptr, hi ? hi + g : nullptr, alpha ? alpha + g : nullptr, gain ? gain + g : nullptr, offset ? offset + g : nullptr, nx, nu, r,
+                                lane);
+    }
+}
+// the record the PA forms read, written on the stream: the launches behind it see it, the ones in front of it have read theirs
+static __global__ void write_actuator_launch_kernel(ActuatorLaunch* __restrict__ out, const ActuatorLaunch v) { *out = v; }
+bool actuator_active(const TinyBatch* b) {
+    return (b->act.kind != 0 || (b->anoise.seq && b->anoise.steps > 0)) && (b->advance_x0 || b->steps_per_launch > 1);
+}
+int actuation_step_base(const TinyBatch* b) { return (int)std::clamp<long>(b->anoise.step, -(1L << 30), 1L << 30); }
+int begin_actuation_log(TinyBatch* b, int rows) {
+    Actuator& s = b->act;
+    s.log_rows = 0;
+    if (!s.log_on) return TINY_OK;
+    if (s.log_steps < rows) {
+        if (s.log) { HIP_TRY(b, hipStreamSynchronize(b->stream)); (void)hipFree(s.log); }
+        s.log = nullptr; s.log_steps = 0;
+        HIP_TRY(b, hipMalloc(&s.log, (size_t)rows * b->batch * b->nu * sizeof(double)));
+        s.log_steps = rows;
+    }
+    s.log_rows = rows;
+    return TINY_OK;
+}
+// (only the one-row kernel's PA forms read the blocks and the record; the coverage path reads the caller's arrays)
+int ensure_actuator_launch(TinyBatch* b, int rows, const ActuatorLaunch** out) {
+    Actuator& s = b->act;
+    if (s.kind && s.dirty) {
+        const int setups = s.kind == 1 ? 1 : b->batch;
+        const size_t total = (size_t)setups * actuator_block_doubles();
+        if (!s.built) HIP_TRY(b, hipMalloc(&s.built, total * sizeof(double)));
+        hipLaunchKernelGGL(fill_actuator_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.built, s.src[0], s.src[1], s.src[2], s.src[3], s.src[4], setups, b->nx,
+                           b->nu);
+        HIP_TRY(b, hipGetLastError());
+        s.dirty = false;
+    }
+    if (int rc = begin_actuation_log(b, rows)) return rc;
+    if (!s.desc) HIP_TRY(b, hipMalloc(&s.desc, sizeof(ActuatorLaunch)));
+    ActuatorLaunch v = {};
+    v.tab = s.kind ? reinterpret_cast<const double*>(reinterpret_cast<uintptr_t>(s.built) | (s.kind == 2 ? (uintptr_t)0 : (uintptr_t)1) | (s.lag ? (uintptr_t)2 : (uintptr_t)0)) : nullptr;
+    v.state = s.lag ? s.state : nullptr;
+    v.noise = b->anoise.seq; v.noise_steps = b->anoise.seq ? b->anoise.steps : 0;
+    v.log = s.log_on ? s.log : nullptr; v.log_step0 = actuation_step_base(b);
+    hipLaunchKernelGGL(write_actuator_launch_kernel, dim3(1), dim3(1), 0, b->stream, static_cast<ActuatorLaunch*>(s.desc), v);
+    HIP_TRY(b, hipGetLastError());
+    *out = static_cast<const ActuatorLaunch*>(s.desc);
+    return TINY_OK;
+}
+// the coverage path's actuator behind one single-step launch: one thread per (instance, input), the four stages of tiny_batch_set_actuator
+// in their stated order over the u0 of the x|u record -- what actuator_limits, actuator_lag, actuator_gain and plant_add do on the
+// one-row kernel, same bits.  Writes ua [batch][nu], which the plant and score helpers behind it read in place of u0, the lag's record
+// and the log's row.  An instance whose launch ran no iteration takes no plant step: no stage runs, its ua is never read
+static __global__ __launch_bounds__(256) void coverage_actuator_kernel(double* __restrict__ ua, double* __restrict__ state, double* __restrict__ log_row,
+                                                                       const double* __restrict__ prim, const int4* __restrict__ status, const double* __restrict__ lo,
+                                                                       const double* __restrict__ hi, const double* __restrict__ alpha, const double* __restrict__ gain,
+                                                                       const double* __restrict__ offset, int installed, int per_instance, const double* __restrict__ noise,
+                                                                       int batch, int nx, int nu, int N) {
+#pragma clang fp contract(off)
+    const size_t total = (size_t)batch * nu;
+    for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(e % nu);
+        const size_t bb = e / nu, p = per_instance ? e : (size_t)c;
+        if (status[bb].x <= 0) continue;
+        double v = prim[bb * N * (nx + nu) + nx + c];
+        if (installed) {
+            const double l = lo ? lo[p] : -__builtin_huge_val(), h = hi ? hi[p] : __builtin_huge_val();
+            v = v < l ? l : (v > h ? h : v);
+            if (alpha) {
+                const double a = state[e], d = v - a;
+                v = __builtin_fma(alpha[p], d, a);
+                state[e] = v;
+            }
+            v = __builtin_fma(v, gain ? gain[p] : 1.0, offset ? offset[p] : -0.0);
+        }
+        if (noise) v = v + noise[e];
+        ua[e] = v;
+        if (log_row) log_row[e] = v;
+    }
+}
+int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row) {
+    Actuator& s = b->act;
+    const size_t total = (size_t)b->batch * b->nu;
+    if (!s.ua) HIP_TRY(b, hipMalloc(&s.ua, total * sizeof(double)));
+    const double* noise = (b->anoise.seq && step >= 0 && step < b->anoise.steps) ? b->anoise.seq + (size_t)step * total : nullptr;
+    hipLaunchKernelGGL(coverage_actuator_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.ua, s.lag ? s.state : nullptr,
+                       (s.log_on && s.log && log_row < s.log_rows) ? s.log + (size_t)log_row * total : nullptr, b->d_prim, b->d_status, s.src[0], s.src[1],
+                       s.lag ? s.src[2] : nullptr, s.src[3], s.src[4], s.kind ? 1 : 0, s.kind == 2 ? 1 : 0, noise, b->batch, b->nx, b->nu, b->N);
     HIP_TRY(b, hipGetLastError());
     return TINY_OK;
 }
@@ -745,6 +852,8 @@ void note_instance_data_read(TinyBatch* b) {
     b->est.last = estimator_active(b);                // (likewise: the one-row kernel's PE forms, or the helper kernels around the coverage kernel)
     b->est.log_rows = 0;                              // (the estimate log is the LAST solve call's, as the state log)
     b->score.last = score_active(b);                  // (likewise: the one-row kernel's PS forms, or the helper kernel behind the coverage kernel)
+    b->act.last = actuator_active(b);                 // (likewise: the one-row kernel's PA forms, or the helper kernel behind the coverage kernel)
+    b->act.log_rows = 0;                              // (the actuation log is the LAST solve call's, as the state log)
 }
 void instance_data_settings_changed(TinyBatch* b) {
     if (b->ibox.on) b->ibox.dirty = true;             // (a disabled family is (-inf, +inf) in the array the kernels read)
@@ -975,7 +1084,7 @@ int tiny_batch_set_estimate(TinyBatch* b, const double* xp, int flags) {
         double* full = nullptr;
         hipError_t err = hipMalloc(&full, row * sizeof(double));
         int rc = TINY_OK;
-        if (err == hipSuccess) rc = expand_disturbance(b, full, fresh, 1);
+        if (err == hipSuccess) rc = expand_disturbance(b, full, fresh, 1, b->nx);
         if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);
         (void)hipFree(fresh);
         if (err != hipSuccess || rc != TINY_OK) {
@@ -1075,6 +1184,129 @@ int tiny_batch_reset_score(TinyBatch* b) {
     HIP_TRY(b, hipSetDevice(b->device));
     b->score.step = 0;
     return enqueue_zero_score(b, b->score.rec);
+}
+
+// an actuator model between the command and the plant step: lo | hi | alpha | gain | offset [batch][nu] (TINY_BROADCAST: one [nu] each),
+// any may be null, kept on the device as given; the blocks the one-row kernel reads are built from them in front of the next launch
+// (ensure_actuator_launch).  Installing a lag where none was installed zeroes its record; replacing the setup keeps it.  Everything that
+// can fail -- the limits' check among it -- happens before anything installed is touched
+int tiny_batch_set_actuator(TinyBatch* b, const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    Actuator& s = b->act;
+    if (flags & ~(TINY_DEVICE | TINY_BROADCAST)) return fail(b, TINY_ERR_ARG, "actuator: flags 0x%x (TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST)", flags);
+    if (!lo && !hi && !alpha && !gain && !offset) {                      // remove: freed once the stream has run dry of its readers (the log goes with it)
+        if (int rc = drop_buffers(b, s)) return rc;
+        s.kind = 0; s.lag = false; s.dirty = false; s.log_steps = 0; s.log_rows = 0;
+        return TINY_OK;
+    }
+    const size_t doubles = ((flags & TINY_BROADCAST) ? 1 : (size_t)b->batch) * b->nu;
+    const UploadPart given[5] = {{lo, doubles}, {hi, doubles}, {alpha, doubles}, {gain, doubles}, {offset, doubles}};
+    double* fresh[5];
+    if (int rc = upload_fresh(b, given, fresh, 5, flags, "actuator setup")) return rc;
+    auto give_up = [&](int rc) { for (double* p : fresh) if (p) (void)hipFree(p); return rc; };
+    if (lo && hi) {                                                      // (read back: the arrays may be the device's)
+        std::vector<double> l(doubles), h(doubles);
+        if (hipMemcpy(l.data(), fresh[0], doubles * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(h.data(), fresh[1], doubles * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return give_up(fail(b, TINY_ERR_HIP, "actuator setup: the limits could not be read back"));
+        }
+        for (size_t i = 0; i < doubles; ++i)
+            if (l[i] > h[i]) return give_up(fail(b, TINY_ERR_ARG, "actuator: lo > hi at input %d of setup %zu", (int)(i % b->nu), i / b->nu));
+    }
+    double* state = s.state;
+    if (alpha && !s.lag) {                                               // a lag where none was installed: its record starts at zero
+        if (state) { (void)hipFree(state); state = nullptr; }
+        hipError_t err = hipMalloc(&state, (size_t)b->batch * b->nu * sizeof(double));
+        if (err == hipSuccess) err = hipMemsetAsync(state, 0, (size_t)b->batch * b->nu * sizeof(double), b->stream);
+        if (err != hipSuccess) { (void)hipGetLastError(); if (state) (void)hipFree(state); s.state = nullptr; return give_up(fail(b, TINY_ERR_HIP, "actuator state: %s", hipGetErrorString(err))); }
+    }
+    for (int i = 0; i < 5; ++i) { if (s.src[i]) (void)hipFree(s.src[i]); s.src[i] = fresh[i]; }
+    if (s.built) (void)hipFree(s.built);                                 // (its size follows the kind)
+    s.built = nullptr; s.state = state;
+    s.kind = (flags & TINY_BROADCAST) ? 1 : 2;
+    s.lag = alpha != nullptr; s.dirty = true;
+    return TINY_OK;
+}
+// the setup instance `instance` is actuated by, as set, defaults filled in (alpha reads 1 with no lag); any output may be null
+int tiny_batch_get_actuator(TinyBatch* b, int instance, double* lo, double* hi, double* alpha, double* gain, double* offset) {
+    if (!b) return TINY_ERR_NULL;
+    const Actuator& s = b->act;
+    if (!s.kind) return fail(b, TINY_ERR_ARG, "no actuator installed");
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    double* const out[5] = {lo, hi, alpha, gain, offset};
+    const double none[5] = {-std::numeric_limits<double>::infinity(), std::numeric_limits<double>::infinity(), 1.0, 1.0, -0.0};
+    for (int i = 0; i < 5; ++i) {
+        if (!out[i]) continue;
+        if (!s.src[i]) { std::fill(out[i], out[i] + b->nu, none[i]); continue; }
+        if (int rc = read_instance(b, out[i], s.src[i], s.kind == 2 ? instance : 0, b->nu)) return rc;
+    }
+    return TINY_OK;
+}
+// the lag's record a [batch][nu] (TINY_BROADCAST: [nu]); TINY_ERR_ARG with no lag installed
+int tiny_batch_set_actuator_state(TinyBatch* b, const double* a, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->act.kind || !b->act.lag) return fail(b, TINY_ERR_ARG, "no actuator lag installed (tiny_batch_set_actuator with alpha)");
+    if (!a) return fail(b, TINY_ERR_ARG, "null actuator state");
+    if (flags & ~(TINY_DEVICE | TINY_BROADCAST)) return fail(b, TINY_ERR_ARG, "actuator state: flags 0x%x (TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST)", flags);
+    HIP_TRY(b, hipSetDevice(b->device));
+    const hipMemcpyKind kind = (flags & TINY_DEVICE) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (!(flags & TINY_BROADCAST)) {
+        HIP_TRY(b, hipMemcpyAsync(b->act.state, a, (size_t)b->batch * b->nu * sizeof(double), kind, b->stream));
+    } else {                                                             // one row for all: staged and expanded, as a broadcast sequence of one step
+        double* stage = nullptr;
+        HIP_TRY(b, hipMalloc(&stage, (size_t)b->nu * sizeof(double)));
+        hipError_t err = hipMemcpyAsync(stage, a, (size_t)b->nu * sizeof(double), kind, b->stream);
+        int rc = TINY_OK;
+        if (err == hipSuccess) rc = expand_disturbance(b, b->act.state, stage, 1, b->nu);
+        if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);
+        (void)hipFree(stage);
+        if (rc != TINY_OK) return rc;
+        if (err != hipSuccess) { (void)hipGetLastError(); return fail(b, TINY_ERR_HIP, "actuator state: %s", hipGetErrorString(err)); }
+        return TINY_OK;
+    }
+    HIP_TRY(b, hipStreamSynchronize(b->stream));                         // (the caller may free its array)
+    return TINY_OK;
+}
+int tiny_batch_get_actuator_state(TinyBatch* b, double* a_out) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->act.kind || !b->act.lag) return fail(b, TINY_ERR_ARG, "no actuator lag installed (tiny_batch_set_actuator with alpha)");
+    if (!a_out) return fail(b, TINY_ERR_ARG, "null output");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(a_out, b->act.state, (size_t)b->batch * b->nu * sizeof(double), hipMemcpyDeviceToHost));
+    return TINY_OK;
+}
+// actuation noise: the applied control of MPC step k takes fl(g + n[k][i]) for its last stage; the disturbance setter's rules, width nu
+int tiny_batch_set_actuation_noise(TinyBatch* b, const double* n, int n_steps, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    return install_sequence(b, b->anoise, n, n_steps, flags, "actuation noise", "actuation noise", b->nu);
+}
+int tiny_batch_get_actuation_noise(TinyBatch* b, int step, int instance, double* n_out) {
+    if (!b) return TINY_ERR_NULL;
+    return read_sequence_row(b, b->anoise, step, instance, n_out, "no actuation-noise sequence installed", b->nu);
+}
+// ... generated on the device from a seed (noise_gen.hpp): stream 2, rows of nu entries
+int tiny_batch_generate_actuation_noise(TinyBatch* b, const TinyNoiseSpec* spec) {
+    if (!b) return TINY_ERR_NULL;
+    return install_generated(b, b->anoise, spec, 2, "generated actuation noise", b->nu);
+}
+// ... and its rows on the host, no GPU touched: out [n_steps][batch][nu] exactly as the device fills them
+int tiny_actuation_noise_generate(const TinyNoiseSpec* spec, int batch, int nu, double* out) {
+    if (noise_spec_refusal(spec, nu) || (spec->flags & TINY_DEVICE) || !out || batch <= 0 || nu <= 0) return TINY_ERR_ARG;
+    std::vector<double> g((size_t)2 * noise_pairs(nu));
+    noise_fill_host(noise_fill_of(spec, 2, batch, nu, spec->scale, spec->mean), out, g.data());
+    return TINY_OK;
+}
+// the applied control of every MPC step of the last solve call (option "actuation_log"): ua [steps][batch][nu]
+int tiny_batch_get_actuation_log(TinyBatch* b, double* ua, int steps) {
+    if (!b) return TINY_ERR_NULL;
+    if (steps <= 0 || steps > b->act.log_rows || !b->act.log) return fail(b, TINY_ERR_ARG, "no actuation log recorded (set_option actuation_log; an actuator or actuation noise; advance_x0 or steps_per_launch)");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    if (ua) HIP_TRY(b, hipMemcpy(ua, b->act.log, (size_t)steps * b->batch * b->nu * sizeof(double), hipMemcpyDeviceToHost));
+    return TINY_OK;
 }
 
 // every instance its own half-spaces, set 0 (static) or 1 (time-varying).  The caller's arrays are kept on the device as given; what

@@ -339,11 +339,12 @@ int tiny_group_set_instance_cone_coefficients(TinyGroup* g, const double* cx, co
 }
 // every instance its own disturbance at the plant step: w [n_steps][batch][nx] over the full batch axis in host memory, the caller's
 // instance order; each shard gets [n_steps][its count][nx] (TINY_BROADCAST: the one sequence, as it is); NULL / n_steps <= 0 removes
-static int group_set_sequence(TinyGroup* g, const double* w, int n_steps, int flags, int (*set)(TinyBatch*, const double*, int, int), const char* what) {
+static int group_set_sequence(TinyGroup* g, const double* w, int n_steps, int flags, int (*set)(TinyBatch*, const double*, int, int), const char* what,
+                              bool input_rows = false) {
     if (!g) return TINY_ERR_NULL;
     if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "%s of a group: host arrays (TINY_HOST)", what);
     const bool pass = !w || n_steps <= 0 || (flags & TINY_BROADCAST);
-    const size_t nx = (size_t)g->nx;
+    const size_t nx = input_rows ? (size_t)g->nu : (size_t)g->nx;      // (the row's width: the actuation noise has rows of nu entries)
     for (int k = 0; k < g->n; ++k) {
         if (!pass) {
             const size_t cnt = (size_t)g->count[k];
@@ -367,12 +368,12 @@ int tiny_group_set_measurement_noise(TinyGroup* g, const double* v, int n_steps,
 // the same sequences generated on the shards' devices (tiny_batch_generate_disturbance / ..._measurement_noise): id_base / id_stride name
 // the CALLER-order instance, so shard k gets id_base + first * id_stride (contiguous shards) or id_base + k * id_stride with the stride
 // id_stride * n (round-robin), and its slice of per-instance scale / mean: the noise of an instance does not depend on the sharding
-static int group_generate(TinyGroup* g, const TinyNoiseSpec* spec, int (*gen)(TinyBatch*, const TinyNoiseSpec*), const char* what) {
+static int group_generate(TinyGroup* g, const TinyNoiseSpec* spec, int (*gen)(TinyBatch*, const TinyNoiseSpec*), const char* what, bool input_rows = false) {
     if (!g) return TINY_ERR_NULL;
     if (!spec) return gfail(g, TINY_ERR_ARG, "%s of a group: null spec", what);
     if (spec->flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "%s of a group: host arrays (TINY_HOST)", what);
     const bool pass = (spec->flags & TINY_BROADCAST) != 0;
-    const size_t nx = (size_t)g->nx;
+    const size_t nx = input_rows ? (size_t)g->nu : (size_t)g->nx;
     std::vector<double> stage[2];
     for (int k = 0; k < g->n; ++k) {
         TinyNoiseSpec mine = *spec;
@@ -446,6 +447,33 @@ int tiny_group_set_score(TinyGroup* g, const double* weight, const double* targe
         if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
     }
     return TINY_OK;
+}
+// an actuator model (tiny_batch_set_actuator, tiny_batch_set_actuator_state): lo | hi | alpha | gain | offset and a, [batch][nu] each over
+// the full batch axis in host memory, the caller's instance order; each shard gets its instances' rows (TINY_BROADCAST: the one setup, as
+// it is); all five NULL removes.  The actuation noise (tiny_batch_set_actuation_noise, tiny_batch_generate_actuation_noise): the
+// disturbance's layout with rows of nu entries, gathered and generated the same way
+int tiny_group_set_actuator(TinyGroup* g, const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "actuator of a group: host arrays (TINY_HOST)");
+    const bool pass = (!lo && !hi && !alpha && !gain && !offset) || (flags & TINY_BROADCAST);
+    const double* src[5] = {lo, hi, alpha, gain, offset};
+    std::vector<double> stage[5];
+    for (int k = 0; k < g->n; ++k) {
+        const double* from[5] = {lo, hi, alpha, gain, offset};
+        if (!pass) for (int a = 0; a < 5; ++a) from[a] = src[a] ? shard_slice(g, k, src[a], (size_t)g->nu, &stage[a]) : nullptr;
+        const int rc = tiny_batch_set_actuator(g->shard[k], from[0], from[1], from[2], from[3], from[4], pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
+int tiny_group_set_actuator_state(TinyGroup* g, const double* a, int flags) {
+    return group_set_rows(g, a, g ? (size_t)g->nu : 0, flags, tiny_batch_set_actuator_state, "actuator state");
+}
+int tiny_group_set_actuation_noise(TinyGroup* g, const double* n, int n_steps, int flags) {
+    return group_set_sequence(g, n, n_steps, flags, tiny_batch_set_actuation_noise, "actuation noise", true);
+}
+int tiny_group_generate_actuation_noise(TinyGroup* g, const TinyNoiseSpec* spec) {
+    return group_generate(g, spec, tiny_batch_generate_actuation_noise, "generated actuation noise", true);
 }
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,

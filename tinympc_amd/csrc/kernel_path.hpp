@@ -44,6 +44,7 @@ struct PathFacts {
     bool measurement = false;           // a measurement-noise sequence is installed AND the launch takes a plant step
     bool estimator = false;             // a state estimator is installed AND the launch takes a plant step
     bool score = false;                 // a closed-loop score is installed AND the launch takes a plant step
+    bool actuator = false;              // an actuator model or an actuation-noise sequence is installed AND the launch takes a plant step
 };
 
 // what path_facts can produce: the sweep of tests/dropin/kernel_path_driver.cpp counts these combinations only
@@ -67,6 +68,8 @@ enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIV
 // (the closed-loop score's, the next value and the next one reported: a constant behind the enumeration, whose closing line
 // tests/test_estimator_cpu.py pins; 11 lies within the enumeration's range)
 constexpr PathRefusal REFUSE_ADAPTIVE_SCORE = static_cast<PathRefusal>(REFUSE_ADAPTIVE_ESTIMATOR + 1);
+// (... and the actuator model's behind it, the last one reported)
+constexpr PathRefusal REFUSE_ADAPTIVE_ACTUATOR = static_cast<PathRefusal>(REFUSE_ADAPTIVE_SCORE + 1);
 constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
@@ -86,8 +89,9 @@ constexpr const char* PATH_REFUSAL_STATE_LOG = "adaptive rho does not combine wi
 constexpr const char* PATH_REFUSAL_MEASUREMENT = "adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)";
 constexpr const char* PATH_REFUSAL_ESTIMATOR = "adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)";
 constexpr const char* PATH_REFUSAL_SCORE = "adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)";
+constexpr const char* PATH_REFUSAL_ACTUATOR = "adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)";
 inline const char* path_refusal_message(PathRefusal r) {
-    return r == REFUSE_ADAPTIVE_SCORE ? PATH_REFUSAL_SCORE : r == REFUSE_ADAPTIVE_ESTIMATOR ? PATH_REFUSAL_ESTIMATOR : r == REFUSE_ADAPTIVE_MEASUREMENT ? PATH_REFUSAL_MEASUREMENT : r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
+    return r == REFUSE_ADAPTIVE_ACTUATOR ? PATH_REFUSAL_ACTUATOR : r == REFUSE_ADAPTIVE_SCORE ? PATH_REFUSAL_SCORE : r == REFUSE_ADAPTIVE_ESTIMATOR ? PATH_REFUSAL_ESTIMATOR : r == REFUSE_ADAPTIVE_MEASUREMENT ? PATH_REFUSAL_MEASUREMENT : r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
 }
 
 struct PathDecision {
@@ -102,6 +106,7 @@ struct PathDecision {
     int pm = 0;                    // ONE_ROW: the form that solves from a measured state (likewise; always with pp)
     int pe = 0;                    // ONE_ROW: the form with a state estimator in front of the solve (likewise; always with pm and pp)
     int ps = 0;                    // ONE_ROW: the form that scores what the plant step hands on (likewise; always with pd or pp)
+    int pa = 0;                    // ONE_ROW: the form with an actuator model between the command and the plant step (likewise; always with pp)
 };
 
 // a one-row kernel exists for the shape: compiled in (counted even under no_jit), or one that run-time instantiation can make
@@ -125,9 +130,10 @@ inline PathDecision decide_path(const PathFacts& f) {
                                 : f.measurement    ? REFUSE_ADAPTIVE_MEASUREMENT
                                 : f.estimator      ? REFUSE_ADAPTIVE_ESTIMATOR
                                 : f.score          ? REFUSE_ADAPTIVE_SCORE
+                                : f.actuator       ? REFUSE_ADAPTIVE_ACTUATOR
                                                    : REFUSE_NONE;
-    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0}; };
-    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0}; };
+    auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
+    auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
     // every instance its own disturbance at the plant step: ONE rule pair, applied to whatever one-row answer the rules below give --
     // the PD form of that very form (PB, PL and PC forms take the bit as well and keep their rule's name; every other one-row answer
     // is "one_row:pd"), run-time instantiated only, so where hipRTC may not be tried, with debug outputs, under force_general and with
@@ -141,14 +147,17 @@ inline PathDecision decide_path(const PathFacts& f) {
     // and the true one is stepped apart from it, so the fact forces pm and pp on: with no noise sequence the launch binds an empty one
     // A closed-loop score: the same rule pair, "one_row:ps" / "cover:ps" -- the PS form of that very form.  It is written where the PD and
     // PP forms hand a state on: with neither installed it rides on the PD form with an empty sequence, as the state log does
+    // An actuator model: the same rule pair, "one_row:pa" / "cover:pa" -- the PA form of that very form.  The plant step must be a chain
+    // over the APPLIED control, not the solver's own x1, so the fact forces pp on: with no plant installed the launch forms the block
+    // from the model, as under measurement noise
     const bool pd_form = f.fits && hiprtc && !f.force_general && !f.debug && !f.adaptive;
-    const bool pe = f.estimator, pm = f.measurement || pe, pp = f.plant || pm, pd = f.disturbance || ((f.state_log || f.score) && !pp);
+    const bool pe = f.estimator, pm = f.measurement || pe, pa = f.actuator, pp = f.plant || pm || pa, pd = f.disturbance || ((f.state_log || f.score) && !pp);
     const bool ps = f.score;
     auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) {
-        if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0, 0, 0};
-        if (!pd_form) return cover(ps ? "cover:ps" : pe ? "cover:pe" : pm ? "cover:pm" : pp ? "cover:pp" : "cover:pd");
-        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : ps ? "one_row:ps" : pe ? "one_row:pe" : pm ? "one_row:pm" : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0,
-                            pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0};
+        if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0, 0, 0, 0};
+        if (!pd_form) return cover(pa ? "cover:pa" : ps ? "cover:ps" : pe ? "cover:pe" : pm ? "cover:pm" : pp ? "cover:pp" : "cover:pd");
+        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : pa ? "one_row:pa" : ps ? "one_row:ps" : pe ? "one_row:pe" : pm ? "one_row:pm" : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0,
+                            pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0, pa ? 1 : 0};
     };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
@@ -163,7 +172,7 @@ inline PathDecision decide_path(const PathFacts& f) {
     // half-space / EXT forms and every form of a shape outside tile_dims.txt are run-time instantiated; EXT forms are for the shapes
     // the one-row kernel does not hold)
     const bool ext = f.tile_ext || f.hetero;
-    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log && !f.measurement && !f.estimator && !f.score &&
+    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log && !f.measurement && !f.estimator && !f.score && !f.actuator &&
                           !((f.tile_is_jit || f.soc || lf || ext) && (f.no_jit || f.tile_soc_failed)) && !(ext && regs);
 
     // ---- the rules, in order
@@ -200,7 +209,7 @@ inline PathDecision decide_path(const PathFacts& f) {
 }
 
 // tiny_batch_kernel_path: 0 the one-row kernel, compiled in; 1 the tile kernel; 2 the coverage kernel; 3 the one-row kernel, instantiated at
-// run time (every form with a per-instance box, half-space set, cone coefficients, disturbance, plant, measurement noise, state estimator or closed-loop score is); 4 the tile kernel, instantiated at run time
+// run time (every form with a per-instance box, half-space set, cone coefficients, disturbance, plant, measurement noise, state estimator, closed-loop score or actuator model is); 4 the tile kernel, instantiated at run time
 inline int kernel_path_code(const PathDecision& d, const PathFacts& f) {
     if (d.kernel == TILE) return f.tile_is_jit ? 4 : 1;
     if (d.kernel == COVERAGE) return 2;

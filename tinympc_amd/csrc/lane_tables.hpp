@@ -208,4 +208,20 @@ __host__ __device__ inline double score_entry(const double* weight, const double
     return (in && hi) ? hi[lane] : __builtin_huge_val();
 }
 
+// ---- an actuator model's setup (tiny_batch_set_actuator): what entry (row r, lane) of an actuator block [lo | hi | alpha | gain | offset]
+// [16 lanes] holds (ActuatorLaunch::tab).  The lanes are the row's: input c sits on lane nx + c, where the one-row kernel keeps u0.  A null
+// array and every lane outside the inputs are neutral: lo -inf, hi +inf, alpha 1, gain 1, offset -0.0 (fma(m, 1, -0.0) is m for every m,
+// the sign of a zero included)
+__host__ __device__ constexpr int actuator_block_doubles() { return 5 * 16; }
+__host__ __device__ inline double actuator_entry(const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int nx, int nu, int r,
+                                                 int lane) {
+    const int c = lane - nx;
+    const bool in = c >= 0 && c < nu;
+    if (r == 0) return (in && lo) ? lo[c] : -__builtin_huge_val();
+    if (r == 1) return (in && hi) ? hi[c] : __builtin_huge_val();
+    if (r == 2) return (in && alpha) ? alpha[c] : 1.0;
+    if (r == 3) return (in && gain) ? gain[c] : 1.0;
+    return (in && offset) ? offset[c] : -0.0;
+}
+
 }  // namespace tinympc_amd

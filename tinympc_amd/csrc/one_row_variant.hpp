@@ -20,10 +20,11 @@ struct JitKey {
     int pm = 0;               // the solve runs from a measured state, the plant from the true one (admm_kernel.hip.h PM): run-time instantiated only, with pp
     int pe = 0;               // a state estimator between the measurement and the solve (admm_kernel.hip.h PE): run-time instantiated only, with pm and pp
     int ps = 0;               // a closed-loop score at the plant step (admm_kernel.hip.h PS): run-time instantiated only, with pd or pp
+    int pa = 0;               // an actuator model between the command and the plant step (admm_kernel.hip.h PA): run-time instantiated only, with pp
     bool operator<(const JitKey& o) const {
-        const int a[19] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd, pp, pm, pe, ps},
-                  b[19] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd, o.pp, o.pm, o.pe, o.ps};
-        for (int i = 0; i < 19; ++i)
+        const int a[20] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd, pp, pm, pe, ps, pa},
+                  b[20] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd, o.pp, o.pm, o.pe, o.ps, o.pa};
+        for (int i = 0; i < 20; ++i)
             if (a[i] != b[i]) return a[i] < b[i];
         return false;
     }
@@ -79,6 +80,7 @@ struct VariantFacts {
     bool pm = false;                   // the measured-state form: bit 7, always with bit 6
     bool pe = false;                   // the state-estimator form: bit 8, always with bits 7 and 6
     bool ps = false;                   // the closed-loop-score form: bit 9, always with bit 5 or bit 6
+    bool pa = false;                   // the actuator-model form: bit 10, always with bit 6
     // ---- from the problem
     bool soc = false, debug = false;
     int dpp_mode = 0;                  // option "dpp_mode" as set (values outside 0..2 count as 0)
@@ -119,7 +121,8 @@ inline bool variant_facts_consistent(const VariantFacts& f, const EntrySlots& s)
            !((f.pd || f.pp) && (f.debug || f.adaptive || f.no_jit || f.variant_jit_failed)) &&     // (decide_path: a PD / PP form only where hipRTC may be tried)
            !(f.pm && !f.pp) &&                                                                     // (... and a PM form is a PP form)
            !(f.pe && !f.pm) &&                                                                     // (... and a PE form is a PM form)
-           !(f.ps && !(f.pd || f.pp));                                                             // (... and a PS form is a PD or a PP form)
+           !(f.ps && !(f.pd || f.pp)) &&                                                           // (... and a PS form is a PD or a PP form)
+           !(f.pa && !f.pp);                                                                       // (... and a PA form is a PP form)
 }
 
 struct VariantChoice {
@@ -156,7 +159,7 @@ inline VariantChoice choose_one_row_variant(const VariantFacts& f, const EntrySl
     // (the PD form of whatever the key is by now -- full rows, no PREFETCH slot --, on the UB form where the compiled-in rungs below would
     // take one: their conditions, asked of the key, since no rung is)
     if (f.pd || f.pp) {                                                  // (PP: PD's rule, bit for bit)
-        k.pd = f.pd ? 1 : 0; k.pp = f.pp ? 1 : 0; k.pm = (f.pp && f.pm) ? 1 : 0; k.pe = (k.pm && f.pe) ? 1 : 0; k.ps = f.ps ? 1 : 0;
+        k.pd = f.pd ? 1 : 0; k.pp = f.pp ? 1 : 0; k.pm = (f.pp && f.pm) ? 1 : 0; k.pe = (k.pm && f.pe) ? 1 : 0; k.ps = f.ps ? 1 : 0; k.pa = (f.pp && f.pa) ? 1 : 0;
         if (!k.pb && !k.pc && !k.lin && !k.adapt && !dbg && k.mode == 2) k.ub = (f.uniform_ub && (!f.hetero || f.het_ub)) ? 1 : 0;
     }
     SlotRef want;

@@ -3,7 +3,7 @@
 the plant a PP form solves exactly the problems the form without it solves (bit for bit under the default dpp_mode), so the times differ
 by what the PP form costs -- and what the host-in-the-loop form it replaces costs.  Launch times from the library's "timing" option
 (device events around the launches of a solve); the host form is wall clock, read-backs and upload included.
-    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A|generated|host [--noise-form diagonal|factor]] [--estimator G [--estimator-shared 1]] [--score device|host] [--package DIR] [--launches L] [--batch 65536]
+    python tools/plant_bench.py --workload rocket|hover --plant none|shared|own|host --steps N [--noise A|generated|host [--noise-form diagonal|factor]] [--estimator G [--estimator-shared 1]] [--score device|host] [--actuator neutral|device|host] [--package DIR] [--launches L] [--batch 65536]
 --workload rocket   BASELINE config 4 as tools/disturbance_bench.py runs it: (6,3,10), box and thrust cone, the closed loop along the
                     reference trajectory.  --steps 90: the fused episode; --steps 1: one warm step per launch (advance_x0)
 --workload hover    the headline shape as bench.py sets it up: (12,4,10) quadrotor hover; --steps 20: fused launches of 20 MPC steps
@@ -34,6 +34,15 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
 --score host        what it took before: nothing installed, "state_log" and "step_log" on, both logs pulled to the host after the
                     episode and scored there in numpy (the same arithmetic, vectorised over the instances); wall_ms is the episode with all
                     of that.  Both need --steps > 1
+--actuator neutral  an actuator model installed (tiny_batch_set_actuator) that changes nothing: every instance its own gain of ones, no other
+                    stage.  The applied control is the command bit for bit, so a PA form solves exactly the problems the same form without
+                    it solves (--plant shared: the PP form; with --noise 0 --estimator G --score device: the PE + PS form), and the times
+                    differ by what the PA form costs (profiles/actuator.md)
+--actuator device   the whole model per instance: limits at 0.8 of the workload's input box, a lag (alpha 0.7), a gain of 0.9 and a noise
+                    sequence generated on the device (1 % of the box), the counter rewound per episode; with --score device wall_ms is the
+                    episode with its four arrays read back
+--actuator host     what it took before (with --plant host): per MPC step one single-step solve, the same four stages, the plant step and
+                    the cost in numpy, set_x0; wall clock per episode
 Prints one JSON line: the median, minimum and maximum time in ms over the timed launches (episodes), the iterations accumulated and
 the read-backs that say which form ran.  profiles/plant.md is where the numbers go."""
 import argparse
@@ -61,6 +70,7 @@ def main():
     ap.add_argument("--estimator", type=float, default=None, help="a state estimator with the gain G * I per instance")
     ap.add_argument("--estimator-shared", type=int, default=0, help="1: ONE gain for all (TINY_BROADCAST) instead of [batch] copies")
     ap.add_argument("--score", choices=("device", "host"), default=None, help="a closed-loop score on the device, or both logs pulled and scored in numpy")
+    ap.add_argument("--actuator", choices=("neutral", "device", "host"), default=None, help="an actuator model: one that changes nothing, the whole model, or its stages in numpy (with --plant host)")
     a = ap.parse_args()
     noise_source = a.noise if a.noise in ("generated", "host") else None
     a.noise = None if (a.noise is None or noise_source) else float(a.noise)
@@ -106,17 +116,31 @@ def main():
     f = np.zeros(nx) if prob.get("f") is None else np.asarray(prob["f"], dtype=float).reshape(nx)
     launches = a.launches or (5 if a.steps > 1 or a.plant == "host" else 50)
     ms = []
+    box = m if a.workload == "rocket" else h
+    act_lo, act_hi = 0.8 * float(np.min(box["u_min"])) * np.ones((B, nu)), 0.8 * float(np.max(box["u_max"])) * np.ones((B, nu))
+    act_alpha, act_gain, act_scale = np.full((B, nu), 0.7), np.full((B, nu), 0.9), 0.01 * float(np.max(box["u_max"])) * np.ones(nu)
     if a.plant == "host":
+        host_cost = None
         for e in range(1 + launches):
             start()
             s.synchronize()
             t0 = time.perf_counter()
-            for _ in range(a.steps):
+            if a.actuator == "host":
+                a_state, host_cost = np.zeros((B, nu)), np.zeros(B)
+                rows = np.random.default_rng(7).standard_normal((a.steps, B, nu)) * act_scale
+            for k in range(a.steps):
                 x0h = s.get("x0")
                 s.solve()
                 u0 = s.get("u")[:, :, 0]
                 s.get("x")                                # (the read-back a host-side plant that also looks at the prediction pays)
-                s.set_x0(x0h @ A.T + u0 @ Bm.T + f)
+                if a.actuator == "host":
+                    lim = np.where(u0 < act_lo, act_lo, np.where(u0 > act_hi, act_hi, u0))
+                    a_state = act_alpha * (lim - a_state) + a_state
+                    u0 = a_state * act_gain + rows[k]
+                xn = x0h @ A.T + u0 @ Bm.T + f
+                if a.actuator == "host":
+                    host_cost += np.sum(xn * xn, axis=1) + np.sum(u0 * u0, axis=1)
+                s.set_x0(xn)
             s.synchronize()
             if e >= 1:
                 ms.append(1e3 * (time.perf_counter() - t0))
@@ -157,6 +181,11 @@ def main():
                         install[k].append(1e3 * v)
         if a.estimator is not None:
             s.set_estimator(a.estimator * np.eye(nx) if a.estimator_shared else np.ascontiguousarray(np.broadcast_to(a.estimator * np.eye(nx), (B, nx, nx))))
+        if a.actuator == "neutral":
+            s.set_actuator(gain=np.ones((B, nu)))
+        elif a.actuator == "device":
+            s.set_actuator(act_lo, act_hi, act_alpha, act_gain)
+            s.generate_actuation_noise(7, a.steps if a.steps > 1 else a.warmup + launches, act_scale)
         wall, scored = [], None
         if a.score is not None:
             lim = m if a.workload == "rocket" else h
@@ -194,6 +223,9 @@ def main():
                     s.set_option("measurement_step", 0)
                 if noise_source:
                     s.set_option("disturbance_step", 0)
+                if a.actuator == "device":
+                    s.set_option("actuation_step", 0)
+                    s.set_actuator_state(np.zeros(nu))
                 if a.estimator is not None:
                     s.set_estimate(s.get("x0"))
                 s.set_option("timing", 1)
@@ -239,6 +271,13 @@ def main():
             out.update(disturbance_generated=int(s.get_option("disturbance_generated")))
     if a.estimator is not None:
         out.update(estimator_gain=a.estimator, estimator=int(s.get_option("estimator")), last_estimator=int(s.get_option("last_estimator")))
+    if a.actuator is not None and a.plant != "host":
+        out.update(actuator=a.actuator, actuator_kind=int(s.get_option("actuator")), actuator_lag=int(s.get_option("actuator_lag")), last_actuator=int(s.get_option("last_actuator")),
+                   actuation_noise=int(s.get_option("actuation_noise")))
+        if wall:
+            out.update(wall_median_ms=float(np.median(wall)), wall_min_ms=float(min(wall)), wall_max_ms=float(max(wall)))
+    if a.actuator == "host":
+        out.update(actuator="host", host_cost_median=float(np.median(host_cost)))
     if a.score is not None and a.steps > 1:
         out.update(score=a.score, score_kind=int(s.get_option("score")), last_score=int(s.get_option("last_score")), wall_median_ms=float(np.median(wall)), wall_min_ms=float(min(wall)),
                    wall_max_ms=float(max(wall)), cost_median=float(np.median(scored[0])), violated_share=float(np.mean(scored[2] > 0)))

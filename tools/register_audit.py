@@ -3,7 +3,8 @@
 (hipcc -Rpass-analysis=kernel-resource-usage on tinympc_amd/csrc/_gen/{k,t}_*.hip).  Scratch > 0 = spilled to memory.
 The one-row forms csrc/jit_prebuilt.txt names (run-time instantiated, never in a unit) are compiled here as explicit instantiations and
 listed after the compiled-in ones; then the setup kernels of batch_dispatch.hip (riccati_kernel, sensitivity_kernel) and, last, the helper
-kernels of batch_instance.hip (the fill kernels of the per-instance data and of the generated noise, the coverage path's helpers).
+kernels of batch_instance.hip (the fill kernels of the per-instance data and of the generated noise, the coverage path's helpers -- fill_actuator_kernel,
+write_actuator_launch_kernel and coverage_actuator_kernel of the actuator model among them).
     python tools/register_audit.py [--all] > profiles/rNN_register_audit.md"""
 import concurrent.futures
 import glob
@@ -54,7 +55,8 @@ def setup_kernel_rows():
 
 
 def helper_kernel_rows():
-    """every __global__ of batch_instance.hip: fill kernels (generate_diagonal_kernel / generate_factor_kernel among them) and coverage helpers"""
+    """every __global__ of batch_instance.hip: fill kernels (generate_diagonal_kernel / generate_factor_kernel, fill_actuator_kernel among them) and
+    coverage helpers (coverage_actuator_kernel: the actuator model behind a coverage launch)"""
     return usage("batch_instance.hip", cwd=CSRC, extra=("--cuda-device-only",))
 
 
