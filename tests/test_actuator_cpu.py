@@ -238,9 +238,11 @@ def test_path_rules_under_an_actuator(driver):
     assert p.returncode == 0 and p.stdout.splitlines() == [
         "11 adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)",
         "12 adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)"], p.stdout
-    text = open(os.path.join(CSRC, "kernel_path.hpp")).read()
-    assert "REFUSE_ADAPTIVE_ACTUATOR = static_cast<PathRefusal>(REFUSE_ADAPTIVE_SCORE + 1)" in text               # the value behind the score's
-    assert text.index(": f.score          ? REFUSE_ADAPTIVE_SCORE") < text.index(": f.actuator       ? REFUSE_ADAPTIVE_ACTUATOR") < text.index(": REFUSE_NONE;")   # reported last
+    # the value behind the score's, and reported last: with the score (or any earlier fact) on as well, the earlier refusal is answered;
+    # with the actuator alone its own; with no such fact none
+    order = _lines(driver, "path", "".join(" ".join("%s=%d" % kv for kv in dict(fits_box=1, fits=1, adaptive=1, **on).items()) + "\n"
+                                           for on in (dict(actuator=1), dict(actuator=1, score=1), dict(actuator=1, score=1, estimator=1), dict(score=1), {})))
+    assert [int(g["refusal"]) for g in order] == [12, 11, 10, 11, 0]
 
 
 def test_path_and_variant_sweeps_follow_the_plants_rule(driver):

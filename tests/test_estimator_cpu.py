@@ -182,8 +182,10 @@ def test_path_rules_under_an_estimator(driver):
     assert p.returncode == 0 and p.stdout.splitlines() == [
         "9 adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)",
         "10 adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)"], p.stdout
-    text = open(os.path.join(CSRC, "kernel_path.hpp")).read()
-    assert "REFUSE_ADAPTIVE_STATE_LOG, REFUSE_ADAPTIVE_MEASUREMENT, REFUSE_ADAPTIVE_ESTIMATOR }" in text      # appended behind the measurement's
+    # appended behind the measurement's: the next value, and with both facts on (or any earlier one) the earlier refusal is answered
+    both = _lines(driver, "path", "".join(" ".join("%s=%d" % kv for kv in dict(BOX, adaptive=1, **on).items()) + "\n"
+                                          for on in ({}, dict(measurement=1), dict(state_log=1, measurement=1))))
+    assert [int(g["refusal"]) for g in both] == [10, 9, 8]
 
 
 def test_path_and_variant_sweeps_follow_the_measurements_rule(driver):

@@ -231,7 +231,17 @@ MESSAGES = ["",
             "kernel, which does not take adaptive rho",
             "adaptive rho does not combine with heterogeneous data / half-spaces / one_shot / repack_after",
             "overlapping cones run on the coverage kernel: no adaptive rho with them",
-            "adaptive rho needs the register-resident kernel (nx+nu <= 16, horizon within the register file)"]
+            "adaptive rho needs the register-resident kernel (nx+nu <= 16, horizon within the register file)",
+            # ... and the eight that came with the per-instance cone coefficients and the closed-loop stages, indexed by their refusal
+            "adaptive rho does not combine with per-instance cone coefficients (tiny_batch_set_instance_cone_coefficients): the adaptive cone form has no per-instance "
+            "coefficients, and the coverage kernel does not take adaptive rho",
+            "adaptive rho does not combine with a per-instance disturbance",
+            "adaptive rho does not combine with a plant of its own at the plant step (tiny_batch_set_plant)",
+            "adaptive rho does not combine with the state log (option state_log)",
+            "adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)",
+            "adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)",
+            "adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)",
+            "adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)"]
 
 
 def test_refusals_in_their_order_and_their_messages(driver, ask):

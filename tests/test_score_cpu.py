@@ -189,8 +189,10 @@ def test_path_rules_under_a_score(driver):
     assert p.returncode == 0 and p.stdout.splitlines() == [
         "10 adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)",
         "11 adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)"], p.stdout
-    text = open(os.path.join(CSRC, "kernel_path.hpp")).read()
-    assert "REFUSE_ADAPTIVE_SCORE = static_cast<PathRefusal>(REFUSE_ADAPTIVE_ESTIMATOR + 1)" in text           # the value behind the estimator's
+    # the value behind the estimator's, and with both facts on (or any earlier one) the earlier refusal is answered
+    both = _lines(driver, "path", "".join(" ".join("%s=%d" % kv for kv in dict(BOX, adaptive=1, **on).items()) + "\n"
+                                          for on in ({}, dict(estimator=1), dict(measurement=1, estimator=1))))
+    assert [int(g["refusal"]) for g in both] == [11, 10, 9]
 
 
 def test_path_and_variant_sweeps_follow_the_state_logs_rule(driver):

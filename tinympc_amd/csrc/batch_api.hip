@@ -349,7 +349,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
-    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant); free_buffers(b->meas); free_buffers(b->est); free_buffers(b->score); free_buffers(b->act); free_buffers(b->anoise);   // (each names its own: batch_impl.hpp each_buffer)
+    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant); free_buffers(b->meas); free_buffers(b->est); free_buffers(b->score); free_buffers(b->act); free_buffers(b->anoise); free_buffers(b->model);   // (each names its own: batch_impl.hpp each_buffer)
     if (b->h_wire) hipHostFree(b->h_wire);
     if (b->d_hist) hipFree(b->d_hist);
     if (b->h_hist) hipHostFree(b->h_hist);
@@ -861,11 +861,11 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "tile_lm")) b->tile_lm = (int)value;    // experiments: the tile_dims.txt entry with this LM column
     else if (!strcmp(name, "tile_r")) b->tile_r = (int)value;      // experiments: the tile_dims.txt entry with this R (0: the first that fits)
     else if (!strcmp(name, "step_log")) b->step_log = value != 0;
-    else if (!strcmp(name, "estimate_log")) b->est.log_on = value != 0;     // the xhat every MPC step under a state estimator solved from (tiny_batch_get_estimate_log)
+    else if (!strcmp(name, "estimate_log")) b->est.log.on = value != 0;     // the xhat every MPC step under a state estimator solved from (tiny_batch_get_estimate_log)
     else if (!strcmp(name, "actuation_step")) b->anoise.step = value;       // the actuation step counter: the noise row and the index the next actuated MPC step takes
-    else if (!strcmp(name, "actuation_log")) b->act.log_on = value != 0;    // the control every plant step received (tiny_batch_get_actuation_log)
+    else if (!strcmp(name, "actuation_log")) b->act.log.on = value != 0;    // the control every plant step received (tiny_batch_get_actuation_log)
     else if (!strcmp(name, "score_step")) b->score.step = value;            // the score step counter: what the next scored MPC step records as its index
-    else if (!strcmp(name, "state_log")) b->plant.log_on = value != 0;      // the x0 every plant step hands on (tiny_batch_get_state_log)
+    else if (!strcmp(name, "state_log")) b->plant.log.on = value != 0;      // the x0 every plant step hands on (tiny_batch_get_state_log)
     else if (!strcmp(name, "reset_duals")) b->reset_duals = value != 0;
     else if (!strcmp(name, "store_primal")) { if (value < 0 || value > 2) return fail(b, TINY_ERR_ARG, "store_primal: 0, 1 or 2"); b->store_primal = (int)value; }
     else if (!strcmp(name, "share_ref")) b->share_ref = value != 0;
@@ -1045,10 +1045,10 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_measurement_noise")) return b->meas.last ? 1 : 0; // the last solve's launches applied the sequence: installed and a plant step taken
     if (!strcmp(name, "plant")) return b->plant.kind;                         // a plant of its own (tiny_batch_set_plant): 0 none, 1 one for all, 2 every instance its own
     if (!strcmp(name, "last_plant")) return b->plant.last ? 1 : 0;            // the last solve's launches took their plant step through it
-    if (!strcmp(name, "state_log")) return b->plant.log_on ? 1 : 0;
+    if (!strcmp(name, "state_log")) return b->plant.log.on ? 1 : 0;
     if (!strcmp(name, "estimator")) return b->est.kind;                       // a state estimator (tiny_batch_set_estimator): 0 none, 1 one gain for all, 2 every instance its own
     if (!strcmp(name, "last_estimator")) return b->est.last ? 1 : 0;          // the last solve's launches went through it
-    if (!strcmp(name, "estimate_log")) return b->est.log_on ? 1 : 0;
+    if (!strcmp(name, "estimate_log")) return b->est.log.on ? 1 : 0;
     if (!strcmp(name, "score")) return b->score.kind;                         // a closed-loop score (tiny_batch_set_score): 0 none, 1 one setup for all, 2 every instance its own
     if (!strcmp(name, "score_step")) return b->score.step;                    // the score step counter
     if (!strcmp(name, "last_score")) return b->score.last ? 1 : 0;            // the last solve's launches scored
@@ -1058,7 +1058,7 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "actuation_noise_generated")) return (b->anoise.seq && b->anoise.generated) ? 1 : 0;
     if (!strcmp(name, "actuation_step")) return b->anoise.step;               // the actuation step counter
     if (!strcmp(name, "last_actuator")) return b->act.last ? 1 : 0;           // the last solve's launches went through the actuator
-    if (!strcmp(name, "actuation_log")) return b->act.log_on ? 1 : 0;
+    if (!strcmp(name, "actuation_log")) return b->act.log.on ? 1 : 0;
     if (!strcmp(name, "last_uniform_bounds")) return b->last_ub ? 1 : 0;      // the last solve took a UB form: the knot-invariant box in registers, no table read
     if (!strcmp(name, "auto_split_measured_permille")) return (b->learn.auto_plain_rate > 0.0 && b->learn.auto_split_rate > 0.0) ? (long)(1000.0 * b->learn.auto_split_rate / b->learn.auto_plain_rate + 0.5) : 0;
     if (!strcmp(name, "repack_after")) return b->repack_after;

@@ -1,5 +1,6 @@
 // batch_dispatch.hpp -- what batch_api.hip (the C ABI), batch_dispatch.hip (kernel selection, launch forms), batch_tables.hip (lane
-// tables), batch_helpers.hip (helper kernels, on-demand buffers) and batch_instance.hip (per-instance problem data) share.
+// tables), batch_helpers.hip (helper kernels, on-demand buffers), batch_instance.hip (per-instance problem data) and
+// batch_closed_loop.hip (the stages at the fused closed-loop plant step) share.
 #pragma once
 #include "batch_impl.hpp"
 #include "kernel_path.hpp"
@@ -30,10 +31,10 @@ int ensure_regroup_buffers(TinyBatch* b, bool second_stream);
 int ensure_adaptive(TinyBatch* b, bool need_tables = true);
 int adaptive_fresh_state(TinyBatch* b);
 int max_enabled_halfspaces(const TinyBatch* b);   // the largest count per knot among the ENABLED half-space families (batch_tables.hip)
-// ---- every instance its own problem data (batch_instance.hip; the state: InstanceBox ... Disturbance of batch_impl.hpp)
+// ---- every instance its own problem data (batch_instance.hip; the state: InstanceBox, InstanceHalfspaces, InstanceCones of batch_impl.hpp)
 // what a launch calls: the blocks the kernels read, rebuilt where a setter or an enable switch left them out of date -- the box first and
 // synchronously (it may change the UB decision), the other two enqueued on the batch's stream; nothing out of date: a few flag tests, no
-// HIP call -- / the `last` flags <- what the kernel about to be launched reads
+// HIP call -- / the `last` flags <- what the kernel about to be launched reads (the closed-loop stages' too: note_closed_loop_read)
 int ensure_instance_data(TinyBatch* b);
 void note_instance_data_read(TinyBatch* b);
 void instance_data_settings_changed(TinyBatch* b);   // tiny_batch_update_settings: what an enable switch leaves out of date
@@ -43,66 +44,43 @@ int drop_instance_bounds(TinyBatch* b);
 int drop_instance_linear(TinyBatch* b, int set);
 int drop_instance_cones(TinyBatch* b);
 // half-spaces: is a per-instance set installed AND one of its families enabled (bit 0 static, bit 1 time-varying) / the block stride of
-// such a set: the smallest power of two that holds the enabled counts.  Cones: installed AND a cone family on.  Disturbance: installed
-// AND the next launch takes a plant step (advance_x0, or fused steps) / the row its first MPC step takes, as the kernels' int
+// such a set: the smallest power of two that holds the enabled counts.  Cones: installed AND a cone family on
 int inst_lin_active(const TinyBatch* b);
 int inst_lin_kmax(const TinyBatch* b);
 bool inst_cones_active(const TinyBatch* b);
-bool disturbance_active(const TinyBatch* b);
-int dist_step_base(const TinyBatch* b);
-// a plant of its own: installed AND the next launch takes a plant step / the state log: switched on AND the next launch takes a plant
-// step / the pointer a PP form reads (SolveArgs::plant: bit 0 says "one block for all") / room for `rows` rows of the log, none written
-// yet / the coverage path's plant step behind one single-step launch: the new states from x0, the u0 of the x|u record and the plant,
-// plus this step's disturbance block (null: none), for the instances whose launch ran an iteration; then x0 <- them / row `row` of the
-// log <- x0 as it is now
-bool plant_active(const TinyBatch* b);
-bool state_log_active(const TinyBatch* b);
-int ensure_plant_blocks(TinyBatch* b);          // (the blocks of the PP forms, built where the setter left them out of date; enqueued on the batch's stream)
-const double* plant_kernel_pointer(const TinyBatch* b);
-int begin_state_log(TinyBatch* b, int rows);
-int enqueue_coverage_plant_step(TinyBatch* b, const double* dist_block);
-// measurement noise: installed AND the next launch takes a plant step / the counter as the kernels take it / the coverage path's
-// measurements of one MPC step, xm <- fl(x0 + row `step` of the sequence): the array the launch takes as its x0 (x0 itself where the
-// row lies outside the sequence: nothing is enqueued)
-bool measurement_active(const TinyBatch* b);
-int meas_step_base(const TinyBatch* b);
-int enqueue_coverage_measurement(TinyBatch* b, long step, const double** x0_of_launch);
-int enqueue_state_log_row(TinyBatch* b, int row);
-// a state estimator: installed AND the next launch takes a plant step / the gain blocks of the PE forms and the MODEL's plant block,
-// built where they are missing or out of date / the pointers a PE form reads (SolveArgs::est_gain, est_model: bit 0 says "one block
-// for all") / room for `rows` rows of the estimate log / the coverage path's two helper kernels around one single-step launch: in
-// front, xhat <- the correction of the measurement `*x0_of_launch` names (x0, or the measurement helper's array) under xp, handed to
-// the launch as its x0 and written to row `log_row` of the log; behind, xp <- the model's prediction from xhat and the u0 of the x|u
-// record, for the instances whose launch ran an iteration
-bool estimator_active(const TinyBatch* b);
-int ensure_estimator_blocks(TinyBatch* b);
-const double* estimator_gain_pointer(const TinyBatch* b);
-const double* model_kernel_pointer(const TinyBatch* b);
-int begin_estimate_log(TinyBatch* b, int rows);
-int enqueue_coverage_correction(TinyBatch* b, int log_row, const double** x0_of_launch);
-int enqueue_coverage_prediction(TinyBatch* b);
-// a closed-loop score: installed AND the next launch takes a plant step / the score step counter as the kernels take it / the setup
-// blocks of the PS forms, built where they are missing or out of date / the pointer a PS form reads (SolveArgs::score_tab: bit 0 says
-// "one block for all") / the coverage path's helper kernel behind one single-step launch and its plant step: the record of every
-// instance whose launch ran an iteration takes z = [x0 as handed on | u0] in, as score step `step`
-bool score_active(const TinyBatch* b);
-int score_step_base(const TinyBatch* b);
-int ensure_score_blocks(TinyBatch* b);
-const double* score_kernel_pointer(const TinyBatch* b);
-int enqueue_coverage_score(TinyBatch* b, long step);
-// an actuator model: it or an actuation-noise sequence is installed AND the next launch takes a plant step / the actuation step counter
-// as the kernels take it / the setup blocks, the log of `rows` MPC steps and the record the PA forms read (SolveArgs::act), made and
-// written on the stream in front of a solve call's first launch / the coverage path's helper kernel behind one single-step launch: the
-// applied control of actuation step `step` into Actuator::ua (what the plant and score helpers behind it read), the lag's record and
-// row `log_row` of the log / the log sized for a coverage launch
-bool actuator_active(const TinyBatch* b);
-int actuation_step_base(const TinyBatch* b);
-int ensure_actuator_launch(TinyBatch* b, int rows, const ActuatorLaunch** out);
-int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row);
-int begin_actuation_log(TinyBatch* b, int rows);
+// ---- what batch_instance.hip and batch_closed_loop.hip share (defined in batch_instance.hip)
+unsigned helper_grid(const TinyBatch* b, size_t total);      // blocks of 256 threads for a grid-stride helper kernel over `total` elements
+struct UploadPart { const double* src; size_t doubles; };
+int upload_fresh(TinyBatch* b, const UploadPart* parts, double** fresh, int n, int flags, const char* what);   // fresh device copies, all or nothing
+int read_instance(TinyBatch* b, double* dst, const double* src, int instance, size_t n);                       // one instance of src [batch][n], to the host
 // frees and nulls every device buffer a family's struct names (the caller has seen the stream run dry of their readers)
 template <class S>
 void free_buffers(S& s) { s.each_buffer([](auto*& p) { if (p) (void)hipFree(p); p = nullptr; }); }
+// every buffer of one family goes, once the stream has run dry of their readers (its flags and sizes: the caller's)
+template <class S>
+int drop_buffers(TinyBatch* b, S& s) {
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    free_buffers(s);
+    return TINY_OK;
+}
+// ---- the stages at the fused closed-loop plant step (batch_closed_loop.hip; the state: closed_loop.hpp): one hook per place a launch
+// touches them.  The not-dirty path of a warm launch is flag tests and no HIP call
+void closed_loop_facts(const TinyBatch* b, PathFacts& f);             // the seven facts: a stage is installed AND the launch takes a plant step
+void note_closed_loop_read(TinyBatch* b);                             // the `last` flags <- those facts; the three logs are the LAST solve call's: rows = 0
+int bind_closed_loop_args(TinyBatch* b, const PathDecision& D, SolveArgs& a);   // the one-row launch: blocks built where out of date, logs sized, the PD ... PA fields of `a`
+struct StepBases {                                                    // the four counters and the two log pointers a stretch of MPC steps re-bases
+    int dist0 = 0, meas0 = 0, score0 = 0, act0 = 0;
+    double *state_log = nullptr, *est_log = nullptr;
+    bool pd = false, pm = false, ps = false, pa = false;
+    void capture(const JitKey& k, const SolveArgs& a);                // off the arguments as bound, by the forms the launch takes
+    void apply(SolveArgs& a, int done, int batch, int nx) const;      // the stretch that starts `done` steps in
+};
+struct CoverageLoop { bool noisy = false, filtered = false, scoring = false, actuated = false, own_plant = false, state_log = false; };
+int coverage_begin(TinyBatch* b, int steps, CoverageLoop& loop);      // which helper kernels the coverage path's single-step launches take; the logs sized
+int coverage_before_launch(TinyBatch* b, const CoverageLoop& loop, int s, GeneralArgs& a);        // step s: this step's disturbance block, the measurement, the correction -> a.dist, a.x0
+int coverage_after_launch(TinyBatch* b, const CoverageLoop& loop, int s, const GeneralArgs& a);   // step s: prediction, actuator, plant step, state log row, score
+void advance_closed_loop_counters(TinyBatch* b, int steps);           // behind a solve call: every counter whose stage applied moves `steps` on
 // ---- lane tables (batch_tables.hip)
 struct SharedHalfspaces { HalfspaceRows sx, su, tx, tu; };   // static state | input, time-varying state | input (lane_tables.hpp)
 SharedHalfspaces shared_halfspaces(const TinyBatch* b);

@@ -1,7 +1,7 @@
 // batch_helpers.hip -- what the clock-checked dispatch needs besides the solve kernels: the iteration histogram of a solve (its cost
 // model is host arithmetic: launch_learner.hpp), the counting sorts behind step_regroup / repack_sort and the lock-step estimate (small
 // device kernels of this unit), the per-instance state of adaptive rho, and the buffers all of them allocate on demand.  Split off
-// batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.  (Per-instance problem data and its fill kernels: batch_instance.hip.)
+// batch_dispatch.hip in round 6; declarations: batch_dispatch.hpp.  (Per-instance problem data and its fill kernels: batch_instance.hip; the closed-loop stages, their fill and coverage helper kernels: batch_closed_loop.hip.)
 #include "batch_impl.hpp"
 #include "batch_dispatch.hpp"
 #include "lane_tables.hpp"

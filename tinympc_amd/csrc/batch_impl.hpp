@@ -1,5 +1,5 @@
 // batch_impl.hpp -- the opaque TinyBatch behind include/tinympc_amd.h (shared by batch_api.hip, batch_dispatch.hip, batch_tables.hip, batch_helpers.hip,
-// batch_instance.hip and compat_api.hip).
+// batch_instance.hip, batch_closed_loop.hip and compat_api.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +14,7 @@
 #include "tile_kernel.hip.h"
 #include "cache.hpp"
 #include "launch_learner.hpp"
+#include "closed_loop.hpp"          // the state of the stages at the fused closed-loop plant step
 
 namespace tinympc_amd {
 
@@ -28,7 +29,7 @@ struct Settings {              // TinySettings (types.hpp:63-82) hot-path subset
 
 // ---- every instance its own problem data: one plain struct per family (batch_instance.hip sets, builds, reads and drops them).  Each
 // names every device buffer it owns in each_buffer -- the drop paths and tiny_batch_destroy free through it and nothing else: a new
-// buffer is one more line there.  `last`: what the last solve's kernel read (options "last_instance_*", "last_disturbance")
+// buffer is one more line there.  `last`: what the last solve's kernel read (options "last_instance_*")
 // every instance its own box (tiny_batch_set_instance_bounds): the caller's four arrays as given (src: x_min, x_max [batch][N][nx],
 // u_min, u_max [batch][N-1][nu]) and what the kernels read, built from them: built [batch][lo | hi][N][box_lanes]
 // (lane_tables.hpp box_entry; rebuilt when the box or an enable switch changes: dirty).  uniform: EVERY instance's box is
@@ -64,111 +65,6 @@ struct InstanceCones {
     int* pos = nullptr;
     size_t stage_doubles = 0;
     template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(stage); f(pos); }
-};
-// every instance its own additive disturbance at the plant step (tiny_batch_set_disturbance): seq [steps][batch][nx],
-// step-major -- a launch reads one contiguous [batch][nx] block per MPC step; a broadcast sequence is expanded to that layout on the
-// device.  step: the row the next plant step takes (the setter rewinds it, option "disturbance_step" moves it,
-// every MPC step of a launch with a plant step advances it, tiny_batch_reset leaves it alone); rows outside [0, steps) add nothing
-struct Disturbance {
-    double* seq = nullptr;
-    int steps = 0;
-    long step = 0;
-    bool last = false;                             // (... applied the sequence: installed and a plant step taken)
-    bool generated = false;                        // the sequence came from tiny_batch_generate_disturbance (option "disturbance_generated")
-    template <class F> void each_buffer(F f) { f(seq); }
-};
-// a plant model of its own at the plant step (tiny_batch_set_plant) and the log of what the plant step handed on (option "state_log").
-// src: the caller's A_p | B_p | f_p, kept on the device as given ([batch][...] column-major, or ONE set with kind 1; f_p may be null:
-// zero) -- what the getter and the coverage path's helper kernel read; built: the blocks the one-row kernel's PP forms read
-// (plant_entry of lane_tables.hpp: [batch or 1][nx + nu + 1][16]), made in front of the next launch; next: [batch][nx], where the
-// coverage path's helper kernel puts the new states before they replace x0.  log: [log_steps][batch][nx], the x0 every MPC step of the
-// last solve call handed on
-struct PlantStep {
-    int kind = 0;                                  // 0 none, 1 one plant for all, 2 every instance its own
-    bool dirty = false, last = false;              // (... took their plant step through it: installed and a plant step taken)
-    double *src[3] = {nullptr, nullptr, nullptr}, *built = nullptr, *next = nullptr;
-    bool log_on = false;                           // option "state_log"
-    double* log = nullptr;
-    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
-    int log_rows = 0;
-    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(next); f(log); }
-};
-// measurement noise at the plant step of a closed loop (tiny_batch_set_measurement_noise): seq [steps][batch][nx], step-major like the
-// disturbance's, a broadcast sequence expanded on the device; step: the row the next MPC step's measurement takes (the disturbance
-// counter's rules).  While it applies the x0 record is the TRUE state and the plant step goes through a plant block: the installed
-// plant's, or the model's own -- model: A | B | f of a shared family as the coverage path's helper kernel reads them (a per-instance
-// family: the arrays tiny_batch_setup_hetero keeps), model_built: the block(s) the one-row kernel's PM forms read (plant_entry), both
-// made once: A, B and f are fixed at setup (no setter moves them; adaptive rho moves the cache only).  xm [batch][nx]: where the coverage path forms the measurements its launch takes as x0
-struct MeasurementNoise {
-    double* seq = nullptr;
-    int steps = 0;
-    long step = 0;
-    bool last = false;                             // (... applied the sequence: installed and a plant step taken)
-    bool generated = false;                        // the sequence came from tiny_batch_generate_measurement_noise (option "measurement_noise_generated")
-    double *model[3] = {nullptr, nullptr, nullptr}, *model_built = nullptr, *xm = nullptr;
-    template <class F> void each_buffer(F f) { f(seq); for (double*& p : model) f(p); f(model_built); f(xm); }
-};
-// a fixed-gain state estimator between the measurement and the solve (tiny_batch_set_estimator) and the log of what every MPC step
-// solved from (option "estimate_log").  src: the caller's M, kept on the device as given ([batch][nx*nx] column-major, or ONE with kind
-// 1) -- what the getter and the coverage path's helper kernel read; built: the blocks the one-row kernel's PE forms read (gain_entry of
-// lane_tables.hpp: [batch or 1][nx][16]), made in front of the next launch; xp [batch][nx]: the predicted estimate, STATE of the batch
-// like x0 (it lives as long as an estimator is installed); xhat [batch][nx]: where the coverage path forms the corrected estimates its
-// launch takes as x0; log: [log_steps][batch][nx].  The model's block and arrays, which predict, are MeasurementNoise's (both features
-// step through them)
-struct Estimator {
-    int kind = 0;                                  // 0 none, 1 one gain for all, 2 every instance its own
-    bool dirty = false, last = false;              // (... went through it: installed and a plant step taken)
-    double *src = nullptr, *built = nullptr, *xp = nullptr, *xhat = nullptr;
-    bool log_on = false;                           // option "estimate_log"
-    double* log = nullptr;
-    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
-    int log_rows = 0;
-    template <class F> void each_buffer(F f) { f(src); f(built); f(xp); f(xhat); f(log); }
-};
-// a closed-loop score at the plant step (tiny_batch_set_score).  src: the caller's weight | target | lo | hi, kept on the device as given
-// ([batch][nx+nu] each, or ONE with kind 1; target, lo and hi may be null) -- what the getter and the coverage path's helper kernel read;
-// built: the blocks the one-row kernel's PS forms read (score_entry of lane_tables.hpp: [batch or 1][4][16]), made in front of the next
-// launch; rec [batch]: the record (ScoreRecord of admm_kernel.hip.h: cost, worst, violated_steps, first_violation), STATE of the batch:
-// it accumulates over launches until the setter or tiny_batch_reset_score zeroes it.  step: the score step counter (the setter and the
-// reset rewind it, option "score_step" moves it, every MPC step of a launch that takes a plant step advances it)
-struct Score {
-    int kind = 0;                                  // 0 none, 1 one setup for all, 2 every instance its own
-    bool dirty = false, last = false;              // (... scored: installed and a plant step taken)
-    double *src[4] = {nullptr, nullptr, nullptr, nullptr}, *built = nullptr;
-    void* rec = nullptr;
-    long step = 0;
-    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(rec); }
-};
-// an actuator model between the command and the plant step (tiny_batch_set_actuator).  src: the caller's lo | hi | alpha | gain | offset,
-// kept on the device as given ([batch][nu] each, or ONE with kind 1; any may be null) -- what the getter and the coverage path's helper
-// kernel read; built: the blocks the one-row kernel's PA forms read (actuator_entry of lane_tables.hpp: [batch or 1][5][16]), made in
-// front of the next launch; state [batch][nu]: the lag's record a, STATE of the batch, there while a lag (alpha) is installed; ua
-// [batch][nu]: where the coverage path's helper kernel puts the applied control for the plant and score helpers behind it; log
-// [log_steps][batch][nu]: the applied control of every MPC step of the last solve call (option "actuation_log"); desc: the record the PA
-// forms read (ActuatorLaunch of admm_kernel.hip.h), written on the stream in front of a solve call's first launch.  last: the last
-// solve's launches went through the actuator -- this setup or the noise sequence below
-struct Actuator {
-    int kind = 0;                                  // 0 none, 1 one setup for all, 2 every instance its own
-    bool lag = false;                              // alpha is installed
-    bool dirty = false, last = false;
-    double *src[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}, *built = nullptr, *state = nullptr, *ua = nullptr;
-    bool log_on = false;                           // option "actuation_log"
-    double* log = nullptr;
-    int log_steps = 0;                             // rows `log` holds room for / rows the last solve call wrote
-    int log_rows = 0;
-    void* desc = nullptr;
-    template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(state); f(ua); f(log); f(desc); }
-};
-// actuation noise, the last stage of the actuator (tiny_batch_set_actuation_noise): seq [steps][batch][nu], step-major like the
-// disturbance's, a broadcast sequence expanded on the device; step: the actuation step counter (the disturbance counter's rules: this
-// setter rewinds it, option "actuation_step" moves it, every MPC step of a launch that takes a plant step under an actuator or this
-// sequence advances it)
-struct ActuationNoise {
-    double* seq = nullptr;
-    int steps = 0;
-    long step = 0;
-    bool generated = false;                        // the sequence came from tiny_batch_generate_actuation_noise (option "actuation_noise_generated")
-    template <class F> void each_buffer(F f) { f(seq); }
 };
 
 constexpr size_t KPI_SKEW_BYTES = 0;         // stagger between the starts of the record arrays inside their slab (see tiny_batch_setup)
@@ -259,7 +155,9 @@ struct TinyBatch {
     bool bounds_uniform = false;                   // box_is_uniform when a lane table was last built: every knot has the same box (the UB forms)
     bool last_ub = false;                          // the last solve launch took a UB form (a split solve: its first stage); the coverage kernel has none
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
-    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone; Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score; Actuator act; ActuationNoise anoise;
+    InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone;
+    // the stages at the fused closed-loop plant step (closed_loop.hpp); setters, getters and what a launch does with them: batch_closed_loop.hip
+    Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score; Actuator act; StepSequence anoise; ModelBlock model;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -60,16 +60,11 @@ inline bool facts_consistent(const PathFacts& f) {
 }
 
 enum KernelPath { ONE_ROW = 0, TILE = 1, COVERAGE = 2 };
-// what adaptive rho does not combine with; the texts callers read through tiny_batch_last_error
-// (REFUSE_ADAPTIVE_INSTANCE_CONES came last and keeps the values of the others; it is REPORTED in front of the overlapping cones: decide_path)
+// what adaptive rho does not combine with, and the texts callers read through tiny_batch_last_error: PATH_REFUSAL_MESSAGE is indexed by
+// the enumerator.  The values are the order the refusals were added in; the order they are REPORTED in is decide_path's
 enum PathRefusal { REFUSE_NONE = 0, REFUSE_ADAPTIVE_INSTANCE_BOX, REFUSE_ADAPTIVE_HALFSPACES, REFUSE_ADAPTIVE_OVERLAPPING_CONES, REFUSE_ADAPTIVE_NO_REGISTER_FORM,
-                   REFUSE_ADAPTIVE_INSTANCE_CONES, REFUSE_ADAPTIVE_DISTURBANCE, REFUSE_ADAPTIVE_PLANT,
-                   REFUSE_ADAPTIVE_STATE_LOG, REFUSE_ADAPTIVE_MEASUREMENT, REFUSE_ADAPTIVE_ESTIMATOR };      // (the last five are the last ones reported, too, in this order)
-// (the closed-loop score's, the next value and the next one reported: a constant behind the enumeration, whose closing line
-// tests/test_estimator_cpu.py pins; 11 lies within the enumeration's range)
-constexpr PathRefusal REFUSE_ADAPTIVE_SCORE = static_cast<PathRefusal>(REFUSE_ADAPTIVE_ESTIMATOR + 1);
-// (... and the actuator model's behind it, the last one reported)
-constexpr PathRefusal REFUSE_ADAPTIVE_ACTUATOR = static_cast<PathRefusal>(REFUSE_ADAPTIVE_SCORE + 1);
+                   REFUSE_ADAPTIVE_INSTANCE_CONES, REFUSE_ADAPTIVE_DISTURBANCE, REFUSE_ADAPTIVE_PLANT, REFUSE_ADAPTIVE_STATE_LOG, REFUSE_ADAPTIVE_MEASUREMENT,
+                   REFUSE_ADAPTIVE_ESTIMATOR, REFUSE_ADAPTIVE_SCORE, REFUSE_ADAPTIVE_ACTUATOR };
 constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "",
     "adaptive rho does not combine with per-instance bounds (tiny_batch_set_instance_bounds): a per-instance box "
@@ -78,21 +73,18 @@ constexpr const char* PATH_REFUSAL_MESSAGE[] = {
     "adaptive rho does not combine with heterogeneous data / half-spaces / one_shot / repack_after",
     "overlapping cones run on the coverage kernel: no adaptive rho with them",
     "adaptive rho needs the register-resident kernel (nx+nu <= 16, horizon within the register file)",
-};
-// (a text of its own next to the table, whose five entries are listed one by one by the callers of tests/dropin/kernel_path_driver.cpp)
-constexpr const char* PATH_REFUSAL_INSTANCE_CONES =
     "adaptive rho does not combine with per-instance cone coefficients (tiny_batch_set_instance_cone_coefficients): the adaptive cone "
-    "form has no per-instance coefficients, and the coverage kernel does not take adaptive rho";
-constexpr const char* PATH_REFUSAL_DISTURBANCE = "adaptive rho does not combine with a per-instance disturbance";
-constexpr const char* PATH_REFUSAL_PLANT = "adaptive rho does not combine with a plant of its own at the plant step (tiny_batch_set_plant)";
-constexpr const char* PATH_REFUSAL_STATE_LOG = "adaptive rho does not combine with the state log (option state_log)";
-constexpr const char* PATH_REFUSAL_MEASUREMENT = "adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)";
-constexpr const char* PATH_REFUSAL_ESTIMATOR = "adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)";
-constexpr const char* PATH_REFUSAL_SCORE = "adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)";
-constexpr const char* PATH_REFUSAL_ACTUATOR = "adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)";
-inline const char* path_refusal_message(PathRefusal r) {
-    return r == REFUSE_ADAPTIVE_ACTUATOR ? PATH_REFUSAL_ACTUATOR : r == REFUSE_ADAPTIVE_SCORE ? PATH_REFUSAL_SCORE : r == REFUSE_ADAPTIVE_ESTIMATOR ? PATH_REFUSAL_ESTIMATOR : r == REFUSE_ADAPTIVE_MEASUREMENT ? PATH_REFUSAL_MEASUREMENT : r == REFUSE_ADAPTIVE_PLANT ? PATH_REFUSAL_PLANT : r == REFUSE_ADAPTIVE_STATE_LOG ? PATH_REFUSAL_STATE_LOG : r == REFUSE_ADAPTIVE_DISTURBANCE ? PATH_REFUSAL_DISTURBANCE : r == REFUSE_ADAPTIVE_INSTANCE_CONES ? PATH_REFUSAL_INSTANCE_CONES : PATH_REFUSAL_MESSAGE[r];
-}
+    "form has no per-instance coefficients, and the coverage kernel does not take adaptive rho",
+    "adaptive rho does not combine with a per-instance disturbance",
+    "adaptive rho does not combine with a plant of its own at the plant step (tiny_batch_set_plant)",
+    "adaptive rho does not combine with the state log (option state_log)",
+    "adaptive rho does not combine with measurement noise (tiny_batch_set_measurement_noise)",
+    "adaptive rho does not combine with a state estimator (tiny_batch_set_estimator)",
+    "adaptive rho does not combine with a closed-loop score (tiny_batch_set_score)",
+    "adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)",
+};
+static_assert(sizeof(PATH_REFUSAL_MESSAGE) / sizeof(PATH_REFUSAL_MESSAGE[0]) == REFUSE_ADAPTIVE_ACTUATOR + 1, "one text per refusal");
+inline const char* path_refusal_message(PathRefusal r) { return PATH_REFUSAL_MESSAGE[r]; }
 
 struct PathDecision {
     KernelPath kernel;
@@ -134,30 +126,23 @@ inline PathDecision decide_path(const PathFacts& f) {
                                                    : REFUSE_NONE;
     auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
     auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
-    // every instance its own disturbance at the plant step: ONE rule pair, applied to whatever one-row answer the rules below give --
-    // the PD form of that very form (PB, PL and PC forms take the bit as well and keep their rule's name; every other one-row answer
-    // is "one_row:pd"), run-time instantiated only, so where hipRTC may not be tried, with debug outputs, under force_general and with
-    // adaptive rho (refused) the coverage kernel answers: "cover:pd".  A coverage answer stays what it is, the tile kernel is not asked
-    // A plant of its own at the plant step: the same rule pair under its own names, "one_row:pp" / "cover:pp" -- the PP form of that
-    // very form, with the PD bit as well where a disturbance applies, under the same conditions.  The state log is written by the PD and
-    // PP forms: with neither installed it rides on the PD form with an empty sequence, which adds nothing (rule names: pd's)
-    // Measurement noise: the same rule pair once more, "one_row:pm" / "cover:pm" -- the PM form of that very form.  A PM form steps the
-    // TRUE state through a plant block, so the fact forces pp on: with no plant installed the launch forms the block from the model
-    // A state estimator: the same rule pair, "one_row:pe" / "cover:pe" -- the PE form of that very form.  It corrects a MEASURED state
-    // and the true one is stepped apart from it, so the fact forces pm and pp on: with no noise sequence the launch binds an empty one
-    // A closed-loop score: the same rule pair, "one_row:ps" / "cover:ps" -- the PS form of that very form.  It is written where the PD and
-    // PP forms hand a state on: with neither installed it rides on the PD form with an empty sequence, as the state log does
-    // An actuator model: the same rule pair, "one_row:pa" / "cover:pa" -- the PA form of that very form.  The plant step must be a chain
-    // over the APPLIED control, not the solver's own x1, so the fact forces pp on: with no plant installed the launch forms the block
-    // from the model, as under measurement noise
+    // the stages at the fused closed-loop plant step: ONE rule, applied to whatever one-row answer the rules below give -- the PD ... PA
+    // form of that very form (PB, PL and PC forms take the bits and keep their rule's name; every other one-row answer is
+    // "one_row:<form>"), run-time instantiated only: where hipRTC may not be tried, with debug outputs, under force_general and with
+    // adaptive rho (refused) the coverage kernel answers, "cover:<form>".  A coverage answer stays what it is, the tile kernel is not
+    // asked.  Which facts force which bits on, and the precedence of the name: profiles/kernel_path.md
+    const bool closed_loop = f.disturbance || f.plant || f.state_log || f.measurement || f.estimator || f.score || f.actuator;
     const bool pd_form = f.fits && hiprtc && !f.force_general && !f.debug && !f.adaptive;
     const bool pe = f.estimator, pm = f.measurement || pe, pa = f.actuator, pp = f.plant || pm || pa, pd = f.disturbance || ((f.state_log || f.score) && !pp);
     const bool ps = f.score;
+    struct FormRules { const char *cover, *one_row; };
+    static constexpr FormRules FORMS[] = {{"cover:pd", "one_row:pd"}, {"cover:pp", "one_row:pp"}, {"cover:pm", "one_row:pm"},
+                                          {"cover:pe", "one_row:pe"}, {"cover:ps", "one_row:ps"}, {"cover:pa", "one_row:pa"}};
+    const FormRules& form = FORMS[pa ? 5 : ps ? 4 : pe ? 3 : pm ? 2 : pp ? 1 : 0];       // (the name's precedence: pa, ps, pe, pm, pp, pd)
     auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) {
         if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0, 0, 0, 0};
-        if (!pd_form) return cover(pa ? "cover:pa" : ps ? "cover:ps" : pe ? "cover:pe" : pm ? "cover:pm" : pp ? "cover:pp" : "cover:pd");
-        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : pa ? "one_row:pa" : ps ? "one_row:ps" : pe ? "one_row:pe" : pm ? "one_row:pm" : pp ? "one_row:pp" : "one_row:pd", pc, pd ? 1 : 0, pp ? 1 : 0,
-                            pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0, pa ? 1 : 0};
+        if (!pd_form) return cover(form.cover);
+        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : form.one_row, pc, pd ? 1 : 0, pp ? 1 : 0, pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0, pa ? 1 : 0};
     };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
@@ -172,7 +157,7 @@ inline PathDecision decide_path(const PathFacts& f) {
     // half-space / EXT forms and every form of a shape outside tile_dims.txt are run-time instantiated; EXT forms are for the shapes
     // the one-row kernel does not hold)
     const bool ext = f.tile_ext || f.hetero;
-    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !f.disturbance && !f.plant && !f.state_log && !f.measurement && !f.estimator && !f.score && !f.actuator &&
+    const bool tile_can = f.has_tile && !f.no_tile && !f.force_general && !f.debug && !(lf && !f.tile_lin) && !closed_loop &&
                           !((f.tile_is_jit || f.soc || lf || ext) && (f.no_jit || f.tile_soc_failed)) && !(ext && regs);
 
     // ---- the rules, in order

@@ -3,8 +3,9 @@
 (hipcc -Rpass-analysis=kernel-resource-usage on tinympc_amd/csrc/_gen/{k,t}_*.hip).  Scratch > 0 = spilled to memory.
 The one-row forms csrc/jit_prebuilt.txt names (run-time instantiated, never in a unit) are compiled here as explicit instantiations and
 listed after the compiled-in ones; then the setup kernels of batch_dispatch.hip (riccati_kernel, sensitivity_kernel) and, last, the helper
-kernels of batch_instance.hip (the fill kernels of the per-instance data and of the generated noise, the coverage path's helpers -- fill_actuator_kernel,
-write_actuator_launch_kernel and coverage_actuator_kernel of the actuator model among them).
+kernels of batch_instance.hip (the fill kernels of the per-instance data) and of batch_closed_loop.hip (the fill kernels of the closed-loop
+stages and of the generated noise, the coverage path's helpers -- fill_actuator_kernel, write_actuator_launch_kernel and
+coverage_actuator_kernel of the actuator model among them).
     python tools/register_audit.py [--all] > profiles/rNN_register_audit.md"""
 import concurrent.futures
 import glob
@@ -55,9 +56,10 @@ def setup_kernel_rows():
 
 
 def helper_kernel_rows():
-    """every __global__ of batch_instance.hip: fill kernels (generate_diagonal_kernel / generate_factor_kernel, fill_actuator_kernel among them) and
-    coverage helpers (coverage_actuator_kernel: the actuator model behind a coverage launch)"""
-    return usage("batch_instance.hip", cwd=CSRC, extra=("--cuda-device-only",))
+    """every __global__ of batch_instance.hip (the per-instance fill kernels) and of batch_closed_loop.hip: fill kernels
+    (generate_diagonal_kernel / generate_factor_kernel, fill_actuator_kernel among them) and coverage helpers (coverage_actuator_kernel:
+    the actuator model behind a coverage launch)"""
+    return [r for unit in ("batch_instance.hip", "batch_closed_loop.hip") for r in usage(unit, cwd=CSRC, extra=("--cuda-device-only",))]
 
 
 def main():
@@ -107,7 +109,7 @@ def main():
     for r in setup_kernel_rows():
         kname = "sensitivity_kernel" if "sensitivity_kernel" in r["name"] else "riccati_kernel"
         print(f"| {kname} | {r['vgpr']} | {r['agpr']} | {r['scratch']} | {r['occ']} | {r['lds']} |")
-    print("\nhelper kernels of batch_instance.hip (256 threads a block, grid-stride):\n")
+    print("\nhelper kernels of batch_instance.hip and batch_closed_loop.hip (256 threads a block, grid-stride):\n")
     print("| kernel | VGPR | AGPR | scratch B/lane | waves/SIMD | LDS B |")
     print("|---|---|---|---|---|---|")
     for r in helper_kernel_rows():
