@@ -453,7 +453,8 @@ int tiny_batch_reset_score(TinyBatch* b);                                       
  * kernel behind each single-step launch of the coverage kernel, same bits.  Adaptive rho on such a launch fails the solve with
  * TINY_ERR_UNSUPPORTED ("adaptive rho does not combine with an actuator model (tiny_batch_set_actuator)").
  * Out of scope: pure transport delays; rate limits; an estimator that is told ua; the tile kernel; the half-row and PREFETCH forms;
- * tiny_codegen; tiny_solve_batch and the drop-in structs. */
+ * tiny_codegen; tiny_solve_batch and the drop-in structs.  (Of these the transport delay has since become a stage of its own in front of
+ * the limits, with an estimator that is told what left the queue: tiny_batch_set_actuator_delay below.) */
 int tiny_batch_set_actuator(TinyBatch* b, const double* lo, const double* hi, const double* alpha, const double* gain, const double* offset, int flags);
 /* the setup instance `instance` is actuated by, as installed, defaults filled in (alpha reads 1.0 with no lag): [nu] each, any may be
  * NULL; TINY_ERR_ARG with none installed */
@@ -470,6 +471,38 @@ int tiny_batch_generate_actuation_noise(TinyBatch* b, const TinyNoiseSpec* spec)
 /* ... and the same rows on the host, no GPU touched: out [n_steps][batch][nu] (tiny_noise_generate keeps to streams 0 and 1) */
 int tiny_actuation_noise_generate(const TinyNoiseSpec* spec, int batch, int nu, double* out);
 int tiny_batch_get_actuation_log(TinyBatch* b, double* ua, int steps);             /* option "actuation_log" = 1: [steps][batch][nu], the control every plant step of the last solve call received */
+/* stage 0 of the actuator, a transport delay: the command computed for period k reaches the motors d periods later (the solve and the
+ * link take time) -- dead time, which the lag of stage 2, a first-order filter, cannot stand in for.
+ * d [batch] ints, or with TINY_BROADCAST one for all; TINY_HOST | TINY_DEVICE; 0 <= d[i] <= d_max <= TINY_MAX_DELAY, otherwise
+ * TINY_ERR_ARG.  d == NULL or d_max <= 0 removes the delay.  A failed call leaves what was installed.
+ * Meaning: the queue is a FIFO of instance i's last d[i] commands, state of the batch like the lag's record a.  Installing (or
+ * replacing) a delay fills it with +0.0.  At every MPC step that takes a plant step, with command uc (what the step log and the u record
+ * keep): d[i] == 0: s0 = uc, its own bits, nothing is read or written; d[i] > 0: s0 is the oldest entry, which leaves, and uc enters as
+ * the newest.  s0 is what the limits of stage 1 see: delay -> limits -> lag -> gain -> noise.  A step that ran no iteration takes no plant
+ * step: no stage runs and the queue stays.  The actuation log keeps the applied control of the delayed command.  A delay alone, with no
+ * actuator and no noise, is allowed.  d == 0 everywhere reproduces the run without a delay, bit for bit.  tiny_batch_set_actuator
+ * (installing, replacing, removing) and tiny_batch_reset leave the delay and its queue alone.
+ * The queue: q [batch][d_max][nu], oldest first (TINY_BROADCAST: [d_max][nu]); only the first d[i] rows of an instance's slice mean
+ * anything, the getter returns them oldest first and +0.0 behind them.  Setter and getter answer TINY_ERR_ARG with no delay installed.
+ * The predictor (tiny_batch_set_option "delay_compensation" = 1, default 0; inert with no delay installed): MPC step k of instance i
+ * does not solve from xin -- the x0 record, the reading xm under measurement noise, or xhat under an estimator -- but from
+ *     xs = xin;  for t = 0 .. d[i]-1 (oldest first):  xs = f + A xs + B q[t]
+ * with A, B, f the batch's OWN model (never the installed plant), every step the fma chain tiny_batch_set_plant documents (the
+ * accumulator starts at f), q the queue as it stands BEFORE this step's push; d[i] == 0 leaves xin's bits alone.  As under measurement
+ * noise the x0 record is the TRUE state while compensation applies: the plant step starts from it (through the installed plant or, with
+ * none, the model), and the state log records true states.  With an estimator the estimate log keeps xhat, not xs, and the model's
+ * prediction of the next xp starts from xhat and uses s0 -- the command the controller knows is reaching the actuator now; with
+ * compensation off it keeps using uc.
+ * Read-backs: "actuator_delay" d_max as installed, 0 when none; "delay_compensation" the switch; "last_actuator" covers the delay.
+ * Where it runs: the one-row kernel's PQ forms (the queue; on a PA form) and PX forms (the predictor; on a PQ and a PM form), run-time
+ * instantiated; everywhere else helper kernels around each single-step launch of the coverage kernel, same bits.  Adaptive rho is
+ * refused as with an actuator model, in its text.
+ * Out of scope: per-input delays; fractional delays; a delay on the measurement side. */
+#define TINY_MAX_DELAY 8
+int tiny_batch_set_actuator_delay(TinyBatch* b, const int* d, int d_max, int flags);
+int tiny_batch_get_actuator_delay(TinyBatch* b, int instance, int* d_out);
+int tiny_batch_set_actuator_queue(TinyBatch* b, const double* q, int flags);
+int tiny_batch_get_actuator_queue(TinyBatch* b, double* q_out);                    /* [batch][d_max][nu], host, oldest first */
 /* == tiny_update_settings (tiny_api.hpp:36-42).  With a linear / time-varying-linear switch on (or a shape
  * without a register-resident instantiation) the solve runs the coverage kernel (general_kernel.hip.h). */
 int tiny_batch_update_settings(TinyBatch* b, double abs_pri_tol, double abs_dua_tol, int max_iter,
@@ -776,6 +809,11 @@ int tiny_group_set_actuator(TinyGroup* g, const double* lo, const double* hi, co
 int tiny_group_set_actuator_state(TinyGroup* g, const double* a, int flags);
 int tiny_group_set_actuation_noise(TinyGroup* g, const double* n, int n_steps, int flags);
 int tiny_group_generate_actuation_noise(TinyGroup* g, const TinyNoiseSpec* spec);
+/* the transport delay (tiny_batch_set_actuator_delay, tiny_batch_set_actuator_queue): host, d [batch] / q [batch][d_max][nu] over the
+ * full batch axis in the caller's order, or with TINY_BROADCAST one; tiny_group_set_option forwards "delay_compensation"; the queue is
+ * read shard by shard (tiny_group_shard) */
+int tiny_group_set_actuator_delay(TinyGroup* g, const int* d, int d_max, int flags);
+int tiny_group_set_actuator_queue(TinyGroup* g, const double* q, int flags);
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc,
                                int en_state_linear, int en_input_linear, int en_tv_state_linear, int en_tv_input_linear);

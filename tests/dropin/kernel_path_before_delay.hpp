@@ -1,3 +1,5 @@
+// kernel_path_before_delay.hpp -- a frozen copy, in a namespace of its own, of csrc/kernel_path.hpp as it stood before the transport
+// delay: tests/dropin/delay_path_driver.cpp compares today's decisions with its.  From here on the header's own text:
 // kernel_path.hpp -- which kernel a solve runs on (the one-row register kernel, the tile kernel or the coverage kernel), which half-space /
 // per-instance form of the one-row kernel it takes and which combinations with adaptive rho are refused: ONE ordered list of rules
 // (decide_path) over a flat set of facts (PathFacts; batch_dispatch.hip path_facts is the only code that reads them off a handle).
@@ -5,7 +7,7 @@
 // call and is not kept on the handle: any setter can change a fact.  The rules, their order and their oddities: profiles/kernel_path.md
 #pragma once
 
-namespace tinympc_amd {
+namespace kernel_path_before_delay {
 
 struct PathFacts {
     // ---- what the shape allows (with the cone / debug / FMA-block mode that are on)
@@ -44,10 +46,7 @@ struct PathFacts {
     bool measurement = false;           // a measurement-noise sequence is installed AND the launch takes a plant step
     bool estimator = false;             // a state estimator is installed AND the launch takes a plant step
     bool score = false;                 // a closed-loop score is installed AND the launch takes a plant step
-    bool actuator = false;              // an actuator model, an actuation-noise sequence or a transport delay is installed AND the launch takes a plant step
-    // ---- the transport delay in front of the actuator (appended likewise; both only with `actuator`: the delay is part of it)
-    bool delay = false;                 // a transport delay is installed AND the launch takes a plant step
-    bool delay_compensation = false;    // ... AND option "delay_compensation" is on: the solve starts from the model's prediction over the queue
+    bool actuator = false;              // an actuator model or an actuation-noise sequence is installed AND the launch takes a plant step
 };
 
 // what path_facts can produce: the sweep of tests/dropin/kernel_path_driver.cpp counts these combinations only
@@ -59,8 +58,7 @@ inline bool facts_consistent(const PathFacts& f) {
            (!f.entry_plain || f.has_entry) && (!f.entry_klin || (f.has_entry && f.lin_families)) &&
            (!f.fits || f.fits_box) && (f.soc || f.fits == f.fits_box) &&             // a cone costs registers
            (!f.tile_is_jit || f.has_tile) && (!f.tile_lin || (f.has_tile && f.lin_kmax != 0)) &&
-           (!f.cones_overlap || f.soc) && (!f.inst_cones || f.soc) &&
-           (!f.delay || f.actuator) && (!f.delay_compensation || f.delay);          // the delay is part of the actuator; the predictor needs a queue
+           (!f.cones_overlap || f.soc) && (!f.inst_cones || f.soc);
 }
 
 enum KernelPath { ONE_ROW = 0, TILE = 1, COVERAGE = 2 };
@@ -103,8 +101,6 @@ struct PathDecision {
     int pe = 0;                    // ONE_ROW: the form with a state estimator in front of the solve (likewise; always with pm and pp)
     int ps = 0;                    // ONE_ROW: the form that scores what the plant step hands on (likewise; always with pd or pp)
     int pa = 0;                    // ONE_ROW: the form with an actuator model between the command and the plant step (likewise; always with pp)
-    int pq = 0;                    // ONE_ROW: the form with a transport delay in front of the actuator's stages (likewise; always with pa)
-    int px = 0;                    // ONE_ROW: the form that solves from the model's prediction over the delay's queue (likewise; always with pq and pm)
 };
 
 // a one-row kernel exists for the shape: compiled in (counted even under no_jit), or one that run-time instantiation can make
@@ -128,7 +124,7 @@ inline PathDecision decide_path(const PathFacts& f) {
                                 : f.measurement    ? REFUSE_ADAPTIVE_MEASUREMENT
                                 : f.estimator      ? REFUSE_ADAPTIVE_ESTIMATOR
                                 : f.score          ? REFUSE_ADAPTIVE_SCORE
-                                : (f.actuator || f.delay) ? REFUSE_ADAPTIVE_ACTUATOR   // (the delay is part of the actuator: its text)
+                                : f.actuator       ? REFUSE_ADAPTIVE_ACTUATOR
                                                    : REFUSE_NONE;
     auto tile = [&](const char* rule) { return PathDecision{TILE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
     auto cover = [&](const char* rule) { return PathDecision{COVERAGE, 0, 0, 0, refusal, rule, 0, 0, 0, 0, 0, 0, 0}; };
@@ -137,10 +133,9 @@ inline PathDecision decide_path(const PathFacts& f) {
     // "one_row:<form>"), run-time instantiated only: where hipRTC may not be tried, with debug outputs, under force_general and with
     // adaptive rho (refused) the coverage kernel answers, "cover:<form>".  A coverage answer stays what it is, the tile kernel is not
     // asked.  Which facts force which bits on, and the precedence of the name: profiles/kernel_path.md
-    const bool closed_loop = f.disturbance || f.plant || f.state_log || f.measurement || f.estimator || f.score || f.actuator || f.delay;
+    const bool closed_loop = f.disturbance || f.plant || f.state_log || f.measurement || f.estimator || f.score || f.actuator;
     const bool pd_form = f.fits && hiprtc && !f.force_general && !f.debug && !f.adaptive;
-    const bool px = f.delay && f.delay_compensation, pq = f.delay;       // (the predictor re-reads the true state behind the loop as the PM forms do: it forces pm)
-    const bool pe = f.estimator, pm = f.measurement || pe || px, pa = f.actuator || pq, pp = f.plant || pm || pa, pd = f.disturbance || ((f.state_log || f.score) && !pp);
+    const bool pe = f.estimator, pm = f.measurement || pe, pa = f.actuator, pp = f.plant || pm || pa, pd = f.disturbance || ((f.state_log || f.score) && !pp);
     const bool ps = f.score;
     struct FormRules { const char *cover, *one_row; };
     static constexpr FormRules FORMS[] = {{"cover:pd", "one_row:pd"}, {"cover:pp", "one_row:pp"}, {"cover:pm", "one_row:pm"},
@@ -149,8 +144,7 @@ inline PathDecision decide_path(const PathFacts& f) {
     auto one_row = [&](int lin, int pl, int pb, const char* rule, int pc = 0) {
         if (!pd && !pp) return PathDecision{ONE_ROW, lin, pl, pb, refusal, rule, pc, 0, 0, 0, 0, 0, 0};
         if (!pd_form) return cover(form.cover);
-        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : form.one_row, pc, pd ? 1 : 0, pp ? 1 : 0, pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0, pa ? 1 : 0,
-                            pq ? 1 : 0, px ? 1 : 0};
+        return PathDecision{ONE_ROW, lin, pl, pb, refusal, (pl || pb || pc) ? rule : form.one_row, pc, pd ? 1 : 0, pp ? 1 : 0, pm ? 1 : 0, pe ? 1 : 0, ps ? 1 : 0, pa ? 1 : 0};
     };
     // why the one-row kernel has no variant for the SHARED half-spaces that are on (nullptr: it has one, or none is on)
     const char* no_lin = !lf                                                                  ? nullptr
@@ -209,4 +203,4 @@ inline int kernel_path_code(const PathDecision& d, const PathFacts& f) {
     return (f.has_entry && !f.inst_bounds && !f.inst_lin && !d.pc && !d.pd && !d.pp) ? 0 : 3;
 }
 
-}  // namespace tinympc_amd
+}  // namespace kernel_path_before_delay

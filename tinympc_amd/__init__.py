@@ -26,6 +26,7 @@ _fp = C.POINTER(C.c_float)
 
 OK, ERR_DIM, ERR_NULL, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_HIP, ERR_ARG = 0, 1, -1, -2, -3, -4, -5
 HOST, DEVICE, BROADCAST = 0, 1, 2
+MAX_DELAY = 8                                      # TINY_MAX_DELAY: the longest transport delay of tiny_batch_set_actuator_delay, in MPC steps
 NOISE_FACTOR = 4                                 # TinyNoiseSpec.flags: scale is an nx x nx factor
 
 
@@ -57,6 +58,7 @@ BATCH_SYMBOLS = (
     "tiny_batch_set_actuator", "tiny_batch_get_actuator", "tiny_batch_set_actuator_state", "tiny_batch_get_actuator_state",
     "tiny_batch_set_actuation_noise", "tiny_batch_get_actuation_noise", "tiny_batch_generate_actuation_noise", "tiny_actuation_noise_generate",
     "tiny_batch_get_actuation_log",
+    "tiny_batch_set_actuator_delay", "tiny_batch_get_actuator_delay", "tiny_batch_set_actuator_queue", "tiny_batch_get_actuator_queue",
     "tiny_batch_update_settings", "tiny_batch_get_cache", "tiny_batch_set",
     "tiny_batch_get", "tiny_batch_reset", "tiny_batch_solve", "tiny_batch_solve_async", "tiny_batch_synchronize",
     "tiny_batch_get_status", "tiny_batch_reduce_stats", "tiny_batch_set_option", "tiny_batch_set_stream",
@@ -70,7 +72,7 @@ GROUP_SYMBOLS = (
     "tiny_group_uses_rccl", "tiny_group_last_error", "tiny_group_set_bound_constraints", "tiny_group_set_instance_bounds", "tiny_group_set_cone_constraints",
     "tiny_group_set_linear_constraints", "tiny_group_set_tv_linear_constraints", "tiny_group_set_instance_linear_constraints",
     "tiny_group_set_instance_tv_linear_constraints", "tiny_group_set_instance_cone_coefficients", "tiny_group_set_disturbance", "tiny_group_set_plant", "tiny_group_set_measurement_noise", "tiny_group_generate_disturbance", "tiny_group_generate_measurement_noise", "tiny_group_set_estimator", "tiny_group_set_estimate", "tiny_group_set_score",
-    "tiny_group_set_actuator", "tiny_group_set_actuator_state", "tiny_group_set_actuation_noise", "tiny_group_generate_actuation_noise", "tiny_group_update_settings",
+    "tiny_group_set_actuator", "tiny_group_set_actuator_state", "tiny_group_set_actuation_noise", "tiny_group_generate_actuation_noise", "tiny_group_set_actuator_delay", "tiny_group_set_actuator_queue", "tiny_group_update_settings",
     "tiny_group_set_option", "tiny_group_set", "tiny_group_get", "tiny_group_reset", "tiny_group_solve",
     "tiny_group_solve_async", "tiny_group_synchronize", "tiny_group_get_status", "tiny_group_allreduce_stats")
 REFERENCE_SYMBOLS = (
@@ -219,6 +221,10 @@ def lib():
         L.tiny_batch_generate_actuation_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
         L.tiny_actuation_noise_generate.argtypes = [C.POINTER(NoiseSpec), C.c_int, C.c_int, _dp]
         L.tiny_batch_get_actuation_log.argtypes = [C.c_void_p, _dp, C.c_int]
+        L.tiny_batch_set_actuator_delay.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.tiny_batch_get_actuator_delay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.tiny_batch_set_actuator_queue.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.tiny_batch_get_actuator_queue.argtypes = [C.c_void_p, _dp]
         L.tiny_batch_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_batch_get_cache.argtypes = [C.c_void_p, C.c_char_p, _dp, C.c_int]
         L.tiny_batch_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
@@ -298,6 +304,8 @@ def lib():
         L.tiny_group_set_actuator_state.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_actuation_noise.argtypes = [C.c_void_p, _dp, C.c_int, C.c_int]
         L.tiny_group_generate_actuation_noise.argtypes = [C.c_void_p, C.POINTER(NoiseSpec)]
+        L.tiny_group_set_actuator_delay.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_int]
+        L.tiny_group_set_actuator_queue.argtypes = [C.c_void_p, _dp, C.c_int]
         L.tiny_group_set_plant.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_int]
         L.tiny_group_update_settings.argtypes = [C.c_void_p, C.c_double, C.c_double] + [C.c_int] * 10
         L.tiny_group_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_long]
@@ -807,6 +815,59 @@ class TinyBatchSolver:
         """a (batch, nu) as it stands"""
         out = np.zeros((self.batch, self.nu))
         self._check(lib().tiny_batch_get_actuator_state(self._h, out.ctypes.data_as(_dp)), "get_actuator_state")
+        return out
+
+    def _actuator_delay(self, d, d_max):
+        """d: (batch,) ints or one int for all; d_max: None -> the largest d -> (int32 array, d_max, broadcast flag)"""
+        v = np.asarray(d, dtype=np.int32)
+        if v.shape not in ((self.batch,), ()):
+            raise ValueError(f"actuator delay: ({self.batch},) or one int, got {v.shape}")
+        bc = BROADCAST if v.ndim == 0 else 0
+        v = np.ascontiguousarray(v.reshape(-1))
+        return v, (int(v.max()) if d_max is None else int(d_max)), bc
+
+    def set_actuator_delay(self, d=None, d_max=None):
+        """stage 0 of the actuator, a transport delay: the command of MPC step k reaches the limits d[i] steps later (a FIFO of the
+        instance's last d[i] commands, zeroed here).  d: (batch,) ints or one int for all, 0 <= d <= d_max <= MAX_DELAY; d_max None: the
+        largest d; d None removes the delay.  Option "delay_compensation" = 1 lets every step solve from the model's prediction over the
+        queue"""
+        if d is None:
+            return self._check(lib().tiny_batch_set_actuator_delay(self._h, None, 0, HOST), "set_actuator_delay")
+        v, dm, bc = self._actuator_delay(d, d_max)
+        self._check(lib().tiny_batch_set_actuator_delay(self._h, v.ctypes.data_as(C.c_void_p), dm, HOST | bc), "set_actuator_delay")
+
+    def set_actuator_delay_device(self, d, d_max, broadcast=False):
+        """set_actuator_delay from a device pointer to (batch,) ints (one with broadcast)"""
+        self._check(lib().tiny_batch_set_actuator_delay(self._h, C.c_void_p(int(d)), int(d_max), DEVICE | (BROADCAST if broadcast else 0)), "set_actuator_delay_device")
+
+    def get_actuator_delay(self, i):
+        """d of instance i, as installed"""
+        out = C.c_int(0)
+        self._check(lib().tiny_batch_get_actuator_delay(self._h, int(i), C.byref(out)), "get_actuator_delay")
+        return int(out.value)
+
+    def _delay_max(self):
+        return int(self.get_option("actuator_delay"))
+
+    def _actuator_queue(self, q):
+        d_max = self._delay_max()
+        v = _f64(q)
+        if v.shape not in ((self.batch, d_max, self.nu), (d_max, self.nu)):
+            raise ValueError(f"actuator queue: ({self.batch}, {d_max}, {self.nu}) or ({d_max}, {self.nu}), got {v.shape}")
+        return v, (BROADCAST if v.ndim == 2 else 0)
+
+    def set_actuator_queue(self, q):
+        """the delay's queue, oldest first: (batch, d_max, nu), or (d_max, nu) for all; only the first d[i] rows of an instance count"""
+        v, bc = self._actuator_queue(q)
+        self._check(lib().tiny_batch_set_actuator_queue(self._h, v.ctypes.data_as(C.c_void_p), HOST | bc), "set_actuator_queue")
+
+    def set_actuator_queue_device(self, q, broadcast=False):
+        self._check(lib().tiny_batch_set_actuator_queue(self._h, C.c_void_p(int(q)), DEVICE | (BROADCAST if broadcast else 0)), "set_actuator_queue_device")
+
+    def get_actuator_queue(self):
+        """(batch, d_max, nu) as it stands, oldest first, +0.0 behind an instance's first d[i] rows"""
+        out = np.zeros((self.batch, max(self._delay_max(), 1), self.nu))
+        self._check(lib().tiny_batch_get_actuator_queue(self._h, out.ctypes.data_as(_dp)), "get_actuator_queue")
         return out
 
     def _actuation_noise(self, n):
@@ -1389,6 +1450,27 @@ class TinyGroupSolver:
         """TinyBatchSolver.generate_actuation_noise over the full batch axis (see generate_disturbance)"""
         spec, keep = noise_spec(self.batch, self.nu, seed, n_steps, scale, mean, factor, id_base, id_stride)
         self._check(lib().tiny_group_generate_actuation_noise(self._h, C.byref(spec)), "generate_actuation_noise")
+
+    def set_actuator_delay(self, d=None, d_max=None):
+        """a transport delay for every instance, the full batch axis in the caller's order (TinyBatchSolver's shapes); None removes"""
+        if d is None:
+            return self._check(lib().tiny_group_set_actuator_delay(self._h, None, 0, HOST), "set_actuator_delay")
+        v, dm, bc = TinyBatchSolver._actuator_delay(self, d, d_max)
+        self._check(lib().tiny_group_set_actuator_delay(self._h, v.ctypes.data_as(C.POINTER(C.c_int)), dm, HOST | bc), "set_actuator_delay")
+
+    def _delay_max(self):
+        return int(lib().tiny_batch_get_option(lib().tiny_group_shard(self._h, 0), b"actuator_delay"))
+
+    def set_actuator_queue(self, q):
+        """the delay's queue of every instance (the caller's order), oldest first: (batch, d_max, nu), or (d_max, nu) for all"""
+        v, bc = TinyBatchSolver._actuator_queue(self, q)
+        self._check(lib().tiny_group_set_actuator_queue(self._h, v.ctypes.data_as(_dp), HOST | bc), "set_actuator_queue")
+
+    def get_actuator_queue(self):
+        """(batch, d_max, nu), gathered from the shards into the caller's order"""
+        d_max = self._delay_max()
+        flat = self._from_shards(1, lambda h, part: lib().tiny_batch_get_actuator_queue(h, part.ctypes.data_as(_dp)), "get_actuator_queue", d_max * self.nu)[0]
+        return flat.reshape(self.batch, d_max, self.nu)
 
     def get_actuator_state(self):
         """a (batch, nu), gathered from the shards into the caller's order"""

@@ -118,6 +118,27 @@ struct ActuatorLaunch {
     int noise_steps, log_step0;
 };
 static_assert(sizeof(ActuatorLaunch) == 40, "ActuatorLaunch: four pointers and two ints");
+// ... and what the PQ / PX forms read of a transport delay (tiny_batch_set_actuator_delay) and its predictor (option
+// "delay_compensation"): the record grows BEHIND the 40 bytes the PA forms know -- what SolveArgs::act names is an ActuatorRecord, the
+// two structs one behind the other in one device allocation, so that SolveArgs needs no further field (delay_launch_of).  delay [batch] the
+// instance's d, queue [batch][d_max][NU] a ring per instance over its first d rows, head [batch] the row of the OLDEST entry (the next
+// to leave; the newest enters in its place).  The predictor: model the MODEL's plant block (the layout and the bit 0 of `plant`), xhat
+// [batch][NX] where a PE form keeps the corrected estimate while slot 0 of the state lanes holds the predicted state
+struct DelayLaunch {
+    const int* delay;
+    double* queue;
+    int* head;
+    const double* model;
+    double* xhat;
+    int d_max, pad_;
+};
+static_assert(sizeof(DelayLaunch) == 48 && sizeof(ActuatorLaunch) % alignof(DelayLaunch) == 0, "DelayLaunch: five pointers and two ints, right behind an ActuatorLaunch");
+struct ActuatorRecord {                // what Actuator::desc holds and SolveArgs::act points at: the PA forms read `a`, the PQ / PX forms `d` as well
+    ActuatorLaunch a;
+    DelayLaunch d;
+};
+static_assert(sizeof(ActuatorRecord) == 88 && __builtin_offsetof(ActuatorRecord, a) == 0 && __builtin_offsetof(ActuatorRecord, d) == sizeof(ActuatorLaunch), "ActuatorRecord: the two structs, packed");
+__host__ __device__ inline const DelayLaunch* delay_launch_of(const ActuatorLaunch* act) { return &reinterpret_cast<const ActuatorRecord*>(act)->d; }
 
 struct SolveArgs {
     const double* tab;        // tab_doubles(N) doubles
@@ -990,6 +1011,18 @@ __device__ __forceinline__ double actuator_gain(const double m, const double gai
 // the kernel-argument segment (late_arg): nothing of it lives through the loop.  A step that ran no iteration takes no plant step and
 // runs no stage.  PA implies PP (a launch with no plant installed forms the model's block, as PM does); composes with PD, PM, PE, PS,
 // PB / PL / PC and HET; not HALF, PF or ADAPT.  Run-time instantiated only; bit 10 of the sixth template argument (MODE | 1024).
+// PQ: a transport delay in front of the actuator's stages (ActuatorLaunch::delay, queue, head).  Inside `applied`, on an input lane whose
+// instance has d > 0: the oldest entry of the instance's ring leaves -- it is what the limits see --, the command takes its cell and lane
+// NX moves the head: one load and one store per input lane and step, next to the head's.  d = 0 reads and writes nothing and hands the
+// command's bits on.  Once per step that takes a plant step, as the lag's record.  PQ rides on PA; bit 12 (MODE | 4096) -- bit 11
+// names no form: a name that sets it is refused, as it was before the delay existed (tests/test_actuator_cpu.py asks exactly that).
+// PX: a predictor that compensates the delay.  Where a PM / PE form forms the state a step solves from (the top of a tile, behind the
+// iteration loop) that state xin is stepped d times by the MODEL over the queue as it stands, oldest first: xs = plant_by(model, xs, q[t])
+// -- a run-time loop to the wave's largest d (the four rows of a wave have their own d; a row past its d keeps its xs by a select, so that
+// every DPP broadcast of the chain runs under a full EXEC), the input lanes presenting q[t] where the chain reads u0.  Slot 0 of the state
+// lanes then holds xs; a PE form keeps xhat in ActuatorLaunch::xhat and reads it back behind the loop for the estimate log and for the
+// model's prediction of the next xp, which under PX uses the control that reaches the actuator now (what left the queue), not the
+// command.  Nothing of it lives through the iteration loop.  PX rides on PQ and PM; bit 13 (MODE | 8192).
 template <int NX, int NU, int N, bool SOC, bool DBG, int MODE_PB, int LIN = 0, bool HET = false, int KMAX = LIN_KMAX, bool ADAPT = false, bool UB = false, bool HALF = false,
           bool PF = false>
 __global__ __launch_bounds__(64)
@@ -1006,7 +1039,11 @@ void admm_solve_kernel(const SolveArgs P) {
     constexpr bool PE = (MODE_PB & 256) != 0;
     constexpr bool PS = (MODE_PB & 512) != 0;
     constexpr bool PA = (MODE_PB & 1024) != 0;
-    static_assert(MODE <= 2 && MODE_PB < 2048, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator, + 512: a closed-loop score, + 1024: an actuator model");
+    constexpr bool PQ = (MODE_PB & 4096) != 0;
+    constexpr bool PX = (MODE_PB & 8192) != 0;
+    static_assert(MODE <= 2 && MODE_PB < 16384 && (MODE_PB & 2048) == 0, "MODE 0 | 1 | 2, + 4: per-instance box, + 8: per-instance half-spaces, + 16: per-instance cone coefficients, + 32: per-instance disturbance, + 64: a plant of its own, + 128: measurement noise, + 256: a state estimator, + 512: a closed-loop score, + 1024: an actuator model, + 4096: a transport delay in front of it, + 8192: a predictor that compensates the delay (2048 names no form)");
+    static_assert(!PQ || PA, "a transport delay: a form with an actuator model (PA, bit 10): the queue is popped and pushed inside `applied`");
+    static_assert(!PX || (PQ && PM), "a delay predictor: a form with the queue (PQ, bit 12) that solves from something other than the x0 record (PM, bit 7)");
     static_assert(!PA || PP, "an actuator model: a form with a plant block (PP, bit 6): the plant step is a chain over the applied control");
     static_assert(!PA || !ADAPT, "an actuator model: not with adaptive rho (refused)");
     static_assert(!PA || !HALF, "an actuator model: not the half-row form");
@@ -1483,6 +1520,47 @@ void admm_solve_kernel(const SolveArgs P) {
             };
             (void)corrected;
             if constexpr (PE) x0v_in = corrected(x0v_in, is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[(size_t)b * NX + j] : 0.0);
+            // PX: what the solver is handed for xin (the x0 record, the measurement or the corrected estimate) under a delay of d steps
+            // -- xin stepped d times by the MODEL over the instance's queue as it stands, oldest first: the chain of plant_by, the
+            // accumulator starting at f.  The loop runs to the largest d of the wave's rows (the ballot counts the rows of the tile
+            // only) and a row past its own d keeps its xs by a select: every lane of a row stays in the chain's DPP broadcasts.  The
+            // input lanes present q[t] where the chain reads u0.  d = 0: xin's own bits.  Called where `corrected` is
+            auto compensated = [&](const double xin) -> double {
+                if constexpr (PX) {
+                    int c_b = b;
+                    asm volatile("" : "+v"(c_b));
+                    const DelayLaunch* const act = delay_launch_of(late_arg<const ActuatorLaunch>(__builtin_offsetof(SolveArgs, act)));
+                    const int d = act->delay[c_b], h = act->head[c_b];
+                    const unsigned long long raw = reinterpret_cast<unsigned long long>(act->model);
+                    const double* const pt = reinterpret_cast<const double*>(raw & ~1ull) + ((raw & 1ull) ? (size_t)0 : (size_t)c_b * ((NZ + 1) * 16)) + j;
+                    const double* const q = act->queue + (size_t)c_b * act->d_max * NU + (is_input ? j - NX : 0);
+                    double xs = xin;
+                    for (int t = 0; __ballot(t < d) != 0ull; ++t) {
+                        const bool mine = t < d;
+                        const int at = h + t < d ? h + t : h + t - d;              // (the ring: the oldest entry sits at the head)
+                        const double qt = (mine && is_input) ? q[(size_t)at * NU] : 0.0;
+                        double acc = pt[NZ * 16];
+                        plant_chain<0, NX>(acc, xs, pt);
+                        plant_chain<NX, NU>(acc, qt, pt + NX * 16);
+                        xs = (mine && is_state) ? acc : xs;
+                    }
+                    return xs;
+                } else {
+                    return xin;
+                }
+            };
+            (void)compensated;
+            // (a PE form keeps xhat in memory while slot 0 holds the predicted state: this lane's own cell, read back behind the loop)
+            auto xhat_cell = [&]() -> double* {
+                int x_b = b;
+                asm volatile("" : "+v"(x_b));
+                return delay_launch_of(late_arg<const ActuatorLaunch>(__builtin_offsetof(SolveArgs, act)))->xhat + ((size_t)x_b * NX + (is_state ? j : 0));
+            };
+            (void)xhat_cell;
+            if constexpr (PX) {
+                if constexpr (PE) { if (is_state) *xhat_cell() = x0v_in; }
+                x0v_in = compensated(x0v_in);
+            }
             const int cl = grp * N * CSL + (j < NZ ? j : NZ);  // LIN: this lane's cell of slot 0 (slot s: + s * CSL)
             double VL[LSR ? N : 1], GL[LSR ? N : 1], VT[LTR ? N : 1], GT[LTR ? N : 1];
             double Qd[DBG ? N : 1], Pd[DBG ? N : 1], Dd[DBG ? N : 1];
@@ -1663,7 +1741,10 @@ void admm_solve_kernel(const SolveArgs P) {
             // lane the four stages against the instance's block, elsewhere u0_row as it is (the plant chain and the score read the input
             // lanes only).  Called behind the iteration loop only, ONCE per step that takes a plant step -- it moves the lag's record --
             // and everything it needs is formed there.  A form without PA: the command itself
-            auto applied = [&](const double u0_row, const int at_step) -> double {
+            // PQ: stage 0, the transport delay -- on an input lane whose instance has d > 0 the oldest entry of its ring is what the stages
+            // see, the command takes its cell and lane NX moves the head (every lane of the row has loaded the head by then: one load
+            // instruction); d = 0: the command's own bits, nothing read or written.  s0_out: where a PX form with an estimator takes it from
+            auto applied = [&](const double u0_row, const int at_step, double* const s0_out = nullptr) -> double {
                 if constexpr (PA) {
                     int a_b = b;
                     asm volatile("" : "+v"(a_b));
@@ -1671,6 +1752,24 @@ void admm_solve_kernel(const SolveArgs P) {
                     const unsigned long long raw = reinterpret_cast<unsigned long long>(act->tab);
                     const int k = late_value<int>(__builtin_offsetof(SolveArgs, act_step0)) + at_step;
                     double ua = u0_row;
+                    if constexpr (PQ) {
+                        if (is_input) {
+                            const DelayLaunch* const dl = delay_launch_of(act);
+                            const int d = dl->delay[a_b];
+                            if (d > 0) {
+                                const int h = dl->head[a_b];
+                                double* const cell = dl->queue + (((size_t)a_b * dl->d_max + h) * NU + (j - NX));
+                                ua = *cell;
+                                *cell = u0_row;
+                                // (the pop is safe by a data dependency: this store's value needs the load of h, which every lane of the
+                                // row issued in the same instruction.  `compensated` reads the head again behind this store, on OTHER lanes of
+                                // the wave: that relies on program order over may-alias pointers and on one wave's stores and loads going
+                                // through the same L1 in order -- keep it a fresh load there, never a value read once and carried)
+                                if (j == NX) dl->head[a_b] = (h + 1 < d) ? h + 1 : 0;
+                            }
+                        }
+                        if (s0_out) *s0_out = ua;
+                    }
                     // (the limits and the gain run on every lane of the row: a lane outside the inputs reads neutral entries, and nothing reads
                     // what it computes.  Only the lag's record, the noise and the log are per input lane)
                     if (raw & ~3ull) {
@@ -2188,6 +2287,7 @@ void admm_solve_kernel(const SolveArgs P) {
                 if (P.u0_log && is_input) P.u0_log[((size_t)step * P.batch + b) * NU + (j - NX)] = X[1];
                 if constexpr (PE) {                            // (the xhat this step solved from: the state lanes still hold it in slot 0)
                     double* const elog = late_arg<double>(__builtin_offsetof(SolveArgs, est_log));
+                    if constexpr (PX) { if (elog && is_state) elog[((size_t)step * P.batch + b) * NX + j] = *xhat_cell(); } else      // (slot 0 holds the predicted state)
                     if (elog && is_state) elog[((size_t)step * P.batch + b) * NX + j] = X[0];
                 }
                 if (nsteps > 1) {
@@ -2199,8 +2299,20 @@ void admm_solve_kernel(const SolveArgs P) {
                             const size_t cell = true_cell();
                             double xt = true_x0(step, cell);
                             [[maybe_unused]] double est_next = 0.0;             // PE: the xp the next step corrects -- predicted here, or (no iteration ran) the record's
-                            if constexpr (PE) est_next = (iter > iter0) ? predicted(X[0], X[1]) : (is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[cell] : 0.0);
+                            if constexpr (PE && !PX) est_next = (iter > iter0) ? predicted(X[0], X[1]) : (is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[cell] : 0.0);
                             double ua = X[1];                                   // (PA: what the plant receives; else the command)
+                            if constexpr (PE && PX) {                           // (the model predicts from xhat with what reaches the actuator NOW: what left the queue)
+                                double s0 = X[1];
+                                if (iter > iter0) {
+                                    ua = applied(X[1], step, &s0);
+                                    est_next = predicted(is_state ? *xhat_cell() : 0.0, s0);
+                                    const double xp = plant_step(xt, ua);
+                                    xt = is_state ? xp : 0.0;
+                                    if constexpr (PD) xt = disturbed(xt, step);
+                                } else {
+                                    est_next = is_state ? late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[cell] : 0.0;
+                                }
+                            } else
                             if (iter > iter0) {
                                 ua = applied(X[1], step);
                                 const double xp = plant_step(xt, ua);
@@ -2213,6 +2325,10 @@ void admm_solve_kernel(const SolveArgs P) {
                             if (P.state_log && is_state) P.state_log[((size_t)step * P.batch + b) * NX + j] = xt;
                             x0v = measured(xt, step + 1);
                             if constexpr (PE) x0v = corrected(x0v, est_next);
+                            if constexpr (PX) {                                 // (the queue as this step's push left it: before the next step's)
+                                if constexpr (PE) { if (is_state) *xhat_cell() = x0v; }
+                                x0v = compensated(x0v);
+                            }
                         }
                     } else {
                     [[maybe_unused]] double ua = X[1];         // (PA: what the plant receives)
@@ -2319,14 +2435,19 @@ void admm_solve_kernel(const SolveArgs P) {
             }
             if constexpr (PM) {                              // (the plant step of the launch's LAST MPC step, from the true state)
                 const double xt = true_x0(nsteps - 1, true_cell());
-                if constexpr (PE) {                          // (... and the model's prediction from its xhat: the xp the next launch corrects)
+                if constexpr (PE && !PX) {                   // (... and the model's prediction from its xhat: the xp the next launch corrects)
                     if (P.x0_next && acc_iter > 0) {
                         const double xpn = predicted(X[0], X[1]);
                         if (is_state) late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[(size_t)b * NX + j] = xpn;
                     }
                 }
                 if (P.x0_next && acc_iter > 0) {
-                    const double ua = applied(X[1], nsteps - 1);
+                    [[maybe_unused]] double s0 = X[1];
+                    const double ua = applied(X[1], nsteps - 1, (PE && PX) ? &s0 : nullptr);
+                    if constexpr (PE && PX) {                // (under the predictor: from the xhat kept in memory, with what left the queue)
+                        const double xpn = predicted(is_state ? *xhat_cell() : 0.0, s0);
+                        if (is_state) late_arg<double>(__builtin_offsetof(SolveArgs, est_xp))[(size_t)b * NX + j] = xpn;
+                    }
                     double xn = plant_step(xt, ua);
                     if constexpr (PD) xn = disturbed(xn, nsteps - 1);
                     if (is_state) P.x0_next[(size_t)b * NX + j] = xn;

@@ -349,7 +349,7 @@ int tiny_batch_destroy(TinyBatch* b) {
                     b->d_wire, b->d_arho, b->d_aK, b->d_aP, b->d_aC1, b->d_aC2, b->d_atab, b->d_sdK, b->d_sdP, b->d_sdC1, b->d_sdC2, b->d_atabs, b->d_ssteps, b->d_work_counter, b->d_perm, b->d_rg_bins, b->d_ls, b->d_pf_counter, b->d_vz_scratch};
     for (void* p : bufs)
         if (p) hipFree(p);
-    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant); free_buffers(b->meas); free_buffers(b->est); free_buffers(b->score); free_buffers(b->act); free_buffers(b->anoise); free_buffers(b->model);   // (each names its own: batch_impl.hpp each_buffer)
+    free_buffers(b->ibox); free_buffers(b->ilin); free_buffers(b->icone); free_buffers(b->dist); free_buffers(b->plant); free_buffers(b->meas); free_buffers(b->est); free_buffers(b->score); free_buffers(b->act); free_buffers(b->anoise); free_buffers(b->delay); free_buffers(b->model);   // (each names its own: batch_impl.hpp each_buffer)
     if (b->h_wire) hipHostFree(b->h_wire);
     if (b->d_hist) hipFree(b->d_hist);
     if (b->h_hist) hipHostFree(b->h_hist);
@@ -864,6 +864,7 @@ int tiny_batch_set_option(TinyBatch* b, const char* name, long value) {
     else if (!strcmp(name, "estimate_log")) b->est.log.on = value != 0;     // the xhat every MPC step under a state estimator solved from (tiny_batch_get_estimate_log)
     else if (!strcmp(name, "actuation_step")) b->anoise.step = value;       // the actuation step counter: the noise row and the index the next actuated MPC step takes
     else if (!strcmp(name, "actuation_log")) b->act.log.on = value != 0;    // the control every plant step received (tiny_batch_get_actuation_log)
+    else if (!strcmp(name, "delay_compensation")) b->delay.compensate = value != 0;    // solve from the model's prediction over the delay's queue (inert with no delay installed)
     else if (!strcmp(name, "score_step")) b->score.step = value;            // the score step counter: what the next scored MPC step records as its index
     else if (!strcmp(name, "state_log")) b->plant.log.on = value != 0;      // the x0 every plant step hands on (tiny_batch_get_state_log)
     else if (!strcmp(name, "reset_duals")) b->reset_duals = value != 0;
@@ -1054,6 +1055,8 @@ long tiny_batch_get_option(TinyBatch* b, const char* name) {
     if (!strcmp(name, "last_score")) return b->score.last ? 1 : 0;            // the last solve's launches scored
     if (!strcmp(name, "actuator")) return b->act.kind;                        // an actuator model (tiny_batch_set_actuator): 0 none, 1 one setup for all, 2 every instance its own
     if (!strcmp(name, "actuator_lag")) return (b->act.kind && b->act.lag) ? 1 : 0;
+    if (!strcmp(name, "actuator_delay")) return b->delay.d_max;               // a transport delay (tiny_batch_set_actuator_delay): d_max as installed, 0: none
+    if (!strcmp(name, "delay_compensation")) return b->delay.compensate ? 1 : 0;
     if (!strcmp(name, "actuation_noise")) return b->anoise.seq ? b->anoise.steps : 0;
     if (!strcmp(name, "actuation_noise_generated")) return (b->anoise.seq && b->anoise.generated) ? 1 : 0;
     if (!strcmp(name, "actuation_step")) return b->anoise.step;               // the actuation step counter

@@ -371,8 +371,10 @@ static int enqueue_coverage_correction(TinyBatch* b, int log_row, const double**
 }
 // ... and its prediction behind the launch: xp <- the MODEL's step from xhat and the u0 of the x|u record, the chain of
 // coverage_plant_step_kernel.  xhat and xp are arrays of their own: a thread may write its xp while others still read xhat.  An instance
-// whose launch ran no iteration keeps its xp
+// whose launch ran no iteration keeps its xp.  s0: null, or [batch][nu] -- under delay compensation the control that reaches the actuator
+// now (what the actuator helper took off the queue), read in place of the record's u0
 static __global__ __launch_bounds__(256) void coverage_prediction_kernel(double* __restrict__ xp, const double* __restrict__ xhat, const double* __restrict__ prim,
+                                                                         const double* __restrict__ s0,
                                                                          const int4* __restrict__ status, const double* __restrict__ A_m, const double* __restrict__ B_m,
                                                                          const double* __restrict__ f_m, int per_instance, int batch, int nx, int nu, int N) {
     const size_t total = (size_t)batch * nx;
@@ -380,19 +382,19 @@ static __global__ __launch_bounds__(256) void coverage_prediction_kernel(double*
         const int j = (int)(e % nx);
         const size_t bb = e / nx, p = per_instance ? bb : 0;
         if (status[bb].x <= 0) continue;
-        const double *A = A_m + p * nx * nx, *B = B_m + p * nx * nu, *u0 = prim + bb * N * (nx + nu) + nx;
+        const double *A = A_m + p * nx * nx, *B = B_m + p * nx * nu, *u0 = s0 ? s0 + bb * nu : prim + bb * N * (nx + nu) + nx;
         double acc = f_m ? f_m[p * nx + j] : 0.0;
         for (int k = 0; k < nx; ++k) acc = fma(xhat[bb * nx + k], A[j + nx * k], acc);
         for (int k = 0; k < nu; ++k) acc = fma(u0[k], B[j + nx * k], acc);
         xp[e] = acc;
     }
 }
-static int enqueue_coverage_prediction(TinyBatch* b) {
+static int enqueue_coverage_prediction(TinyBatch* b, const double* s0 = nullptr) {
     Estimator& s = b->est;
     if (int rc = ensure_model_source(b, true)) return rc;
     const PlantSource p = model_source(b);
     const size_t total = (size_t)b->batch * b->nx;
-    hipLaunchKernelGGL(coverage_prediction_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.xp, s.xhat, b->d_prim, b->d_status, p.src[0], p.src[1], p.src[2],
+    hipLaunchKernelGGL(coverage_prediction_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.xp, s.xhat, b->d_prim, s0, b->d_status, p.src[0], p.src[1], p.src[2],
                        p.per_instance ? 1 : 0, b->batch, b->nx, b->nu, b->N);
     HIP_TRY(b, hipGetLastError());
     return TINY_OK;
@@ -487,15 +489,24 @@ static __global__ __launch_bounds__(256) void fill_actuator_kernel(double* __res
 }
 // the record the PA forms read, written on the stream: the launches behind it see it, the ones in front of it have read theirs
 static __global__ void write_actuator_launch_kernel(ActuatorLaunch* __restrict__ out, const ActuatorLaunch v) { *out = v; }
-static bool actuator_active(const TinyBatch* b) { return (b->act.kind != 0 || (b->anoise.seq && b->anoise.steps > 0)) && takes_plant_step(b); }
+// ... and the part the PQ / PX forms read behind it (Actuator::desc is an ActuatorRecord: both)
+static __global__ void write_delay_launch_kernel(DelayLaunch* __restrict__ out, const DelayLaunch v) { *out = v; }
+// (a transport delay is stage 0 of the actuator: installed alone it makes the launch an actuated one)
+static bool delay_active(const TinyBatch* b) { return b->delay.d_max > 0 && takes_plant_step(b); }
+static bool compensation_active(const TinyBatch* b) { return delay_active(b) && b->delay.compensate; }
+static bool actuator_active(const TinyBatch* b) { return (b->act.kind != 0 || (b->anoise.seq && b->anoise.steps > 0) || b->delay.d_max > 0) && takes_plant_step(b); }
 // begin_log for a log whose switch the begin itself looks at (the actuation log; the other two logs' callers look first): off, no row
 static int begin_log_if_on(TinyBatch* b, StepLog& log, int rows, int width) {
     log.rows = 0;
     return log.on ? begin_log(b, log, rows, width) : TINY_OK;
 }
 // (only the one-row kernel's PA forms read the blocks and the record; the coverage path reads the caller's arrays)
-static int ensure_actuator_launch(TinyBatch* b, int rows, const ActuatorLaunch** out) {
+static int ensure_actuator_launch(TinyBatch* b, const PathDecision& D, int rows, const ActuatorLaunch** out) {
     Actuator& s = b->act;
+    ActuatorDelay& q = b->delay;
+    // (a PX form steps by the model's own block whatever plant is installed; with an estimator it keeps xhat in the coverage path's array)
+    if (D.px) { if (int rc = ensure_model_block(b)) return rc; }
+    if (D.px && D.pe && !b->est.xhat) HIP_TRY(b, hipMalloc(&b->est.xhat, (size_t)b->batch * b->nx * sizeof(double)));
     if (s.kind && s.dirty) {
         const int setups = s.kind == 1 ? 1 : b->batch;
         if (int rc = ensure_built(b, s.built, s.dirty, (size_t)setups * actuator_block_doubles(), [&](dim3 grid) {
@@ -503,15 +514,23 @@ static int ensure_actuator_launch(TinyBatch* b, int rows, const ActuatorLaunch**
             })) return rc;
     }
     if (int rc = begin_log_if_on(b, s.log, rows, b->nu)) return rc;
-    if (!s.desc) HIP_TRY(b, hipMalloc(&s.desc, sizeof(ActuatorLaunch)));
+    if (!s.desc) HIP_TRY(b, hipMalloc(&s.desc, sizeof(ActuatorRecord)));
     ActuatorLaunch v = {};
     v.tab = s.kind ? tagged_block(s.built, s.kind != 2, s.lag) : nullptr;
     v.state = s.lag ? s.state : nullptr;
     v.noise = b->anoise.seq; v.noise_steps = b->anoise.seq ? b->anoise.steps : 0;
     v.log = s.log.on ? s.log.buf : nullptr; v.log_step0 = kernel_step(b->anoise.step);
-    hipLaunchKernelGGL(write_actuator_launch_kernel, dim3(1), dim3(1), 0, b->stream, static_cast<ActuatorLaunch*>(s.desc), v);
+    ActuatorRecord* const record = static_cast<ActuatorRecord*>(s.desc);
+    hipLaunchKernelGGL(write_actuator_launch_kernel, dim3(1), dim3(1), 0, b->stream, &record->a, v);
     HIP_TRY(b, hipGetLastError());
-    *out = static_cast<const ActuatorLaunch*>(s.desc);
+    if (D.pq) {
+        DelayLaunch w = {};
+        w.delay = q.d; w.queue = q.queue; w.head = q.head; w.d_max = q.d_max;
+        if (D.px) { w.model = block_pointer(model_source(b)); w.xhat = D.pe ? b->est.xhat : nullptr; }
+        hipLaunchKernelGGL(write_delay_launch_kernel, dim3(1), dim3(1), 0, b->stream, &record->d, w);
+        HIP_TRY(b, hipGetLastError());
+    }
+    *out = &record->a;
     return TINY_OK;
 }
 // the coverage path's actuator behind one single-step launch: one thread per (instance, input), the four stages of tiny_batch_set_actuator
@@ -522,7 +541,8 @@ static __global__ __launch_bounds__(256) void coverage_actuator_kernel(double* _
                                                                        const double* __restrict__ prim, const int4* __restrict__ status, const double* __restrict__ lo,
                                                                        const double* __restrict__ hi, const double* __restrict__ alpha, const double* __restrict__ gain,
                                                                        const double* __restrict__ offset, int installed, int per_instance, const double* __restrict__ noise,
-                                                                       int batch, int nx, int nu, int N) {
+                                                                       const int* __restrict__ delay, const int* __restrict__ head, double* __restrict__ queue, int d_max,
+                                                                       double* __restrict__ s0, int batch, int nx, int nu, int N) {
 #pragma clang fp contract(off)
     const size_t total = (size_t)batch * nu;
     for (size_t e = blockIdx.x * (size_t)blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
@@ -530,6 +550,15 @@ static __global__ __launch_bounds__(256) void coverage_actuator_kernel(double* _
         const size_t bb = e / nu, p = per_instance ? e : (size_t)c;
         if (status[bb].x <= 0) continue;
         double v = prim[bb * N * (nx + nu) + nx + c];
+        // stage 0, the transport delay: the oldest entry of the instance's ring leaves, the command takes its cell (the head is only
+        // read here: the threads of an instance's other inputs read it too -- coverage_queue_head_kernel moves it behind this kernel)
+        if (delay && delay[bb] > 0) {
+            double* const cell = queue + (bb * d_max + head[bb]) * nu + c;
+            const double uc = v;
+            v = *cell;
+            *cell = uc;
+        }
+        if (s0) s0[e] = v;
         if (installed) {
             const double l = lo ? lo[p] : -__builtin_huge_val(), h = hi ? hi[p] : __builtin_huge_val();
             v = v < l ? l : (v > h ? h : v);
@@ -545,15 +574,71 @@ static __global__ __launch_bounds__(256) void coverage_actuator_kernel(double* _
         if (log_row) log_row[e] = v;
     }
 }
-static int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row) {
+// ... and the head of every ring that popped and pushed: one thread per instance, behind the actuator helper
+static __global__ __launch_bounds__(256) void coverage_queue_head_kernel(int* __restrict__ head, const int* __restrict__ delay, const int4* __restrict__ status, int batch) {
+    for (int bb = blockIdx.x * blockDim.x + threadIdx.x; bb < batch; bb += gridDim.x * blockDim.x) {
+        const int d = delay[bb];
+        if (status[bb].x <= 0 || d <= 0) continue;
+        const int h = head[bb] + 1;
+        head[bb] = h < d ? h : 0;
+    }
+}
+static int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row, bool keep_s0) {
     Actuator& s = b->act;
+    ActuatorDelay& q = b->delay;
     const size_t total = (size_t)b->batch * b->nu;
     if (!s.ua) HIP_TRY(b, hipMalloc(&s.ua, total * sizeof(double)));
+    if (keep_s0 && !q.s0) HIP_TRY(b, hipMalloc(&q.s0, total * sizeof(double)));
+    const bool delayed = q.d_max > 0;
     const double* noise = (b->anoise.seq && step >= 0 && step < b->anoise.steps) ? b->anoise.seq + (size_t)step * total : nullptr;
     hipLaunchKernelGGL(coverage_actuator_kernel, dim3(helper_grid(b, total)), dim3(256), 0, b->stream, s.ua, s.lag ? s.state : nullptr,
                        (s.log.on && s.log.buf && log_row < s.log.rows) ? s.log.buf + (size_t)log_row * total : nullptr, b->d_prim, b->d_status, s.src[0], s.src[1],
-                       s.lag ? s.src[2] : nullptr, s.src[3], s.src[4], s.kind ? 1 : 0, s.kind == 2 ? 1 : 0, noise, b->batch, b->nx, b->nu, b->N);
+                       s.lag ? s.src[2] : nullptr, s.src[3], s.src[4], s.kind ? 1 : 0, s.kind == 2 ? 1 : 0, noise, delayed ? q.d : nullptr, q.head, q.queue, q.d_max,
+                       keep_s0 ? q.s0 : nullptr, b->batch, b->nx, b->nu, b->N);
     HIP_TRY(b, hipGetLastError());
+    if (delayed) {
+        hipLaunchKernelGGL(coverage_queue_head_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, q.head, q.d, b->d_status, b->batch);
+        HIP_TRY(b, hipGetLastError());
+    }
+    return TINY_OK;
+}
+// the coverage path's predictor in front of one single-step launch: one thread per instance, xs <- xin stepped d times by the MODEL over
+// the instance's queue as it stands, oldest first -- the chain of coverage_plant_step_kernel in explicit fma()s, what `compensated` does
+// on the one-row kernel, same bits.  d = 0: xin's own bits.  (nx <= 31: the two iterates in local arrays)
+static __global__ __launch_bounds__(256) void coverage_compensation_kernel(double* __restrict__ xs, const double* __restrict__ xin, const int* __restrict__ delay,
+                                                                           const int* __restrict__ head, const double* __restrict__ queue, int d_max,
+                                                                           const double* __restrict__ A_m, const double* __restrict__ B_m, const double* __restrict__ f_m,
+                                                                           int per_instance, int batch, int nx, int nu) {
+    for (int bb = blockIdx.x * blockDim.x + threadIdx.x; bb < batch; bb += gridDim.x * blockDim.x) {
+        const size_t p = per_instance ? (size_t)bb : 0;
+        const double *A = A_m + p * nx * nx, *B = B_m + p * nx * nu;
+        double cur[32], next[32];
+        for (int j = 0; j < nx; ++j) cur[j] = xin[(size_t)bb * nx + j];
+        const int d = delay[bb], h = head[bb];
+        for (int t = 0; t < d; ++t) {
+            const int at = h + t < d ? h + t : h + t - d;
+            const double* u = queue + ((size_t)bb * d_max + at) * nu;
+            for (int j = 0; j < nx; ++j) {
+                double acc = f_m ? f_m[p * nx + j] : 0.0;
+                for (int k = 0; k < nx; ++k) acc = fma(cur[k], A[j + nx * k], acc);
+                for (int k = 0; k < nu; ++k) acc = fma(u[k], B[j + nx * k], acc);
+                next[j] = acc;
+            }
+            for (int j = 0; j < nx; ++j) cur[j] = next[j];
+        }
+        for (int j = 0; j < nx; ++j) xs[(size_t)bb * nx + j] = cur[j];
+    }
+}
+static int enqueue_coverage_compensation(TinyBatch* b, const double** x0_of_launch) {
+    ActuatorDelay& q = b->delay;
+    if (b->nx > 32) return fail(b, TINY_ERR_UNSUPPORTED, "delay compensation: nx = %d (the helper kernel holds 32 states)", b->nx);
+    if (int rc = ensure_model_source(b, true)) return rc;
+    const PlantSource p = model_source(b);
+    if (!q.xs) HIP_TRY(b, hipMalloc(&q.xs, (size_t)b->batch * b->nx * sizeof(double)));
+    hipLaunchKernelGGL(coverage_compensation_kernel, dim3(helper_grid(b, (size_t)b->batch)), dim3(256), 0, b->stream, q.xs, *x0_of_launch, q.d, q.head, q.queue, q.d_max,
+                       p.src[0], p.src[1], p.src[2], p.per_instance ? 1 : 0, b->batch, b->nx, b->nu);
+    HIP_TRY(b, hipGetLastError());
+    *x0_of_launch = q.xs;
     return TINY_OK;
 }
 
@@ -561,6 +646,7 @@ static int enqueue_coverage_actuator(TinyBatch* b, long step, int log_row) {
 void closed_loop_facts(const TinyBatch* b, PathFacts& f) {
     f.disturbance = disturbance_active(b); f.plant = plant_active(b); f.state_log = state_log_active(b);
     f.measurement = measurement_active(b); f.estimator = estimator_active(b); f.score = score_active(b); f.actuator = actuator_active(b);
+    f.delay = delay_active(b); f.delay_compensation = compensation_active(b);
 }
 void note_closed_loop_read(TinyBatch* b) {
     b->dist.last = disturbance_active(b);             // (the one-row and the coverage kernel both add it; decide_path keeps such a launch off the tile kernel)
@@ -608,7 +694,7 @@ int bind_closed_loop_args(TinyBatch* b, const PathDecision& D, SolveArgs& a) {
     // an actuator model: the PA form of that.  Its int sits in the padding behind score_step0, its pointer over arho_max -- which no PA
     // launch reads; what the pointer names is written on the stream here, once per solve call
     if (D.pa) {
-        if (int rc = ensure_actuator_launch(b, a.steps, &a.act)) return rc;
+        if (int rc = ensure_actuator_launch(b, D, a.steps, &a.act)) return rc;
         a.act_step0 = kernel_step(b->anoise.step);
     }
     return TINY_OK;
@@ -636,6 +722,7 @@ void StepBases::apply(SolveArgs& a, int done, int batch, int nx) const {
 // none of measurement noise, estimator, actuator and plant the launch itself hands x0 on), the state log's row, the score
 int coverage_begin(TinyBatch* b, int steps, CoverageLoop& loop) {
     loop.noisy = b->meas.last; loop.filtered = b->est.last; loop.scoring = b->score.last; loop.actuated = b->act.last;
+    loop.compensated = loop.actuated && compensation_active(b);
     loop.own_plant = b->plant.last || loop.noisy || loop.filtered || loop.actuated;
     loop.state_log = state_log_active(b);
     if (loop.actuated) { if (int rc = begin_log_if_on(b, b->act.log, steps, b->nu)) return rc; }
@@ -649,11 +736,16 @@ int coverage_before_launch(TinyBatch* b, const CoverageLoop& loop, int s, Genera
     a.dist = (b->dist.last && dk >= 0 && dk < b->dist.steps) ? b->dist.seq + (size_t)dk * b->batch * b->nx : nullptr;
     if (loop.noisy) { if (int rc = enqueue_coverage_measurement(b, b->meas.step + s, &a.x0)) return rc; }
     if (loop.filtered) { if (!loop.noisy) a.x0 = b->d_x0; if (int rc = enqueue_coverage_correction(b, s, &a.x0)) return rc; }
+    // the delay's predictor: the launch solves from the model's prediction over the queue (of the x0 record itself with neither in front)
+    if (loop.compensated) { if (!loop.noisy && !loop.filtered) a.x0 = b->d_x0; if (int rc = enqueue_coverage_compensation(b, &a.x0)) return rc; }
     return TINY_OK;
 }
 int coverage_after_launch(TinyBatch* b, const CoverageLoop& loop, int s, const GeneralArgs& a) {
-    if (loop.filtered) { if (int rc = enqueue_coverage_prediction(b)) return rc; }
-    if (loop.actuated) { if (int rc = enqueue_coverage_actuator(b, b->anoise.step + s, s)) return rc; }
+    // (under delay compensation the prediction uses what the actuator helper took off the queue: it runs behind that helper)
+    const bool late_prediction = loop.filtered && loop.compensated;
+    if (loop.filtered && !late_prediction) { if (int rc = enqueue_coverage_prediction(b)) return rc; }
+    if (loop.actuated) { if (int rc = enqueue_coverage_actuator(b, b->anoise.step + s, s, late_prediction)) return rc; }
+    if (late_prediction) { if (int rc = enqueue_coverage_prediction(b, b->delay.s0)) return rc; }
     if (loop.own_plant) { if (int rc = enqueue_coverage_plant_step(b, a.dist)) return rc; }
     if (loop.state_log) { if (int rc = enqueue_state_log_row(b, s)) return rc; }
     if (loop.scoring) { if (int rc = enqueue_coverage_score(b, b->score.step + s)) return rc; }
@@ -1003,6 +1095,118 @@ int tiny_actuation_noise_generate(const TinyNoiseSpec* spec, int batch, int nu, 
     if (noise_spec_refusal(spec, nu) || (spec->flags & TINY_DEVICE) || !out || batch <= 0 || nu <= 0) return TINY_ERR_ARG;
     std::vector<double> g((size_t)2 * noise_pairs(nu));
     noise_fill_host(noise_fill_of(spec, 2, batch, nu, spec->scale, spec->mean), out, g.data());
+    return TINY_OK;
+}
+// a transport delay in front of the actuator's stages: d [batch] ints (TINY_BROADCAST: one), 0 <= d[i] <= d_max <= TINY_MAX_DELAY.
+// Installing or replacing one fills the queue with +0.0 and rewinds every ring; d == NULL or d_max <= 0 removes it.  The values are
+// checked on the host (a device array is read back); everything that can fail happens before anything installed is touched
+int tiny_batch_set_actuator_delay(TinyBatch* b, const int* d, int d_max, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    HIP_TRY(b, hipSetDevice(b->device));
+    ActuatorDelay& s = b->delay;
+    if (flags & ~(TINY_DEVICE | TINY_BROADCAST)) return fail(b, TINY_ERR_ARG, "actuator delay: flags 0x%x (TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST)", flags);
+    if (!d || d_max <= 0) {                                              // remove: freed once the stream has run dry of its readers
+        if (s.d_max) { if (int rc = drop_buffers(b, s)) return rc; }
+        s.d_max = 0;
+        return TINY_OK;
+    }
+    if (d_max > TINY_MAX_DELAY) return fail(b, TINY_ERR_ARG, "actuator delay: d_max %d (at most TINY_MAX_DELAY = %d)", d_max, TINY_MAX_DELAY);
+    const size_t given = (flags & TINY_BROADCAST) ? 1 : (size_t)b->batch;
+    std::vector<int> h((size_t)b->batch);
+    if (flags & TINY_DEVICE) HIP_TRY(b, hipMemcpy(h.data(), d, given * sizeof(int), hipMemcpyDeviceToHost));
+    else std::copy(d, d + given, h.begin());
+    if (given == 1) std::fill(h.begin(), h.end(), h[0]);
+    for (size_t i = 0; i < h.size(); ++i)
+        if (h[i] < 0 || h[i] > d_max) return fail(b, TINY_ERR_ARG, "actuator delay: d = %d at instance %zu (0 .. d_max = %d)", h[i], given == 1 ? (size_t)0 : i, d_max);
+    const size_t cells = (size_t)b->batch * d_max * b->nu;
+    int *fd = nullptr, *fh = nullptr;
+    double* fq = nullptr;
+    hipError_t err = hipMalloc(&fd, h.size() * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&fh, h.size() * sizeof(int));
+    if (err == hipSuccess) err = hipMalloc(&fq, cells * sizeof(double));
+    if (err == hipSuccess) err = hipMemcpyAsync(fd, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, b->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(fh, 0, h.size() * sizeof(int), b->stream);
+    if (err == hipSuccess) err = hipMemsetAsync(fq, 0, cells * sizeof(double), b->stream);          // (+0.0: all bits zero)
+    if (err == hipSuccess) err = hipStreamSynchronize(b->stream);       // (h may go; nothing reads the old arrays any more)
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        if (fd) (void)hipFree(fd);
+        if (fh) (void)hipFree(fh);
+        if (fq) (void)hipFree(fq);
+        return fail(b, TINY_ERR_HIP, "actuator delay: %s", hipGetErrorString(err));
+    }
+    free_buffers(s);                                                     // (the scratch arrays come back with the launch that needs them)
+    s.d = fd; s.head = fh; s.queue = fq; s.d_max = d_max;
+    return TINY_OK;
+}
+int tiny_batch_get_actuator_delay(TinyBatch* b, int instance, int* d_out) {
+    if (!b) return TINY_ERR_NULL;
+    if (!b->delay.d_max) return fail(b, TINY_ERR_ARG, "no actuator delay installed (tiny_batch_set_actuator_delay)");
+    if (!d_out) return fail(b, TINY_ERR_ARG, "null output");
+    if (instance < 0 || instance >= b->batch) return fail(b, TINY_ERR_ARG, "instance %d of %d", instance, b->batch);
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    HIP_TRY(b, hipMemcpy(d_out, b->delay.d + instance, sizeof(int), hipMemcpyDeviceToHost));
+    return TINY_OK;
+}
+// the queue: q [batch][d_max][nu], oldest first (TINY_BROADCAST: [d_max][nu]); every ring is rewound, so that row t of an instance is its
+// t-th oldest entry.  The fresh array is complete before it takes the place of the one installed
+int tiny_batch_set_actuator_queue(TinyBatch* b, const double* q, int flags) {
+    if (!b) return TINY_ERR_NULL;
+    ActuatorDelay& s = b->delay;
+    if (!s.d_max) return fail(b, TINY_ERR_ARG, "no actuator delay installed (tiny_batch_set_actuator_delay)");
+    if (!q) return fail(b, TINY_ERR_ARG, "null actuator queue");
+    if (flags & ~(TINY_DEVICE | TINY_BROADCAST)) return fail(b, TINY_ERR_ARG, "actuator queue: flags 0x%x (TINY_HOST or TINY_DEVICE, with or without TINY_BROADCAST)", flags);
+    HIP_TRY(b, hipSetDevice(b->device));
+    const size_t slice = (size_t)s.d_max * b->nu, cells = (size_t)b->batch * slice;
+    const UploadPart given = {q, (flags & TINY_BROADCAST) ? slice : cells};
+    double* fresh = nullptr;
+    if (int rc = upload_fresh(b, &given, &fresh, 1, flags, "actuator queue")) return rc;
+    if (flags & TINY_BROADCAST) {                                        // one slice for all: expanded as a broadcast sequence of one step
+        double* full = nullptr;
+        hipError_t err = hipMalloc(&full, cells * sizeof(double));
+        int rc = TINY_OK;
+        if (err == hipSuccess) rc = expand_disturbance(b, full, fresh, 1, (int)slice);
+        if (err == hipSuccess && rc == TINY_OK) err = hipStreamSynchronize(b->stream);
+        (void)hipFree(fresh);
+        if (err != hipSuccess || rc != TINY_OK) {
+            (void)hipGetLastError();
+            if (full) (void)hipFree(full);
+            return rc != TINY_OK ? rc : fail(b, TINY_ERR_HIP, "actuator queue: %s", hipGetErrorString(err));
+        }
+        fresh = full;
+    }
+    // (everything fallible is behind us but the rewind itself: where that fails the fresh array goes and the queue installed stays)
+    hipError_t err = hipStreamSynchronize(b->stream);                    // (nothing reads the old queue any more)
+    if (err == hipSuccess) err = hipMemset(s.head, 0, (size_t)b->batch * sizeof(int));
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(fresh);
+        return fail(b, TINY_ERR_HIP, "actuator queue: %s", hipGetErrorString(err));
+    }
+    (void)hipFree(s.queue);
+    s.queue = fresh;
+    return TINY_OK;
+}
+// ... on the host, oldest first: the first d[i] rows of an instance's slice, +0.0 behind them
+int tiny_batch_get_actuator_queue(TinyBatch* b, double* q_out) {
+    if (!b) return TINY_ERR_NULL;
+    const ActuatorDelay& s = b->delay;
+    if (!s.d_max) return fail(b, TINY_ERR_ARG, "no actuator delay installed (tiny_batch_set_actuator_delay)");
+    if (!q_out) return fail(b, TINY_ERR_ARG, "null output");
+    HIP_TRY(b, hipSetDevice(b->device));
+    HIP_TRY(b, hipStreamSynchronize(b->stream));
+    const size_t nu = (size_t)b->nu, slice = (size_t)s.d_max * nu;
+    std::vector<int> d((size_t)b->batch), head((size_t)b->batch);
+    std::vector<double> ring((size_t)b->batch * slice);
+    HIP_TRY(b, hipMemcpy(d.data(), s.d, d.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(head.data(), s.head, head.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(b, hipMemcpy(ring.data(), s.queue, ring.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < d.size(); ++i)
+        for (int t = 0; t < s.d_max; ++t) {
+            const int at = t < d[i] ? (head[i] + t) % d[i] : 0;
+            for (size_t c = 0; c < nu; ++c) q_out[i * slice + (size_t)t * nu + c] = t < d[i] ? ring[i * slice + (size_t)at * nu + c] : 0.0;
+        }
     return TINY_OK;
 }
 // the applied control of every MPC step of the last solve call (option "actuation_log"): ua [steps][batch][nu]

@@ -76,7 +76,7 @@ struct StepBases {                                                    // the fou
     void capture(const JitKey& k, const SolveArgs& a);                // off the arguments as bound, by the forms the launch takes
     void apply(SolveArgs& a, int done, int batch, int nx) const;      // the stretch that starts `done` steps in
 };
-struct CoverageLoop { bool noisy = false, filtered = false, scoring = false, actuated = false, own_plant = false, state_log = false; };
+struct CoverageLoop { bool noisy = false, filtered = false, scoring = false, actuated = false, own_plant = false, state_log = false, compensated = false; };
 int coverage_begin(TinyBatch* b, int steps, CoverageLoop& loop);      // which helper kernels the coverage path's single-step launches take; the logs sized
 int coverage_before_launch(TinyBatch* b, const CoverageLoop& loop, int s, GeneralArgs& a);        // step s: this step's disturbance block, the measurement, the correction -> a.dist, a.x0
 int coverage_after_launch(TinyBatch* b, const CoverageLoop& loop, int s, const GeneralArgs& a);   // step s: prediction, actuator, plant step, state log row, score

@@ -157,7 +157,7 @@ struct TinyBatch {
     // every instance its own problem data, one struct per family (above); setters, getters, drops and the ensure_* builds: batch_instance.hip
     InstanceBox ibox; InstanceHalfspaces ilin; InstanceCones icone;
     // the stages at the fused closed-loop plant step (closed_loop.hpp); setters, getters and what a launch does with them: batch_closed_loop.hip
-    Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score; Actuator act; StepSequence anoise; ModelBlock model;
+    Disturbance dist; PlantStep plant; MeasurementNoise meas; Estimator est; Score score; Actuator act; StepSequence anoise; ActuatorDelay delay; ModelBlock model;
     bool xref_shared = true, uref_shared = true;   // the Xref / Uref records of all instances are identical (broadcast, or still zero)
     bool share_ref = true;                         // option "share_ref": let launches exploit that
     int half_rows = -1;                  // option "half_rows": the one-row kernel's HALF form (nx+nu <= 8, eight instances per wave) where it exists; 0 = off

@@ -1,6 +1,6 @@
 // closed_loop.hpp -- the state of the stages at the fused closed-loop plant step (batch_closed_loop.hip sets, builds, reads and drops
 // it; TinyBatch of batch_impl.hpp holds one member per stage): a disturbance, a plant of its own with the state log, measurement
-// noise, a state estimator, a score, an actuator model with actuation noise.  One shape per kind of state: StepSequence (a step-major
+// noise, a state estimator, a score, an actuator model with actuation noise and a transport delay in front of it.  One shape per kind of state: StepSequence (a step-major
 // sequence and its counter), StepLog (what every MPC step of the last solve call left), ModelBlock (the batch's own model as a plant
 // block), and per stage the caller's arrays `src` next to the lane block `built` the one-row kernel reads.  Plain C++, no HIP call.
 // Every struct names the device buffers it owns in each_buffer: the drop paths and tiny_batch_destroy free through it, nothing else
@@ -101,6 +101,20 @@ struct Actuator {
     StepLog log;                                   // rows of nu entries
     void* desc = nullptr;
     template <class F> void each_buffer(F f) { for (double*& p : src) f(p); f(built); f(state); f(ua); f(log.buf); f(desc); }
+};
+// a transport delay in front of the actuator's stages (tiny_batch_set_actuator_delay) and the predictor that compensates it (option
+// "delay_compensation").  d [batch] ints: every instance's delay in MPC steps, 0 .. d_max; queue [batch][d_max][nu]: the instance's last
+// d commands, STATE of the batch like the lag's record -- a ring over the instance's first d rows; head [batch] ints: the row of the
+// oldest entry (the getter unrolls it: how the device stores the queue is not observable).  s0 [batch][nu]: where the coverage path's
+// actuator helper puts what left the queue, for the estimator's prediction helper under compensation; xs [batch][nx]: where the coverage
+// path forms the predicted states its launch takes as x0.  On the one-row kernel the PQ / PX forms read all of it through the actuator's
+// launch record (Actuator::desc)
+struct ActuatorDelay {
+    int d_max = 0;                                 // 0: none installed
+    bool compensate = false;                       // option "delay_compensation" (inert with no delay installed)
+    int *d = nullptr, *head = nullptr;
+    double *queue = nullptr, *s0 = nullptr, *xs = nullptr;
+    template <class F> void each_buffer(F f) { f(d); f(head); f(queue); f(s0); f(xs); }
 };
 
 namespace tinympc_amd {

@@ -475,6 +475,37 @@ int tiny_group_set_actuation_noise(TinyGroup* g, const double* n, int n_steps, i
 int tiny_group_generate_actuation_noise(TinyGroup* g, const TinyNoiseSpec* spec) {
     return group_generate(g, spec, tiny_batch_generate_actuation_noise, "generated actuation noise", true);
 }
+// the transport delay (tiny_batch_set_actuator_delay): d [batch] ints over the full batch axis in host memory, the caller's instance
+// order; each shard gets its instances' (TINY_BROADCAST: the one, as it is); d == NULL or d_max <= 0 removes.  The queue
+// (tiny_batch_set_actuator_queue): slices of d_max * nu doubles, d_max as the shards have it installed
+int tiny_group_set_actuator_delay(TinyGroup* g, const int* d, int d_max, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    if (flags & TINY_DEVICE) return gfail(g, TINY_ERR_ARG, "actuator delay of a group: host arrays (TINY_HOST)");
+    const bool pass = !d || d_max <= 0 || (flags & TINY_BROADCAST);
+    // (the whole array is checked before any shard is touched: a refused call leaves every shard as it was)
+    if (d && d_max > 0) {
+        if (flags & ~TINY_BROADCAST) return gfail(g, TINY_ERR_ARG, "actuator delay of a group: flags 0x%x (TINY_HOST, with or without TINY_BROADCAST)", flags);
+        if (d_max > TINY_MAX_DELAY) return gfail(g, TINY_ERR_ARG, "actuator delay: d_max %d (at most TINY_MAX_DELAY = %d)", d_max, TINY_MAX_DELAY);
+        const long n = (flags & TINY_BROADCAST) ? 1 : (long)g->batch;
+        for (long i = 0; i < n; ++i)
+            if (d[i] < 0 || d[i] > d_max) return gfail(g, TINY_ERR_ARG, "actuator delay: d = %d at instance %ld (0 .. d_max = %d)", d[i], i, d_max);
+    }
+    std::vector<int> stage;
+    for (int k = 0; k < g->n; ++k) {
+        if (!pass) {
+            stage.resize((size_t)g->count[k] + 1);
+            for (long i = 0; i < g->count[k]; ++i) stage[(size_t)i] = d[global_index(g, k, i)];
+        }
+        const int rc = tiny_batch_set_actuator_delay(g->shard[k], pass ? d : stage.data(), d_max, pass ? flags : TINY_HOST);
+        if (rc) return gfail(g, rc, "shard %d: %s", k, tiny_batch_last_error(g->shard[k]));
+    }
+    return TINY_OK;
+}
+int tiny_group_set_actuator_queue(TinyGroup* g, const double* q, int flags) {
+    if (!g) return TINY_ERR_NULL;
+    const long d_max = g->n > 0 ? tiny_batch_get_option(g->shard[0], "actuator_delay") : 0;
+    return group_set_rows(g, q, (size_t)(d_max > 0 ? d_max : 0) * g->nu, flags, tiny_batch_set_actuator_queue, "actuator queue");
+}
 int tiny_group_update_settings(TinyGroup* g, double abs_pri_tol, double abs_dua_tol, int max_iter, int check_termination,
                                int en_state_bound, int en_input_bound, int en_state_soc, int en_input_soc, int en_state_linear,
                                int en_input_linear, int en_tv_state_linear, int en_tv_input_linear) {

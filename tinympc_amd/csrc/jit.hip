@@ -303,7 +303,7 @@ hipFunction_t jit_solve_kernel(const JitKey& k, std::string* err) {
     // instance its own cone coefficients, bit 4, PD, every instance its own disturbance at the plant step, bit 5, PP, a plant of its own there, bit 6, PM, the solve from a measured state, bit 7, PE, a state estimator in front of it, bit 8, PS, a closed-loop score at the plant step, bit 9, PA, an actuator model in front of it, bit 10: the name of every form
     // without them is what it was)
     snprintf(name, sizeof(name), "tinympc_amd::admm_solve_kernel<%d, %d, %d, %s, %s, %d, %d, %s, %d, %s%s>", k.nx, k.nu, k.N,
-             k.soc ? "true" : "false", k.dbg ? "true" : "false", k.mode | (k.pb ? 4 : 0) | (k.pl ? 8 : 0) | (k.pc ? 16 : 0) | (k.pd ? 32 : 0) | (k.pp ? 64 : 0) | (k.pm ? 128 : 0) | (k.pe ? 256 : 0) | (k.ps ? 512 : 0) | (k.pa ? 1024 : 0), k.lin, k.het ? "true" : "false", k.kmax, k.adapt ? "true" : "false", k.ub ? ", true" : "");
+             k.soc ? "true" : "false", k.dbg ? "true" : "false", k.mode | (k.pb ? 4 : 0) | (k.pl ? 8 : 0) | (k.pc ? 16 : 0) | (k.pd ? 32 : 0) | (k.pp ? 64 : 0) | (k.pm ? 128 : 0) | (k.pe ? 256 : 0) | (k.ps ? 512 : 0) | (k.pa ? 1024 : 0) | (k.pq ? 4096 : 0) | (k.px ? 8192 : 0), k.lin, k.het ? "true" : "false", k.kmax, k.adapt ? "true" : "false", k.ub ? ", true" : "");
     return get(name, false, err);
 }
 

@@ -21,10 +21,12 @@ struct JitKey {
     int pe = 0;               // a state estimator between the measurement and the solve (admm_kernel.hip.h PE): run-time instantiated only, with pm and pp
     int ps = 0;               // a closed-loop score at the plant step (admm_kernel.hip.h PS): run-time instantiated only, with pd or pp
     int pa = 0;               // an actuator model between the command and the plant step (admm_kernel.hip.h PA): run-time instantiated only, with pp
+    int pq = 0;               // a transport delay in front of the actuator's stages (admm_kernel.hip.h PQ): run-time instantiated only, with pa
+    int px = 0;               // the solve runs from the model's prediction over the delay's queue (admm_kernel.hip.h PX): run-time instantiated only, with pq and pm
     bool operator<(const JitKey& o) const {
-        const int a[20] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd, pp, pm, pe, ps, pa},
-                  b[20] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd, o.pp, o.pm, o.pe, o.ps, o.pa};
-        for (int i = 0; i < 20; ++i)
+        const int a[22] = {nx, nu, N, soc, dbg, mode, lin, het, kmax, adapt, ub, pb, pl, pc, pd, pp, pm, pe, ps, pa, pq, px},
+                  b[22] = {o.nx, o.nu, o.N, o.soc, o.dbg, o.mode, o.lin, o.het, o.kmax, o.adapt, o.ub, o.pb, o.pl, o.pc, o.pd, o.pp, o.pm, o.pe, o.ps, o.pa, o.pq, o.px};
+        for (int i = 0; i < 22; ++i)
             if (a[i] != b[i]) return a[i] < b[i];
         return false;
     }
@@ -81,6 +83,8 @@ struct VariantFacts {
     bool pe = false;                   // the state-estimator form: bit 8, always with bits 7 and 6
     bool ps = false;                   // the closed-loop-score form: bit 9, always with bit 5 or bit 6
     bool pa = false;                   // the actuator-model form: bit 10, always with bit 6
+    bool pq = false;                   // the transport-delay form: bit 12, always with bit 10 (bit 11 names no form)
+    bool px = false;                   // the delay-predictor form: bit 13, always with bits 12 and 7
     // ---- from the problem
     bool soc = false, debug = false;
     int dpp_mode = 0;                  // option "dpp_mode" as set (values outside 0..2 count as 0)
@@ -122,7 +126,8 @@ inline bool variant_facts_consistent(const VariantFacts& f, const EntrySlots& s)
            !(f.pm && !f.pp) &&                                                                     // (... and a PM form is a PP form)
            !(f.pe && !f.pm) &&                                                                     // (... and a PE form is a PM form)
            !(f.ps && !(f.pd || f.pp)) &&                                                           // (... and a PS form is a PD or a PP form)
-           !(f.pa && !f.pp);                                                                       // (... and a PA form is a PP form)
+           !(f.pa && !f.pp) &&                                                                     // (... and a PA form is a PP form)
+           !(f.pq && !f.pa) && !(f.px && !(f.pq && f.pm));                                         // (... a PQ form a PA form, a PX form a PQ and a PM form)
 }
 
 struct VariantChoice {
@@ -160,6 +165,7 @@ inline VariantChoice choose_one_row_variant(const VariantFacts& f, const EntrySl
     // take one: their conditions, asked of the key, since no rung is)
     if (f.pd || f.pp) {                                                  // (PP: PD's rule, bit for bit)
         k.pd = f.pd ? 1 : 0; k.pp = f.pp ? 1 : 0; k.pm = (f.pp && f.pm) ? 1 : 0; k.pe = (k.pm && f.pe) ? 1 : 0; k.ps = f.ps ? 1 : 0; k.pa = (f.pp && f.pa) ? 1 : 0;
+        k.pq = (k.pa && f.pq) ? 1 : 0; k.px = (k.pq && k.pm && f.px) ? 1 : 0;
         if (!k.pb && !k.pc && !k.lin && !k.adapt && !dbg && k.mode == 2) k.ub = (f.uniform_ub && (!f.hetero || f.het_ub)) ? 1 : 0;
     }
     SlotRef want;

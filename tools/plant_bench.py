@@ -34,6 +34,8 @@ by what the PP form costs -- and what the host-in-the-loop form it replaces cost
 --score host        what it took before: nothing installed, "state_log" and "step_log" on, both logs pulled to the host after the
                     episode and scored there in numpy (the same arithmetic, vectorised over the instances); wall_ms is the episode with all
                     of that.  Both need --steps > 1
+--delay D [--compensate]  a transport delay of D MPC steps in front of the actuator's stages (tiny_batch_set_actuator_delay: the PQ forms), every
+                    instance the same and the queue emptied before every episode; with --compensate option "delay_compensation" (the PX forms)
 --actuator neutral  an actuator model installed (tiny_batch_set_actuator) that changes nothing: every instance its own gain of ones, no other
                     stage.  The applied control is the command bit for bit, so a PA form solves exactly the problems the same form without
                     it solves (--plant shared: the PP form; with --noise 0 --estimator G --score device: the PE + PS form), and the times
@@ -71,7 +73,13 @@ def main():
     ap.add_argument("--estimator-shared", type=int, default=0, help="1: ONE gain for all (TINY_BROADCAST) instead of [batch] copies")
     ap.add_argument("--score", choices=("device", "host"), default=None, help="a closed-loop score on the device, or both logs pulled and scored in numpy")
     ap.add_argument("--actuator", choices=("neutral", "device", "host"), default=None, help="an actuator model: one that changes nothing, the whole model, or its stages in numpy (with --plant host)")
+    ap.add_argument("--delay", type=int, default=0, help="a transport delay of D MPC steps in front of the actuator's stages, every instance the same (tiny_batch_set_actuator_delay)")
+    ap.add_argument("--compensate", action="store_true", help="with --delay: option delay_compensation, every step solves from the model's prediction over the queue")
     a = ap.parse_args()
+    if a.compensate and a.delay <= 0:
+        ap.error("--compensate needs --delay D")
+    if a.delay < 0 or a.delay > 8:
+        ap.error("--delay: 0 .. 8 MPC steps (TINY_MAX_DELAY)")
     noise_source = a.noise if a.noise in ("generated", "host") else None
     a.noise = None if (a.noise is None or noise_source) else float(a.noise)
     sys.path.insert(0, a.package)
@@ -186,6 +194,9 @@ def main():
         elif a.actuator == "device":
             s.set_actuator(act_lo, act_hi, act_alpha, act_gain)
             s.generate_actuation_noise(7, a.steps if a.steps > 1 else a.warmup + launches, act_scale)
+        if a.delay > 0:
+            s.set_actuator_delay(np.full(B, a.delay, dtype=np.int32), a.delay)
+            s.set_option("delay_compensation", int(a.compensate))
         wall, scored = [], None
         if a.score is not None:
             lim = m if a.workload == "rocket" else h
@@ -226,6 +237,8 @@ def main():
                 if a.actuator == "device":
                     s.set_option("actuation_step", 0)
                     s.set_actuator_state(np.zeros(nu))
+                if a.delay > 0:
+                    s.set_actuator_queue(np.zeros((a.delay, nu)))
                 if a.estimator is not None:
                     s.set_estimate(s.get("x0"))
                 s.set_option("timing", 1)
@@ -276,6 +289,8 @@ def main():
                    actuation_noise=int(s.get_option("actuation_noise")))
         if wall:
             out.update(wall_median_ms=float(np.median(wall)), wall_min_ms=float(min(wall)), wall_max_ms=float(max(wall)))
+    if a.delay > 0:
+        out.update(delay=a.delay, compensate=int(a.compensate), actuator_delay=int(s.get_option("actuator_delay")), last_actuator=int(s.get_option("last_actuator")))
     if a.actuator == "host":
         out.update(actuator="host", host_cost_median=float(np.median(host_cost)))
     if a.score is not None and a.steps > 1:
